@@ -14,6 +14,13 @@ Synthetic data: a unique corpus of --unique-mb MB is generated on the host
 and tiled on the device up to --corpus-gb (every tile is its own set of
 partitions with its own seeds).  See DESIGN.md "Measurement".
 
+A plain run does what the headline needs and no more: set up, warm up, time
+--steps steps, write the last step's outputs with --dump-outputs DIR, print
+the line.  --full adds, outside the timed region, everything else the
+benchmark measures or checks (the preprocessor CLI legs, the parquet writer
+sample, the CPU baseline, the oracle check of one full-size partition, the
+other BASELINE workloads as legs).
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -55,6 +62,16 @@ def parse():
                   help='the step\'s row output: spans of the dense ids (lddl_row_spans, what the writer renders '
                        'from; with --masking + lddl_masked_lm_spans) or materialised token rows (lddl_materialize '
                        '[+ lddl_masked_lm])')
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline also run everything else the benchmark measures or checks: the CLI '
+                       'front-end legs, the parquet writer sample, the CPU baseline, the oracle check of one '
+                       'full-size partition, the replica check and the other BASELINE workloads (--legs).  Off by '
+                       'default: a plain run sets up, warms up, times --steps steps and prints the line.  The '
+                       'options below that size or switch off one of those parts act under --full only')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='after the timed steps write what the last timed step returned (the tokenizer\'s ids / '
+                       'counts and the pack result\'s columns; fixed seeded samples of the large ones, whole-array '
+                       'checksums of all) as DIR/<name>.npy, float32 / float64, under 64 MB in all (rank 0)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-sample-check', action='store_true',
                   help='skip the oracle comparison of one full-size partition after the timed steps')
@@ -88,6 +105,8 @@ def parse():
                   help='with --launch-check: every rank also runs the library build (a no-op after the launching '
                        'process built it), loads the library and reports its SHA-1')
   args = ap.parse_args()
+  if args.steps < 1 or args.warmup < 0:
+    ap.error('--steps must be at least 1 and --warmup at least 0')
   code = args.corpus == 'code'
   if args.unique_mb is None:
     args.unique_mb = 16 if code else 256
@@ -634,6 +653,94 @@ def run_leg(args, name, local, device, shards=None):
   return out
 
 
+DUMP_SEED = 20261019
+DUMP_ROWS = 1 << 18     # sampled rows of the per-row columns
+DUMP_TOKENS = 1 << 21   # sampled entries of the dense ids / the materialised rows
+DUMP_SENTS = 1 << 20    # sampled sentences of the token counts
+DUMP_MASKED = 1 << 20   # sampled masked positions
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample_index(n, k, salt, device):
+  """k sorted indices into [0, n): the same fractions of n on every run
+  (all of [0, n) when n <= k)"""
+  if n <= k:
+    return torch.arange(n, dtype=torch.int64, device=device)
+  u = np.random.RandomState(DUMP_SEED + salt).random_sample(k)
+  return torch.from_numpy(np.sort(np.minimum((u * n).astype(np.int64), n - 1))).to(device)
+
+
+def _checksum(t, n):
+  """the sum of t[:n] modulo 2^32 (exact: int64 partial sums of 2^26
+  entries; int16 views of uint16 sum as the signed values they hold)"""
+  s = 0
+  for i in range(0, n, 1 << 26):
+    s = (s + int(t[i:min(n, i + (1 << 26))].sum(dtype=torch.int64).item())) & 0xFFFFFFFF
+  return float(s)
+
+
+def dump_outputs(d, res, ntok, n_sent, n_tok):
+  """--dump-outputs: what the last timed step handed back, as d/<name>.npy.
+  The tokenizer's dense ids and per-sentence counts, and every column of the
+  pack result (row spans or materialised rows, lengths, flags, bins,
+  partitions, per-(partition, bin) counts, the masked-LM columns with
+  --masking).  bin_count and the totals are whole; of the large arrays a
+  fixed seeded sample of entries (the sampled rows are the same for every
+  per-row column) as float32 (values below 2^24) or float64 (offsets), and
+  checksums.npy holds the sum modulo 2^32 of each whole array in the order
+  of checksum_names.npy's rows (the names' bytes, zero padded)."""
+  os.makedirs(d, exist_ok=True)
+  dev = ntok.device
+  n = res.n_pairs
+  out, sums = {}, {}
+
+  def u16(t):  # int16 views of uint16 values -> the values
+    return (t.to(torch.int32) & 0xFFFF).to(torch.float32)
+
+  def take(name, t, count, idx, conv):
+    sums[name] = _checksum(t, count)
+    out[name] = conv(t[idx]).cpu().numpy()
+
+  f32 = lambda t: t.to(torch.float32)  # noqa: E731
+  f64 = lambda t: t.to(torch.float64)  # noqa: E731
+  out['totals'] = np.array([n_sent, n_tok, n, res.n_tokens, res.n_masked, res.nbins], np.float64)
+  take('ntok', ntok, n_sent, _sample_index(n_sent, DUMP_SENTS, 1, dev), f32)
+  take('ids', res.ids, n_tok, _sample_index(n_tok, DUMP_TOKENS, 2, dev), u16)
+  rows = _sample_index(n, DUMP_ROWS, 3, dev)
+  out['sampled_rows'] = rows.cpu().numpy().astype(np.float64)
+  take('tok_off', res.tok_off, n + 1, rows, f64)
+  take('len0', res.len0, n, rows, u16)
+  take('len1', res.len1, n, rows, u16)
+  take('flags', res.flags, n, rows, f32)
+  take('bins', res.bins, n, rows, f32)
+  take('part', res.part, n, rows, f64)
+  bc = res.bin_count.reshape(-1)
+  take('bin_count', bc, bc.numel(), torch.arange(bc.numel(), device=dev), f64)
+  out['bin_count'] = out['bin_count'].reshape(tuple(res.bin_count.shape))
+  if res.spans:
+    take('src0', res.src0, n, rows, f64)
+    take('src1', res.src1, n, rows, f64)
+  else:
+    take('tokens', res.tokens, res.n_tokens, _sample_index(res.n_tokens, DUMP_TOKENS, 4, dev), u16)
+  if res.mlm_off is not None:
+    take('mlm_off', res.mlm_off, n + 1, rows, f64)
+    mi = _sample_index(res.n_masked, DUMP_MASKED, 5, dev)
+    take('mlm_pos', res.mlm_pos, res.n_masked, mi, u16)
+    take('mlm_label', res.mlm_label, res.n_masked, mi, u16)
+    if res.mlm_token is not None:
+      take('mlm_token', res.mlm_token, res.n_masked, mi, u16)
+  names = sorted(sums)
+  out['checksums'] = np.array([sums[k] for k in names], np.float64)
+  w = max(len(k) for k in names)
+  out['checksum_names'] = np.array([list(k.encode().ljust(w, b'\0')) for k in names], np.float32)
+  total = sum(a.nbytes for a in out.values())
+  if total > DUMP_MAX_BYTES:
+    raise RuntimeError('--dump-outputs: %d bytes, over the %d allowed' % (total, DUMP_MAX_BYTES))
+  for k, a in out.items():
+    np.save(os.path.join(d, k + '.npy'), a)
+  return {'dir': d, 'arrays': len(out), 'bytes': total}
+
+
 _T0 = time.perf_counter()
 
 
@@ -660,7 +767,7 @@ def main():
   # the writer sample's encode processes, forked while the process is GPU-free
   # (LDDL_ENCODE_PROCS=0: the thread pool instead)
   enc = None
-  if args.parquet_parts > 0 and os.environ.get('LDDL_ENCODE_PROCS', '1') != '0':
+  if args.full and args.parquet_parts > 0 and os.environ.get('LDDL_ENCODE_PROCS', '1') != '0':
     from lddl_amd import writer
     enc = writer.ProcessEncoder()
   def cli_leg(*a, **kw):  # (a failed CLI leg is recorded in the line; the headline still runs)
@@ -669,10 +776,10 @@ def main():
     except Exception as e:  # noqa: BLE001
       return {'error': '%s: %s' % (type(e).__name__, e)}
 
-  fe = cli_leg(args.frontend_mb) if world == 1 and args.frontend_mb > 0 else None
+  fe = cli_leg(args.frontend_mb) if args.full and world == 1 and args.frontend_mb > 0 else None
   progress(rank, 'frontend leg done')
   fe2 = (cli_leg(args.frontend_c2_mb, seq=512, bin_size=64)
-         if world == 1 and args.frontend_c2_mb > 0 else None)
+         if args.full and world == 1 and args.frontend_c2_mb > 0 else None)
   torch.cuda.set_device(local)
   device = torch.device('cuda', local)
   dist = None
@@ -766,11 +873,12 @@ def main():
     dist.barrier()
   el = time.perf_counter() - t0
   n_tok = int(ntok[:sh.n_sent].sum().item())
-  # full-size property check (outside the timed region): every replica of the
-  # unique corpus must tokenize to the same number of tokens
-  per_rep = ntok[:reps * base.n_sent].view(reps, base.n_sent).to(torch.int64).sum(1)
-  if not bool((per_rep == per_rep[0]).all()):
-    raise RuntimeError('tokenize: replicas disagree: %s' % per_rep.tolist()[:16])
+  if args.full:
+    # full-size property check (outside the timed region): every replica of the
+    # unique corpus must tokenize to the same number of tokens
+    per_rep = ntok[:reps * base.n_sent].view(reps, base.n_sent).to(torch.int64).sum(1)
+    if not bool((per_rep == per_rep[0]).all()):
+      raise RuntimeError('tokenize: replicas disagree: %s' % per_rep.tolist()[:16])
   tk = float(np.mean([a.elapsed_time(b) for a, b in tok_ms]))
   ks = pk.tok.stats()  # the last timed step's tokenize kernels
   if not ks['launches'] or ks['scan_ms'] <= 0:
@@ -861,7 +969,11 @@ def main():
   except (OSError, ValueError, KeyError):
     pass
   progress(rank, 'timed steps done')
-  if args.parquet_parts > 0:
+  line['full'] = bool(args.full)
+  if args.dump_outputs:
+    line['dump_outputs'] = dump_outputs(args.dump_outputs, res, ntok, sh.n_sent, n_tok)
+    progress(rank, 'outputs written')
+  if args.full and args.parquet_parts > 0:
     try:
       line['parquet_writer'] = parquet_sample(args, pk, res, sh, enc)
     except Exception as e:  # (recorded: the headline line still prints)
@@ -872,7 +984,7 @@ def main():
     line['frontend'] = fe
   if fe2 is not None:
     line['frontend_c2'] = fe2
-  if not args.no_cpu_baseline and world == 1:  # the host leg (the oracle): rank 0 at N=1 only
+  if args.full and not args.no_cpu_baseline and world == 1:  # the host leg (the oracle): rank 0 at N=1 only
     progress(rank, 'cpu baseline')
     try:
       line['cpu_baseline'] = cpu_baseline(args, base, pdo, args.cpu_seconds)
@@ -883,7 +995,7 @@ def main():
         line['cpu_baseline']['sample_check'] = sample_partition_check(args, pk, res, base, pdo, reps, kw['seed'])
       except Exception as e:  # (recorded, never as a pass: identical is absent)
         line['cpu_baseline']['sample_check'] = {'error': '%s: %s' % (type(e).__name__, e)}
-  if world == 1 and args.legs and args.legs != 'none':
+  if args.full and world == 1 and args.legs and args.legs != 'none':
     # the other BASELINE workloads, after everything above read the headline's
     # results: its packer scratch goes first (a second context beside it would
     # double the tokenizer / packer scratch), its shards stay for the legs on

@@ -24,7 +24,7 @@ for S in ${STEPS:-tests tok bench}; do
       done ;;
     bench|benchmat)
       X=""; [ $S = benchmat ] && X="--rows materialize"
-      timeout -k 10 600 python -u bench.py $BA $X > $OUT/$S.log 2>&1 || { echo "$S failed"; tail -20 $OUT/$S.log; exit 1; }
+      timeout -k 10 600 python -u bench.py --full $BA $X > $OUT/$S.log 2>&1 || { echo "$S failed"; tail -20 $OUT/$S.log; exit 1; }
       tail -1 $OUT/$S.log > $OUT/$S.json
       python3 -c "import json; d=json.load(open('$OUT/$S.json')); print('$S', round(d['ms_per_step'],1), 'ms/step', round(d['value']/1e9,2), 'G tok/s', 'tok', {k: round(v,1) for k,v in d['tokenize_kernels_ms'].items()}, 'writer rows/s', round(d.get('parquet_writer',{}).get('rows_per_s',0)))" ;;
     kt|kthead)

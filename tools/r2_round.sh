@@ -15,7 +15,7 @@ if [ -z "$SKIP_TESTS" ]; then
   cat $OUT/smoke.log
 fi
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 900 python -u bench.py ${BENCH_ARGS} > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
+  timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS} > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
   tail -1 $OUT/bench.log > $OUT/bench.json
   cat $OUT/bench.json
 fi

@@ -14,7 +14,7 @@ TESTS="tests/test_pack_gpu.py tests/test_writer_gpu.py tests/test_preprocess.py"
 timeout -k 10 600 python -u -m pytest -x -v --timeout 200 --timeout-method thread -m gpu $TESTS > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -1 $O/pytest.log
 if [ -n "$CODE_WRITER" ]; then
-  timeout -k 10 300 python -u bench.py --corpus code --no-cpu-baseline --frontend-mb 0 --steps 1 --warmup 0 > $O/code.log 2>&1 || { tail -5 $O/code.log; exit 1; }
+  timeout -k 10 300 python -u bench.py --full --corpus code --no-cpu-baseline --frontend-mb 0 --steps 1 --warmup 0 > $O/code.log 2>&1 || { tail -5 $O/code.log; exit 1; }
   tail -1 $O/code.log > $O/code.json
   python -c "import json; print('code writer', json.load(open('$O/code.json'))['parquet_writer'])"
 fi

@@ -16,13 +16,13 @@ if [ -z "$SKIP_TESTS" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $OUT/smoke.log; exit 1; }
   tail -1 $OUT/smoke.log
 fi
-timeout -k 10 900 python -u bench.py > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log > $OUT/bench.json
 python3 -c "import json; d=json.load(open('$OUT/bench.json')); print('bench', round(d['ms_per_step'],1), 'ms/step', round(d['value']/1e9,2), 'G tok/s', d['cpu_baseline'].get('sample_check'))"
 if [ -z "$SKIP_CONFIGS" ]; then
   for C in "--corpus code" "--masking" "--corpus wikibooks" "--rows materialize"; do
     N=$(echo $C | tr -d ' -')
-    timeout -k 10 900 python -u bench.py $C --no-cpu-baseline --frontend-mb 0 > $OUT/bench_$N.log 2>&1 || { echo "bench $C failed"; tail -20 $OUT/bench_$N.log; exit 1; }
+    timeout -k 10 900 python -u bench.py --full $C --no-cpu-baseline --frontend-mb 0 > $OUT/bench_$N.log 2>&1 || { echo "bench $C failed"; tail -20 $OUT/bench_$N.log; exit 1; }
     tail -1 $OUT/bench_$N.log > $OUT/bench_$N.json
     python3 -c "import json; d=json.load(open('$OUT/bench_$N.json')); print('$N', round(d['ms_per_step'],1), 'ms/step', round(d['value']/1e9,2), 'G tok/s', 'writer', round(d.get('parquet_writer',{}).get('rows_per_s',0)))"
   done

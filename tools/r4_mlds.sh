@@ -21,6 +21,6 @@ print('$v', round(d['ms_per_step'], 2), 'ms/step', d.get('sample_check', d.get('
 done
 unset LDDL_LIB
 # one full-size masked partition of the tree's run against the oracle
-timeout -k 10 400 python -u bench.py --masking --parquet-parts 0 --frontend-mb 0 --steps 1 --warmup 0 > $O/m_check.log 2>&1 || { tail -5 $O/m_check.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full --masking --parquet-parts 0 --frontend-mb 0 --steps 1 --warmup 0 > $O/m_check.log 2>&1 || { tail -5 $O/m_check.log; exit 1; }
 python -c "
 import json; d = json.loads(open('$O/m_check.log').read().strip().splitlines()[-1]); print('sample check', d['cpu_baseline']['sample_check'])"

@@ -17,7 +17,7 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -1 $OUT/smoke.log
 fi
 if [ -z "$SKIP_BENCH" ]; then
-timeout -k 10 900 python -u bench.py > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed"; tail -20 $OUT/bench.log; exit 1; }
 grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json
 python3 -c "import json; d=json.load(open('$OUT/bench.json')); print('bench', round(d['ms_per_step'],1), 'ms/step', round(d['value']/1e9,2), 'G tok/s', d['cpu_baseline'].get('sample_check'))"
 fi

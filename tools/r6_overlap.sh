@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=${1:-r6ov}
 cd "${GRAFT_REPO_ROOT:-.}" && export TMPDIR=/tmp && mkdir -p gpurun_out/$TAG
-B="bench.py --cpu-seconds 2 --parquet-parts 0 --frontend-mb 0 --frontend-c2-mb 0 --legs none --steps ${STEPS:-5} --warmup 1"
+B="bench.py --full --cpu-seconds 2 --parquet-parts 0 --frontend-mb 0 --frontend-c2-mb 0 --legs none --steps ${STEPS:-5} --warmup 1"
 for R in 1 2; do
   for M in overlap no-overlap; do
     timeout -k 10 400 python -u $B --$M > gpurun_out/$TAG/$M.$R.log 2>&1 || { tail -20 gpurun_out/$TAG/$M.$R.log; exit 1; }

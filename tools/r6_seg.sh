@@ -5,7 +5,7 @@
 set -o pipefail
 TAG=${1:-r6seg}
 cd "${GRAFT_REPO_ROOT:-.}" && export TMPDIR=/tmp && mkdir -p gpurun_out/$TAG
-B="bench.py --cpu-seconds 2 --parquet-parts 0 --frontend-mb 0 --frontend-c2-mb 0 --legs none --steps ${STEPS:-3} --warmup 1"
+B="bench.py --full --cpu-seconds 2 --parquet-parts 0 --frontend-mb 0 --frontend-c2-mb 0 --legs none --steps ${STEPS:-3} --warmup 1"
 for R in 1 2; do
   for S in ${SEGS:-4194304 8388608}; do
     LDDL_SPLIT_SEG=$S timeout -k 10 400 python -u $B > gpurun_out/$TAG/seg$S.$R.log 2>&1 || { tail -20 gpurun_out/$TAG/seg$S.$R.log; exit 1; }

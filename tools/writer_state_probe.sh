@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp
 O=gpurun_out/${TAG:-r5wstate}; mkdir -p $O
 mhz() { awk '/cpu MHz/ {s+=$4; n++} END {printf "%.0f", s/n}' /proc/cpuinfo; }
 run() {
-  timeout -k 10 300 python -u bench.py --legs none --no-cpu-baseline --no-sample-check --steps 1 --warmup 1 --frontend-mb 0 --frontend-c2-mb 0 > $O/b.json 2>> $O/err.log || exit 1
+  timeout -k 10 300 python -u bench.py --full --legs none --no-cpu-baseline --no-sample-check --steps 1 --warmup 1 --frontend-mb 0 --frontend-c2-mb 0 > $O/b.json 2>> $O/err.log || exit 1
   grep -h "^{" $O/b.json | python3 -c "import json,sys; p=json.load(sys.stdin)['parquet_writer']; print('$1', 'writer', round(p['rows_per_s']/1e6,3), 'M rows/s, table_s', round(p['stages']['table_s'],3))" >> $O/summary.txt
   echo "  mean cpu MHz $(mhz)" >> $O/summary.txt
 }

@@ -48,6 +48,75 @@ struct WsBuf {
   size_t cap = 0;
 };
 
+// Slots of lddl_pack::ws, the buffers of one pack result.
+enum PackWs {
+  PW_FS_NTOK,      // per filtered sentence: its token count
+  PW_FS_BASE,      // per filtered sentence: its byte offset
+  PW_FD_FIRST,     // per filtered doc: its first filtered sentence
+  PW_FD_N,         // per filtered doc: its filtered sentences
+  PW_FD_ND,        // per filtered doc: CodeBERT docstring segment count
+  PW_PAIRS,        // the pair records
+  PW_ORDER,        // their shuffled order
+  PW_BINNED,       // their binned order
+  PW_TOK_LOCAL,    // per pair: its token offset within the partition
+  PW_PART_NPAIRS,  // per partition: its pairs
+  PW_PART_NTOK,    // per partition: its tokens
+  PW_BIN_COUNT,    // per partition and bin: its rows
+  PW_BIN_CURSOR,   // per partition and bin: the binning cursor
+  PW_PART_ERR,     // per partition: PACK_E* flags
+  PW_PAIR_BASE,    // [n_part + 1] exclusive scan of PW_PART_NPAIRS (read by the post-pack calls)
+  PW_TOK_BASE,     // [n_part + 1] exclusive scan of PW_PART_NTOK (read by the post-pack calls)
+  PW_ERR_ANY,      // the partitions' error flags or-ed
+  PW_KEPT,         // [n_sent + n_part + 1] wave packer scratch
+  PW_MT_STATES,    // MT19937 state per partition (whole 64-partition rows)
+  PW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP], when the tokenizer's flags (CW_SENT_SPEC) do not apply
+  PW_FS_SPEC,      // the same per filtered sentence
+  PW_MREF,         // masking: per record, arena offset | #masked << 48
+  PW_MLOC,         // masking: per binned position, the masked entries before it
+  PW_PART_NMASK,   // masking: per partition, its masked entries
+  PW_MASK_BASE,    // masking: [n_part + 1] exclusive scan of PW_PART_NMASK (read by lddl_masked_lm[_spans])
+  PW_MASK_BASE2,   // masking: the second output of that scan (unused)
+  PW_MCOUNTER,     // masking: the arena's bump allocator
+  PW_MARENA,       // masking: the arena of masked entries
+  PW_MCAND,        // masking: per partition, MLM_MAX_SEQ candidate positions
+  PW_FS_DENSE,     // per filtered sentence: its offset in the tokenizer's dense ids
+  PW_COUNT
+};
+
+// Slots of lddl_ctx::ws.  The header allows one call at a time per ctx, so
+// entry points that never need a buffer at the same time share a slot (the
+// CW_SHARED_* ones: one allocation serves all their users); CW_SENT_SPEC is
+// handed from lddl_tokenize to the next masked lddl_pack_bert on purpose.
+// ("tokenize": algorithms 5 and 0; the lane tokenizer, 6, takes only
+// CW_TILE_SENT, CW_FB_LIST, CW_FB_COUNT, CW_ENT, CW_SHARED_BSUM, CW_SCAN_BSUM
+// and CW_TILE_OFF.)
+enum CtxWs {
+  CW_BIN_HIST,     // lddl_bin: per chunk and bin, its rows
+  CW_BIN_BASE,     // lddl_bin: exclusive scan of CW_BIN_HIST
+  CW_BIN_BSUM,     // lddl_bin: block sums of that scan
+  CW_BIN_ERR,      // lddl_bin: the error flag
+  CW_NPY_ERR,      // lddl_render_npy: the error flag
+  CW_TILE_SENT,    // tokenize: [tiles + 1] first sentence of each tile
+  CW_FB_LIST,      // tokenize: sentence ranges for the serial path
+  CW_FB_COUNT,     // tokenize: ranges listed in the segment
+  CW_ENT,          // tokenize: the segment's entry / staging buffer
+  CW_SHARED_ROWS,  // tokenize: rec, the record slots; lddl_render_strings / _npy / _masked: lens, bytes per row
+  CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan
+  CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate_seq_len: max_len
+  CW_COLLATE_ERR,  // lddl_collate_bert: the error word
+  CW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP]; written by lddl_tokenize (lddl_set_special_flags),
+                   // read by the next masked lddl_pack_bert over the same buffers (pack_common)
+  CW_PCS,          // tokenize: WordPiece pieces 4.. per record slot
+  CW_SNSLOT,       // tokenize: per sentence, its record slots
+  CW_CNT8,         // tokenize: per record slot, the word's pieces
+  CW_SCAN_BSUM,    // tokenize: block sums of the token-count scan
+  CW_PCH,          // tokenize: WordPiece head per record slot
+  CW_TILE_OFF,     // lane tokenizer: [tiles + 1] first byte offset of each tile
+  CW_CHUNK_PART,   // lddl_row_spans: the partition of every 64 rows
+  CW_PART_PB,      // lddl_row_spans: per partition, launch_chunk_parts' pair base
+  CW_COUNT
+};
+
 // The result of one lddl_pack_* call, owned by the caller (lddl_pack_new):
 // the pair records, their shuffled / binned order, the per-partition counts
 // and offsets and (masking) the masked positions -- everything the post-pack
@@ -56,7 +125,7 @@ struct WsBuf {
 // NULL.  Buffers grow on demand and are reused by later packs into it.
 struct lddl_pack {
   int device = 0;
-  WsBuf ws[34];
+  WsBuf ws[PW_COUNT];
   PackParams pp{};
   int64_t last_npairs = -1, last_ntok = -1, last_nmask = -1, last_nsent = 0, last_ndense = 0;
   int pack_codebert = 0;
@@ -89,8 +158,6 @@ struct lddl_ctx {
   uint4* d_vt = nullptr;         // v4 bucketed vocab table
   uint32_t vt_mask = 0;
   uint32_t* d_vbloom = nullptr;  // its Bloom filter
-  uint4* d_st = nullptr;         // the scan's whole-word table
-  uint32_t st_mask = 0;
   bool scan_ok = false;          // the ASCII page fits the split scan's per-byte class table
   // lane tokenizer (tokenize_lane.hip): the vocab trie, its roots, the byte classes
   uint2* d_trie = nullptr;
@@ -103,7 +170,7 @@ struct lddl_ctx {
   SplitTiming* tm = nullptr;
   unsigned long long* d_nrec = nullptr;
   int64_t last_tok_bytes = 0, last_tok_sent = 0;
-  // per-sentence [CLS]/[SEP] flags written by the last lddl_tokenize (ws 41),
+  // per-sentence [CLS]/[SEP] flags written by the last lddl_tokenize (CW_SENT_SPEC),
   // reused by a masked lddl_pack_bert over the same id / count buffers
   const void* spec_ids = nullptr;
   const void* spec_ntok = nullptr;
@@ -111,7 +178,7 @@ struct lddl_ctx {
   int64_t spec_nsent = -1;
   bool spec_flags = false;  // lddl_set_special_flags
   // tokenizer / render / collate workspace (grown on demand)
-  WsBuf ws[50];
+  WsBuf ws[CW_COUNT];
   int64_t* h_tot = nullptr;  // pinned [8]
   lddl_pack own;             // the pack result of calls that pass no lddl_pack
   uint64_t mlm_cap0 = 0;     // initial masking arena (LDDL_MLM_CAP, tests)
@@ -176,7 +243,6 @@ static void free_ctx(lddl_ctx* c) {
   (void)hipFree(c->d_rinfo);
   (void)hipFree(c->d_vt);
   (void)hipFree(c->d_vbloom);
-  (void)hipFree(c->d_st);
   (void)hipFree(c->d_ovf);
   (void)hipFree(c->d_counter);
   (void)hipFree(c->d_ctab);
@@ -227,12 +293,10 @@ static int load_table(lddl_ctx* c, const char* path) {
 static int load_vocab(lddl_ctx* c, const char* path) {
   VocabTables V;
   std::string err;
-  // the trie only for the options that read it (its build is the bulk of
-  // the table setup)
+  // the trie only for the lane tokenizer (its build is the bulk of the table
+  // setup)
   const char* algo = getenv("LDDL_TOKENIZE_ALGO");
-  const char* wp = getenv("LDDL_WP_ALGO");
-  const bool want_trie = (algo && algo[0] == '6') || (wp && strcmp(wp, "trie") == 0);
-  int rc = build_vocab_tables(path, V, err, want_trie);
+  int rc = build_vocab_tables(path, V, err, algo && algo[0] == '6');
   if (rc) return set_err(rc, "%s", err.c_str());
   c->vocab_size = (int)V.vocab.size();
   for (int k = 0; k < 5; ++k) c->special[k] = V.special[k];
@@ -243,8 +307,6 @@ static int load_vocab(lddl_ctx* c, const char* path) {
   if ((rc = upload(&c->d_bloom, V.bloom.data(), V.bloom.size() * 4))) return rc;
   if ((rc = upload(&c->d_vt, V.vt.data(), V.vt.size() * 4))) return rc;
   if ((rc = upload(&c->d_vbloom, V.vbloom.data(), V.vbloom.size() * 4))) return rc;
-  c->st_mask = V.st_mask;
-  if ((rc = upload(&c->d_st, V.st.data(), V.st.size() * 4))) return rc;
   if ((rc = upload(&c->d_slots, V.slots.data(), V.slots.size() * sizeof(uint4)))) return rc;
   if ((rc = upload(&c->d_pool, V.pool.data(), V.pool.size()))) return rc;
   if ((rc = upload(&c->d_voff, V.voff.data(), V.voff.size() * 4))) return rc;
@@ -287,12 +349,9 @@ extern "C" int lddl_create(const char* vocab_path, const char* table_path, int d
   c->n_cu = prop.multiProcessorCount;
   if ((rc = load_table(c, table_path)) || (rc = load_vocab(c, vocab_path))) { free_ctx(c); return rc; }
   // 5: the split tokenizer (default); 6: the lane tokenizer of round 5
-  // (measured slower; A/B); 0: every tile through the exact serial
-  // path -- LDDL_TOKENIZE_ALGO selects (tests); an algorithm that does not model the tables falls back
-  // to the serial one (the lane tokenizer needs the trie and a table in which
-  // no code point normalises to more chars than its UTF-8 bytes; the split
-  // one keeps ids below SPLIT_EDEF and derives its byte classes from the
-  // ASCII page)
+  // (measured slower; A/B); 0: every tile through the
+  // exact serial path -- LDDL_TOKENIZE_ALGO selects (tests); select_tok_algo
+  // falls back to 0 for tables the algorithm does not model
   const char* algo = getenv("LDDL_TOKENIZE_ALGO");
   select_tok_algo(c, !algo ? 5 : algo[0] == '0' ? 0 : algo[0] == '6' ? 6 : 5);
   const char* mcap = getenv("LDDL_MLM_CAP");  // initial masking arena (tests force the regrow path)
@@ -360,7 +419,7 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
   c->spec_ids = nullptr;
   if (c->spec_flags) {
     int rc;
-    if ((rc = ws_get(c, 41, n_sent, &P.sent_spec))) return rc;
+    if ((rc = ws_get(c, CW_SENT_SPEC, n_sent, &P.sent_spec))) return rc;
     c->spec_ids = d_out_ids;
     c->spec_ntok = d_out_ntok;
     c->spec_soff = d_sent_off;
@@ -383,17 +442,6 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
   P.vt = c->d_vt;
   P.vt_mask = c->vt_mask;
   P.vbloom = c->d_vbloom;
-  // LDDL_SCAN_TABLE=1: the scan probes its two-choice whole-word table
-  // (half the scan's fetch, 3 % fewer WordPiece records, but the scan 3.5 %
-  // slower: profiles/r5_scan_table.txt); default: slot 0 of the vt bucket
-  {
-    const char* e = getenv("LDDL_SCAN_TABLE");
-    P.st = (e && e[0] == '1') ? c->d_st : nullptr;
-    P.st_mask = c->st_mask;
-  }
-  P.trie = c->d_trie;
-  P.trie_base[0] = c->trie_base[0];
-  P.trie_base[1] = c->trie_base[1];
   P.ovf = c->d_ovf;
   P.work_counter = c->d_counter;
   HIP_TRY(hipMemsetAsync(c->d_counter, 0, 64, st));
@@ -421,25 +469,25 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
   int rc;
   // (the entry / staging buffer: u16 per byte of a segment + the last
   // sentence's ids past its end)
-  if ((rc = ws_get(c, 19, nt + 1, &tile_sent)) || (rc = ws_get(c, 20, (size_t)fb_list_cap(seg), &S.fb_list)) ||
-      (rc = ws_get(c, 21, 16, &S.fb_count)) ||
-      (rc = ws_get(c, 34, (size_t)seg * 1024 + (size_t)max_tok + 4096, &S.ent)) ||
-      (rc = ws_get(c, 36, (size_t)n_chunks + 16, &S.chunk_fill)) ||
-      (rc = ws_get(c, 45, (size_t)scan_blocks(n_sent) + 1, &S.scan_bsum)))
+  if ((rc = ws_get(c, CW_TILE_SENT, nt + 1, &tile_sent)) || (rc = ws_get(c, CW_FB_LIST, (size_t)fb_list_cap(seg), &S.fb_list)) ||
+      (rc = ws_get(c, CW_FB_COUNT, 16, &S.fb_count)) ||
+      (rc = ws_get(c, CW_ENT, (size_t)seg * 1024 + (size_t)max_tok + 4096, &S.ent)) ||
+      (rc = ws_get(c, CW_SHARED_BSUM, (size_t)n_chunks + 16, &S.chunk_fill)) ||
+      (rc = ws_get(c, CW_SCAN_BSUM, (size_t)scan_blocks(n_sent) + 1, &S.scan_bsum)))
     return rc;
   // (the serial path (0) runs the split path's finish: count / expand read
   // smeta, snslot, cnt8 and, unconditionally, pch[0] -- one chunk of them)
   if (c->tok_algo != 6 &&
-      ((rc = ws_get(c, 35, (size_t)slots * 4, &S.rec)) || (rc = ws_get(c, 42, (size_t)slots * 4, &S.pcs)) ||
-       (rc = ws_get(c, 47, (size_t)slots, &S.pch)) || (rc = ws_get(c, 37, n_sent, &S.smeta)) ||
-       (rc = ws_get(c, 43, n_sent, &S.snslot)) || (rc = ws_get(c, 44, (size_t)slots, &S.cnt8))))
+      ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)slots * 4, &S.rec)) || (rc = ws_get(c, CW_PCS, (size_t)slots * 4, &S.pcs)) ||
+       (rc = ws_get(c, CW_PCH, (size_t)slots, &S.pch)) || (rc = ws_get(c, CW_SHARED_META, n_sent, &S.smeta)) ||
+       (rc = ws_get(c, CW_SNSLOT, n_sent, &S.snslot)) || (rc = ws_get(c, CW_CNT8, (size_t)slots, &S.cnt8))))
     return rc;
   // (the finish pass -- count_kernel and expand_kernel of algorithms 5 and 0
   // -- reads these unconditionally: refuse to run it without them)
   if (c->tok_algo != 6 && (!S.pch || !S.smeta || !S.snslot || !S.cnt8 || !S.rec || !S.pcs))
     return set_err(LDDL_EINVAL, "tokenize: finish scratch not allocated");
   int64_t* tile_off = nullptr;
-  if (c->tok_algo == 6 && (rc = ws_get(c, 46, nt + 1, &tile_off))) return rc;  // (the lane tokenizer's tile starts)
+  if (c->tok_algo == 6 && (rc = ws_get(c, CW_TILE_OFF, nt + 1, &tile_off))) return rc;  // (the lane tokenizer's tile starts)
   S.tile_off = tile_off;
   S.chunk_ctr = S.chunk_fill + n_chunks;
   S.n_chunks = (uint32_t)n_chunks;
@@ -604,28 +652,28 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
   P.nbins = nbins;
   const size_t npair_cap = (size_t)duplicate_factor * (size_t)(n_sent ? n_sent : 1);
   int rc;
-  if ((rc = ws_get(k->ws, 0, n_sent, &P.fs_ntok)) || (rc = ws_get(k->ws, 1, n_sent, &P.fs_base)) ||
-      (rc = ws_get(k->ws, 2, n_doc, &P.fd_first)) || (rc = ws_get(k->ws, 3, n_doc, &P.fd_n)) ||
-      (rc = ws_get(k->ws, 4, n_doc, &P.fd_nd)) ||
-      (rc = ws_get(k->ws, 6, npair_cap, &P.pairs)) || (rc = ws_get(k->ws, 7, npair_cap, &P.order)) ||
-      (rc = ws_get(k->ws, 8, npair_cap, &P.binned)) || (rc = ws_get(k->ws, 9, npair_cap, &P.tok_local)) ||
-      (rc = ws_get(k->ws, 10, n_part, &P.part_npairs)) || (rc = ws_get(k->ws, 11, n_part, &P.part_ntok)) ||
-      (rc = ws_get(k->ws, 12, (size_t)n_part * nbins, &P.bin_count)) ||
-      (rc = ws_get(k->ws, 13, (size_t)n_part * nbins, &P.bin_cursor)) ||
-      (rc = ws_get(k->ws, 14, n_part, &P.part_err)) || (rc = ws_get(k->ws, 18, n_sent + n_part + 1, &P.kept)) ||
-      (rc = ws_get(k->ws, 33, n_sent, &P.fs_dense)))
+  if ((rc = ws_get(k->ws, PW_FS_NTOK, n_sent, &P.fs_ntok)) || (rc = ws_get(k->ws, PW_FS_BASE, n_sent, &P.fs_base)) ||
+      (rc = ws_get(k->ws, PW_FD_FIRST, n_doc, &P.fd_first)) || (rc = ws_get(k->ws, PW_FD_N, n_doc, &P.fd_n)) ||
+      (rc = ws_get(k->ws, PW_FD_ND, n_doc, &P.fd_nd)) ||
+      (rc = ws_get(k->ws, PW_PAIRS, npair_cap, &P.pairs)) || (rc = ws_get(k->ws, PW_ORDER, npair_cap, &P.order)) ||
+      (rc = ws_get(k->ws, PW_BINNED, npair_cap, &P.binned)) || (rc = ws_get(k->ws, PW_TOK_LOCAL, npair_cap, &P.tok_local)) ||
+      (rc = ws_get(k->ws, PW_PART_NPAIRS, n_part, &P.part_npairs)) || (rc = ws_get(k->ws, PW_PART_NTOK, n_part, &P.part_ntok)) ||
+      (rc = ws_get(k->ws, PW_BIN_COUNT, (size_t)n_part * nbins, &P.bin_count)) ||
+      (rc = ws_get(k->ws, PW_BIN_CURSOR, (size_t)n_part * nbins, &P.bin_cursor)) ||
+      (rc = ws_get(k->ws, PW_PART_ERR, n_part, &P.part_err)) || (rc = ws_get(k->ws, PW_KEPT, n_sent + n_part + 1, &P.kept)) ||
+      (rc = ws_get(k->ws, PW_FS_DENSE, n_sent, &P.fs_dense)))
     return rc;
   {
     uint32_t* mts;
-    if ((rc = ws_get(k->ws, 19, (size_t)((n_part + 63) & ~(int64_t)63) * MT_N, &mts))) return rc;  // (whole 64-partition rows)
+    if ((rc = ws_get(k->ws, PW_MT_STATES, (size_t)((n_part + 63) & ~(int64_t)63) * MT_N, &mts))) return rc;  // (whole 64-partition rows)
     HIP_TRY(launch_mt_seed_states(seed, n_part, mts, st));
     P.mt_states = mts;
   }
   P.tokoff = d_tok_off;  // the tokenizer's dense offsets (lddl_tokenize d_out_tok_off)
   int64_t *pair_base, *tok_base;
   int32_t* err_any;
-  if ((rc = ws_get(k->ws, 15, n_part + 1, &pair_base)) || (rc = ws_get(k->ws, 16, n_part + 1, &tok_base)) ||
-      (rc = ws_get(k->ws, 17, 4, &err_any)))
+  if ((rc = ws_get(k->ws, PW_PAIR_BASE, n_part + 1, &pair_base)) || (rc = ws_get(k->ws, PW_TOK_BASE, n_part + 1, &tok_base)) ||
+      (rc = ws_get(k->ws, PW_ERR_ANY, 4, &err_any)))
     return rc;
   if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   int64_t *mask_base = nullptr, *mask_base2 = nullptr;
@@ -644,12 +692,12 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
     const bool spec_ok = c->spec_ids == d_ids && c->spec_ntok == d_ntok && c->spec_soff == d_sent_off &&
                          c->spec_nsent == n_sent;
     c->spec_ids = nullptr;
-    if ((rc = spec_ok ? ws_get(c->ws, 41, n_sent, &sent_spec) : ws_get(k->ws, 22, n_sent, &sent_spec)) ||
-        (rc = ws_get(k->ws, 23, n_sent, &fs_spec)) ||
-        (rc = ws_get(k->ws, 24, npair_cap, &P.mref)) || (rc = ws_get(k->ws, 25, npair_cap, &P.mloc)) ||
-        (rc = ws_get(k->ws, 26, n_part, &P.part_nmask)) || (rc = ws_get(k->ws, 27, n_part + 1, &mask_base)) ||
-        (rc = ws_get(k->ws, 28, n_part + 1, &mask_base2)) || (rc = ws_get(k->ws, 29, 1, &P.mcounter)) ||
-        (rc = ws_get(k->ws, 31, (size_t)n_part * MLM_MAX_SEQ, &P.mcand)))
+    if ((rc = spec_ok ? ws_get(c->ws, CW_SENT_SPEC, n_sent, &sent_spec) : ws_get(k->ws, PW_SENT_SPEC, n_sent, &sent_spec)) ||
+        (rc = ws_get(k->ws, PW_FS_SPEC, n_sent, &fs_spec)) ||
+        (rc = ws_get(k->ws, PW_MREF, npair_cap, &P.mref)) || (rc = ws_get(k->ws, PW_MLOC, npair_cap, &P.mloc)) ||
+        (rc = ws_get(k->ws, PW_PART_NMASK, n_part, &P.part_nmask)) || (rc = ws_get(k->ws, PW_MASK_BASE, n_part + 1, &mask_base)) ||
+        (rc = ws_get(k->ws, PW_MASK_BASE2, n_part + 1, &mask_base2)) || (rc = ws_get(k->ws, PW_MCOUNTER, 1, &P.mcounter)) ||
+        (rc = ws_get(k->ws, PW_MCAND, (size_t)n_part * MLM_MAX_SEQ, &P.mcand)))
       return rc;
     P.sent_spec = sent_spec;
     P.fs_spec = fs_spec;
@@ -677,7 +725,7 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
   }
   for (int attempt = 0;; ++attempt) {
     if (masking) {
-      if ((rc = ws_get(k->ws, 30, k->mlm_cap, &P.marena))) return rc;
+      if ((rc = ws_get(k->ws, PW_MARENA, k->mlm_cap, &P.marena))) return rc;
       P.mcap = k->mlm_cap;
       HIP_TRY(hipMemsetAsync(P.mcounter, 0, 8, st));
     }
@@ -830,8 +878,8 @@ static MatParams mat_params(const lddl_ctx* c, const lddl_pack* k) {
   M.binned = P.binned;
   M.tok_local = P.tok_local;
   M.part_npairs = P.part_npairs;
-  M.pair_base = (const int64_t*)k->ws[15].p;
-  M.tok_base = (const int64_t*)k->ws[16].p;
+  M.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
+  M.tok_base = (const int64_t*)k->ws[PW_TOK_BASE].p;
   M.n_part = P.n_part;
   M.dup = P.dup;
   M.bin_size = P.bin_size;
@@ -907,8 +955,8 @@ extern "C" int lddl_row_spans(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_src0, i
     int32_t* chunk_part = nullptr;
     int64_t* part_pb = nullptr;
     int rc;
-    if ((rc = ws_get(c, 48, (size_t)((k->last_npairs + 63) >> 6), &chunk_part)) ||
-        (rc = ws_get(c, 49, (size_t)P.n_part, &part_pb)))
+    if ((rc = ws_get(c, CW_CHUNK_PART, (size_t)((k->last_npairs + 63) >> 6), &chunk_part)) ||
+        (rc = ws_get(c, CW_PART_PB, (size_t)P.n_part, &part_pb)))
       return rc;
     HIP_TRY(launch_chunk_parts(M.pair_base, P.doc_sent_off, P.part_doc_off, P.dup, P.n_part, chunk_part, part_pb, st));
     M.chunk_part = chunk_part;
@@ -938,11 +986,11 @@ extern "C" int lddl_masked_lm(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_mlm_off
     MlmParams M{};
     M.doc_sent_off = P.doc_sent_off;
     M.part_doc_off = P.part_doc_off;
-    M.pair_base = (const int64_t*)k->ws[15].p;
+    M.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
     M.binned = P.binned;
     M.mref = P.mref;
     M.mloc = P.mloc;
-    M.mask_base = (const int64_t*)k->ws[27].p;
+    M.mask_base = (const int64_t*)k->ws[PW_MASK_BASE].p;
     M.marena = P.marena;
     M.n_part = P.n_part;
     M.dup = P.dup;
@@ -979,11 +1027,11 @@ extern "C" int lddl_masked_lm_spans(lddl_ctx* c, lddl_pack* pk, const uint16_t* 
     MlmParams M{};
     M.doc_sent_off = P.doc_sent_off;
     M.part_doc_off = P.part_doc_off;
-    M.pair_base = (const int64_t*)k->ws[15].p;
+    M.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
     M.binned = P.binned;
     M.mref = P.mref;
     M.mloc = P.mloc;
-    M.mask_base = (const int64_t*)k->ws[27].p;
+    M.mask_base = (const int64_t*)k->ws[PW_MASK_BASE].p;
     M.marena = P.marena;
     M.n_part = P.n_part;
     M.dup = P.dup;
@@ -1038,8 +1086,8 @@ extern "C" int lddl_bin(lddl_ctx* c, const int64_t* d_num_tokens, int64_t n, int
   int32_t *hist, *err;
   int64_t *base, *bsum;
   int rc;
-  if ((rc = ws_get(c, 0, (size_t)(nh ? nh : 1), &hist)) || (rc = ws_get(c, 1, (size_t)nh + 1, &base)) ||
-      (rc = ws_get(c, 2, (size_t)scan_blocks(nh) + 1, &bsum)) || (rc = ws_get(c, 3, 1, &err)))
+  if ((rc = ws_get(c, CW_BIN_HIST, (size_t)(nh ? nh : 1), &hist)) || (rc = ws_get(c, CW_BIN_BASE, (size_t)nh + 1, &base)) ||
+      (rc = ws_get(c, CW_BIN_BSUM, (size_t)scan_blocks(nh) + 1, &bsum)) || (rc = ws_get(c, CW_BIN_ERR, 1, &err)))
     return rc;
   if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   HIP_TRY(launch_bin(d_num_tokens, n, bin_size, nbins, hist, base, bsum, d_out_perm, d_out_bin_counts, err, st));
@@ -1078,8 +1126,8 @@ extern "C" int lddl_render_strings(lddl_ctx* c, const uint16_t* d_tokens, const 
   R.vpool = c->d_rpool;
   int64_t* bsum;
   int rc;
-  if ((rc = ws_get(c, 35, (size_t)n_rows, &R.lens))) return rc;
-  if ((rc = ws_get(c, 36, (size_t)scan_blocks(n_rows) + 1, &bsum))) return rc;
+  if ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)n_rows, &R.lens))) return rc;
+  if ((rc = ws_get(c, CW_SHARED_BSUM, (size_t)scan_blocks(n_rows) + 1, &bsum))) return rc;
   HIP_TRY(launch_render_len(R, c->n_cu, st));
   HIP_TRY(launch_scan_ntok(R.lens, n_rows, d_out_off, bsum, st));
   HIP_TRY(hipMemcpyAsync(&c->h_tot[6], d_out_off + n_rows, 8, hipMemcpyDeviceToHost, st));
@@ -1113,8 +1161,8 @@ extern "C" int lddl_render_npy(lddl_ctx* c, const int64_t* d_mlm_off, const uint
   N.kmax = kmax;
   int64_t* bsum;
   int rc;
-  if ((rc = ws_get(c, 35, (size_t)(n_rows ? n_rows : 1), &N.lens)) ||
-      (rc = ws_get(c, 36, (size_t)scan_blocks(n_rows) + 1, &bsum)) || (rc = ws_get(c, 4, 1, &N.err)))
+  if ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)(n_rows ? n_rows : 1), &N.lens)) ||
+      (rc = ws_get(c, CW_SHARED_BSUM, (size_t)scan_blocks(n_rows) + 1, &bsum)) || (rc = ws_get(c, CW_NPY_ERR, 1, &N.err)))
     return rc;
   if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   HIP_TRY(hipMemsetAsync(N.err, 0, 4, st));
@@ -1163,8 +1211,8 @@ extern "C" int lddl_render_masked(lddl_ctx* c, const uint16_t* d_ids, const int6
   R.mseg = segment;
   int64_t* bsum;
   int rc;
-  if ((rc = ws_get(c, 35, (size_t)n_rows, &R.lens))) return rc;
-  if ((rc = ws_get(c, 36, (size_t)scan_blocks(n_rows) + 1, &bsum))) return rc;
+  if ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)n_rows, &R.lens))) return rc;
+  if ((rc = ws_get(c, CW_SHARED_BSUM, (size_t)scan_blocks(n_rows) + 1, &bsum))) return rc;
   HIP_TRY(launch_render_len(R, c->n_cu, st));
   HIP_TRY(launch_scan_ntok(R.lens, n_rows, d_out_off, bsum, st));
   HIP_TRY(hipMemcpyAsync(&c->h_tot[6], d_out_off + n_rows, 8, hipMemcpyDeviceToHost, st));
@@ -1190,7 +1238,7 @@ extern "C" int lddl_row_docs(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_doc, voi
   RowDocParams D{};
   D.pairs = P.pairs;
   D.binned = P.binned;
-  D.pair_base = (const int64_t*)k->ws[15].p;
+  D.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
   D.fs_base = P.fs_base;
   D.sent_off = P.sent_off;
   D.doc_sent_off = P.doc_sent_off;
@@ -1257,7 +1305,7 @@ extern "C" int lddl_collate_seq_len(lddl_ctx* c, const uint8_t* d_a, const int64
   P.b = d_b;
   P.b_off = d_b_off;
   P.n_rows = n_rows;
-  if ((rc = ws_get(c, 37, 1, &P.max_len))) return rc;
+  if ((rc = ws_get(c, CW_SHARED_META, 1, &P.max_len))) return rc;
   if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   HIP_TRY(hipMemsetAsync(P.max_len, 0, 4, st));
   HIP_TRY(launch_collate_len(P, c->n_cu, st));
@@ -1314,7 +1362,7 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
   P.attention_mask = d_attention_mask;
   P.labels = d_labels;
   P.next_sentence_labels = d_next_sentence_labels;
-  if ((rc = ws_get(c, 39, 1, &P.err))) return rc;
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
   if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
   HIP_TRY(launch_collate_fill(P, c->n_cu, st));

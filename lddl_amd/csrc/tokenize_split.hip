@@ -47,19 +47,6 @@ namespace tok5 {
 // (a 1.5 KiB window for 6 waves/SIMD measured slower: 0.2 % of the tiles fall
 // back to the serial path, finish 0.97 -> 3.2 ms per GiB, and the 80-VGPR
 // scan spills: 3.80 vs 3.49)
-// LDDL_PROBE_REC (measurement builds only, results not exact): 1 stores
-// only a record's first 16 B, 2 no record bytes (the scan-side bound of
-// smaller WordPiece records)
-#ifndef LDDL_PROBE_REC
-#define LDDL_PROBE_REC 0
-#endif
-// LDDL_PROBE_L2 (measurement builds only, results not exact): the whole-word
-// probe reads 1 MB of the table (L2-resident); 2: and takes every probed word
-// as found (no records from probe misses); 3: the whole table, every probed
-// word taken as found
-#ifndef LDDL_PROBE_L2
-#define LDDL_PROBE_L2 0
-#endif
 constexpr int CAP = 2048;                // window bytes (32 per lane)
 constexpr int DCAP = 256;                // side buffer for dirty words
 constexpr int SCAN_OCC = 5;              // waves per SIMD the scan's LDS admits (4 measured 5 % slower)
@@ -1036,7 +1023,6 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void scan_kernel(TokParams P, Spli
         // then the compares, so the batch's probe round trips overlap (the
         // loads of a batch are issued back to back; no store sits between
         // them and their first use)
-        const bool fprobe = P.st == nullptr || LDDL_PROBE_L2;  // (the two-choice scan table: probed in the record pass)
         // (the entry buffer's last element: no unit's entry, no serial-path id reaches it,
         // capi.hip sizes it seg_tiles * 1 KiB + max_tok + 4096)
         const int64_t ent_spare = S.seg_tiles * 1024 + max_tok + 4095;
@@ -1053,13 +1039,13 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void scan_kernel(TokParams P, Spli
             int p, q;
             decode(u, valid, p, q, dirty[k], sj[k]);
             len[k] = q - p;
-            probe[k] = fprobe && valid && !dirty[k] && len[k] <= mbf;
+            probe[k] = valid && !dirty[k] && len[k] <= mbf;
             // (every lane: the key's reads depend on p alone and fly with the mask reads)
             key[k] = FKEY == 16 ? load_key16(L.nb, p, len[k]) : load_key(L.nb, p, len[k]);
             probe[k] = probe[k] && !((key[k].d0 & 0xFFu) >= BS && (key[k].d0 & 0xFFu) < BS + 5);
             // (every lane loads: a lane with nothing to probe reads bucket 0)
             const uint32_t hk = probe[k] ? key_hash(key[k], len[k], 0u) : 0u;
-            const uint4* bk = P.vt + 4 * (hk & vmask & ((LDDL_PROBE_L2 == 1 || LDDL_PROBE_L2 == 2) ? 0x3FFFu : ~0u));
+            const uint4* bk = P.vt + 4 * (hk & vmask);
             fa[k] = bk[0];
             fb[k] = bk[1];
           }
@@ -1071,7 +1057,7 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void scan_kernel(TokParams P, Spli
             const uint32_t want = ((uint32_t)len[k] << 16) | 0x80000000u;
             // (branch-free: a branch around the compare leaves the batch's loads
             // pending on one path, and the join then waits for every store too)
-            const bool eq = LDDL_PROBE_L2 >= 2 || slot_eq(fa[k], fb[k], key[k], want);
+            const bool eq = slot_eq(fa[k], fb[k], key[k], want);
             const bool hit = probe[k] & eq;
             const uint32_t id = fb[k].z & 0xFFFFu;
             // every lane stores (no branch around a store: the join after one
@@ -1132,23 +1118,11 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void scan_kernel(TokParams P, Spli
           STAMP(6);
           if (w != 0 && !miss && len <= 24 && len <= mb0) {
             const uint32_t hk = key_hash(key, len, 0u), want = ((uint32_t)len << 16) | 0x80000000u;
-            if (P.st && !LDDL_PROBE_L2) {
-              // the scan table: both candidate slots loaded before either compare
-              const uint4* s1 = P.st + 2 * (hk & P.st_mask);
-              const uint4* s2 = P.st + 2 * (st_second(hk) & P.st_mask);
-              const uint4 fa = s1[0], fb = s1[1], ga = s2[0], gb = s2[1];
-              const bool h1 = slot_eq(fa, fb, key, want), h2 = slot_eq(ga, gb, key, want);
-              if (h1 || h2) {
-                id = (uint16_t)((h1 ? fb.z : gb.z) & 0xFFFFu);
-                w = 0;
-              }
-            } else {
-              const uint4* bk = P.vt + 4 * (hk & vmask & ((LDDL_PROBE_L2 == 1 || LDDL_PROBE_L2 == 2) ? 0x3FFFu : ~0u));
-              const uint4 fa = bk[0], fb = bk[1];
-              if (LDDL_PROBE_L2 >= 2 || slot_eq(fa, fb, key, want)) {
-                id = (uint16_t)(fb.z & 0xFFFFu);
-                w = 0;
-              }
+            const uint4* bk = P.vt + 4 * (hk & vmask);
+            const uint4 fa = bk[0], fb = bk[1];
+            if (slot_eq(fa, fb, key, want)) {
+              id = (uint16_t)(fb.z & 0xFFFFu);
+              w = 0;
             }
           }
           if (__any(lovf)) {
@@ -1217,10 +1191,10 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void scan_kernel(TokParams P, Spli
 #pragma unroll
               for (int i = 0; i < 6; ++i) kd[i] = __builtin_amdgcn_alignbyte(xx[i + 1], xx[i], sh);
             }
-            if (LDDL_PROBE_REC < 2) *recq(S, 0, slot) = make_uint4((uint32_t)len | (nsl << 8) | 0x80000000u, 0u, kd[0], kd[1]);
-            if (LDDL_PROBE_REC < 1) *recq(S, 1, slot) = make_uint4(kd[2], kd[3], kd[4], kd[5]);
+            *recq(S, 0, slot) = make_uint4((uint32_t)len | (nsl << 8) | 0x80000000u, 0u, kd[0], kd[1]);
+            *recq(S, 1, slot) = make_uint4(kd[2], kd[3], kd[4], kd[5]);
             // key bytes 24..55 (wp_kernel reads them only for a longer key)
-            if (LDDL_PROBE_REC < 1 && len > 24) {
+            if (len > 24) {
               uint32_t xx[9];
 #pragma unroll
               for (int i = 0; i < 9; ++i) xx[i] = L.nb[a + 6 + i];
@@ -1602,183 +1576,6 @@ __global__ __launch_bounds__(64 * WAVES) void wp_kernel(TokParams P, SplitParams
   }
 }
 
-// ---------------------------------------------------- WordPiece by trie --
-// The same records, pieces and counts as wp_kernel, found by walking the
-// vocab's double-array trie (tok_tables.h build_trie, common.h trie_*): per
-// step one byte of the key and one 8-B entry load; the walk from a piece
-// start ends where no key extends the bytes read, and the longest prefix it
-// accepted on the way is the piece (greedy longest-match-first, exactly
-// WordPiece's); the next piece's walk starts from the "##" root at its end.
-// No Bloom filter and no key hashing: ~30 instructions per step against
-// ~470 per step of wp_kernel's Bloom scan.  One record per lane with refill,
-// as wp_kernel (a lane whose word ends begins the next record in the same
-// step); WPT_STEPS steps per round of the refill bookkeeping.
-// Measured, not kept as the default (LDDL_WP_ALGO=trie selects it):
-// 2.08 / 2.34 / 2.56 ms per GB of corpus at WPT_STEPS 8 / 4 / 2 against
-// wp_kernel's 1.28 (profiles/r5_wp_trie_ab.txt).  The steps are cheap but
-// each is a dependent ~L2 round trip (~13 per record), and the refill
-// bookkeeping per round costs what the Bloom scan saves.
-#ifdef LDDL_WPT_STEPS
-constexpr int WPT_STEPS = LDDL_WPT_STEPS;  // (A/B builds, tools/ab_build.py)
-#else
-constexpr int WPT_STEPS = 8;
-#endif
-
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void wpt_kernel(TokParams P, SplitParams S) {
-  __shared__ uint32_t kbuf[WAVES * 64 * KB_DW];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  uint32_t* kb = kbuf + wv * 64 * KB_DW + lane;  // dword i at kb[64 * i]
-  auto kbyte = [&](int i) { return (kb[64 * min(i >> 2, KB_DW - 1)] >> (8 * (i & 3))) & 0xFFu; };
-  const uint32_t nch = min(__builtin_amdgcn_readfirstlane(*S.chunk_ctr), S.n_chunks);
-  const uint32_t nwaves = gridDim.x * WAVES;
-  const uint2* const trie = P.trie;
-  const uint32_t rb0 = P.trie_base[0], rb1 = P.trie_base[1];
-  uint32_t* const wctr = S.chunk_ctr + 1;  // zeroed with chunk_ctr per segment
-  uint32_t c = blockIdx.x * WAVES + wv, off = 0, fill = 0;
-  uint32_t cn = 0;  // (lane 0) the next chunk
-  if (c < nch) {
-    fill = __builtin_amdgcn_readfirstlane(S.chunk_fill[c]);
-    if (lane == 0) cn = nwaves + atomicAdd(wctr, 1u);
-  }
-  auto advance = [&]() {
-    while (off >= fill && c < nch) {
-      c = (uint32_t)__builtin_amdgcn_readlane((int)cn, 0);
-      off = 0;
-      fill = 0u;
-      if (c < nch) {
-        fill = __builtin_amdgcn_readfirstlane(S.chunk_fill[c]);
-        if (lane == 0) cn = nwaves + atomicAdd(wctr, 1u);
-      }
-    }
-  };
-  advance();
-  uint32_t nrec = 0;
-  int r = -1;   // record slot being tokenised
-  int pr = -1;  // record slot loaded, not begun
-  uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0, q2 = q0, q3 = q0;
-  bool qlong = false;
-  int q = 0, len = 0, ps = 0, la = -1, np = 0;
-  uint32_t node = 0, nbase = 0, laid = 0;
-  uint4* const outs = S.pcs;
-  uint32_t pw01 = 0, pw23 = 0;
-  auto put_piece = [&](int k, uint32_t id) {
-    if (k < 4) {
-      const uint32_t sh = 16u * (uint32_t)(k & 1);
-      const uint32_t keep = ~(0xFFFFu << sh), val = id << sh;
-      if (k < 2) pw01 = (pw01 & keep) | val;
-      else pw23 = (pw23 & keep) | val;
-    } else {
-      reinterpret_cast<uint16_t*>(outs + (size_t)r * 4)[piece_at(k)] = (uint16_t)id;
-    }
-  };
-  auto finish = [&]() {
-    S.pch[r] = make_uint4((uint32_t)np, pw01, pw23, 0u);
-    S.cnt8[r] = (uint8_t)np;
-    r = -1;
-  };
-  for (;;) {
-    // ---- the walk: WPT_STEPS trie steps of each working lane
-#pragma unroll
-    for (int st = 0; st < WPT_STEPS; ++st) {
-      if (r >= 0) {
-        const uint32_t idx = nbase + kbyte(q);
-        const uint2 t = trie[idx];
-        if (trie_check(t) == node) {
-          node = idx;
-          nbase = trie_base(t);
-          ++q;
-          if (trie_accept(t)) {
-            la = q;
-            laid = trie_id(t);
-          }
-          if (q < len) continue;
-        }
-        // the walk stopped: at the word's end, or no key extends [ps, q]
-        if (la >= 0) {
-          put_piece(np, laid);
-          ++np;
-          if (la == len) {
-            finish();
-          } else {  // the next piece, "##", from the end of this one
-            q = ps = la;
-            la = -1;
-            node = 1;
-            nbase = rb1;
-          }
-        } else {  // some position has no match: the whole word is [UNK]
-          np = 0;
-          put_piece(0, (uint32_t)P.unk);
-          np = 1;
-          finish();
-        }
-      }
-    }
-    // ---- idle lanes take the next slots of the stream (one record ahead)
-    {
-      const uint64_t idle = __ballot(pr < 0);
-      if (idle != 0 && c < nch) {
-        const uint32_t avail = fill - off;
-        const int k = lane_rank(idle);
-        if (pr < 0 && (uint32_t)k < avail) {
-          pr = (int)(c * SPLIT_CHUNK + off + (uint32_t)k);
-          q0 = *recq(S, 0, (uint32_t)pr);
-          q1 = *recq(S, 1, (uint32_t)pr);
-          q2 = q3 = make_uint4(0, 0, 0, 0);
-          qlong = false;
-        }
-        off += min((uint32_t)__popcll(idle), avail);
-        advance();
-      }
-    }
-    // ---- an extension slot is dropped, a long key's bytes 24.. loaded, idle
-    //      lanes with a loaded record begin it
-    if (pr >= 0) {
-      if (q0.x == 0u) {
-        pr = -1;
-      } else if ((q0.x & 0xFFu) > 24u && !qlong) {
-        q2 = *recq(S, 2, (uint32_t)pr);
-        q3 = *recq(S, 3, (uint32_t)pr);
-        qlong = true;
-      } else if (r < 0) {
-        len = (int)(q0.x & 0xFFu);
-        kb[0] = q0.z; kb[64] = q0.w;
-        kb[128] = q1.x; kb[192] = q1.y; kb[256] = q1.z; kb[320] = q1.w;
-        kb[384] = q2.x; kb[448] = q2.y; kb[512] = q2.z; kb[576] = q2.w;
-        kb[640] = q3.x; kb[704] = q3.y; kb[768] = q3.z; kb[832] = q3.w;
-        kb[896] = 0u;
-        kb[960] = 0u;
-        r = pr;
-        pr = -1;
-        ++nrec;
-        q = ps = 0;
-        la = -1;
-        np = 0;
-        node = 0;
-        nbase = rb0;
-      }
-    }
-    if (__ballot(r >= 0 || pr >= 0) == 0 && c >= nch) break;
-  }
-  if (S.n_rec) {
-    const uint32_t tot = lane_get(wave_incl_add(nrec), 63);
-    if (lane == 0 && tot) atomicAdd(S.n_rec, (unsigned long long)tot);
-  }
-}
-
-template <int WAVES>
-static hipError_t launch_wpt(const TokParams& P, const SplitParams& S, int n_cu, hipStream_t s) {
-  static int per_cu = 0;
-  if (per_cu == 0 &&
-      (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, wpt_kernel<WAVES>, 64 * WAVES, 0) != hipSuccess ||
-       per_cu < 1))
-    per_cu = 1;
-  const int64_t grid = (int64_t)n_cu * per_cu;
-  hipLaunchKernelGGL(wpt_kernel<WAVES>, dim3((unsigned)grid), dim3(64 * WAVES), 0, s, P, S);
-  return hipGetLastError();
-}
-
 // ---------------------------------------------------------------- count --
 // Final token count per sentence of the segment: its direct ids (the scan's
 // entries that are vocab ids) + the pieces of its queued words (wp_kernel's
@@ -2005,7 +1802,7 @@ static hipError_t launch_wp(const TokParams& P, const SplitParams& S, int n_cu, 
 
 }  // namespace tok5
 
-constexpr int SCAN_WAVES = 4, WP_WAVES = 12, WPT_WAVES = 8;
+constexpr int SCAN_WAVES = 4, WP_WAVES = 12;
 hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_grid, hipStream_t s);
 
 int64_t split_seg_slots(int64_t seg_tiles, int n_cu) {
@@ -2066,12 +1863,7 @@ hipError_t launch_tokenize_split(const TokParams& P, int64_t nbytes, int64_t* ti
     if (P.dbg) e = tok5::launch_scan<SCAN_WAVES, true, tok5::SCAN_OCC>(P, S, n_cu, s);
     else e = tok5::launch_scan<SCAN_WAVES, false, tok5::SCAN_OCC>(P, S, n_cu, s);
     if (e != hipSuccess || (e = mark(0, 1)) != hipSuccess || (e = mark(1, 0)) != hipSuccess) return e;
-    // WordPiece by Bloom scan + bucket probes (default) or by trie walk
-    // (LDDL_WP_ALGO=trie: A/B, slower)
-    const bool trie = getenv("LDDL_WP_ALGO") && strcmp(getenv("LDDL_WP_ALGO"), "trie") == 0;
-    if ((e = (trie && P.trie) ? tok5::launch_wpt<WPT_WAVES>(P, S, n_cu, s) : tok5::launch_wp<WP_WAVES>(P, S, n_cu, s)) !=
-        hipSuccess)
-      return e;
+    if ((e = tok5::launch_wp<WP_WAVES>(P, S, n_cu, s)) != hipSuccess) return e;
     if ((e = mark(1, 1)) != hipSuccess || (e = mark(2, 0)) != hipSuccess) return e;
     if ((e = finish_segment(P, S, n_cu, fb_grid, s)) != hipSuccess || (e = mark(2, 1)) != hipSuccess) return e;
   }

@@ -719,29 +719,40 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
   // one document visit ahead (the load flies while this visit's pairs run)
   // (with the document's first slot and length, carried to its visit)
   int df_next = 0, dn_next = 0;
-  auto doc_lens = [&](int d) -> int {
-    bool got = false;
+  // a document's first slot and length: one branch on the table's residence
+  // for both fields (if / else: no "done" flag for the scalar unit to retest)
+  auto doc_at = [&](int d, int& f, int& n) {
     if constexpr (!MASK) {
-      if (dres) {  // (one residence branch for both fields)
-        df_next = (int)DL.dfirst[d];
-        dn_next = (int)DL.dn[d];
-        got = true;
+      if (dres) {
+        f = (int)DL.dfirst[d];
+        n = (int)DL.dn[d];
+      } else {
+        f = doc_first(d);
+        n = doc_n(d);
       }
+    } else {
+      f = doc_first(d);
+      n = doc_n(d);
     }
-    if (!got) {
-      df_next = doc_first(d);
-      dn_next = doc_n(d);
-    }
-    return dn_next <= 64 && lane < dn_next ? len_at(df_next + lane) : 0;
+  };
+  // (a longer document's lanes load too, in bounds; nothing reads them: one
+  // per-lane compare, no wave-uniform "<= 64" test folded into the exec mask)
+  auto doc_lens = [&](int d) -> int {
+    doc_at(d, df_next, dn_next);
+    return lane < dn_next ? len_at(df_next + lane) : 0;
   };
   int dl_next = nd > 0 ? doc_lens(0) : 0;
   // the records of the current 64 pairs, one per lane (lane k = pair
   // (np & ~63) + k), written by one coalesced flush per 64 pairs: each pair's
   // fields are selected into these columns by the vector unit instead of
   // being packed, addressed and stored by lane 0 from scalar registers
+  uint64_t bad = 0;  // unmasked: lanes of any pair whose truncation left an empty side
+  (void)bad;
   int c_fs0 = 0, c_fs1 = 0, c_lo0 = 0, c_hi0 = 0, c_lo1 = 0, c_hi1 = 0, c_n0 = 0, c_n1 = 0, c_rn = 0;
-  auto flush = [&](int b, int cnt) {
-    if (lane < cnt) {
+  // all: a full block of 64 (no per-lane count test merged into the
+  // wave-uniform "block complete" test of every pair)
+  auto flush = [&](int b, int cnt, bool all) {
+    if (all || lane < cnt) {
       PairRec q;
       q.fs0 = s0 + c_fs0;
       q.fs1 = s0 + c_fs1;
@@ -751,7 +762,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
       q.flags = (uint16_t)(c_rn | 2);
       q.num_tokens = (uint16_t)((c_hi0 - c_lo0) + (c_hi1 - c_lo1) + 3);
       out[b + lane] = q;
-      if (b + lane < pcap) D.ntk[b + lane] = q.num_tokens;
+      if (LDSOK && b + lane < pcap) D.ntk[b + lane] = q.num_tokens;
     }
   };
   for (int dup = 0; dup < P.dup && !err; ++dup) {
@@ -770,20 +781,27 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
       int i = 0;
       while (i < len) {
         const int cs = i;
-        int cur;
-        int fbase = 0;
-        const int j = dreg ? find_fill_reg(dps, dex, dtot, cs, target, &cur, &fbase)
-                           : find_fill([&](int k) { return len_at(first + k); }, cs, len, target, lane, &cur);
-        const int nchunk = j - cs + 1;
+        // one branch on the document's residence for the fill, the A split's
+        // draw and the A length together (the draw is the same call in both)
+        int cur, j, nchunk, la;
         int a_end = 1;
-        if (nchunk >= 2) a_end = (int)rng.randint(1, nchunk - 1);
-        const int la = a_end == nchunk ? cur
-                       : dreg ? __builtin_amdgcn_readlane(dps, cs + a_end - 1) - fbase
-                              : range_sum([&](int k) { return len_at(first + k); }, cs, cs + a_end, lane);
+        if (dreg) {
+          int fbase;
+          j = find_fill_reg(dps, dex, dtot, cs, target, &cur, &fbase);
+          nchunk = j - cs + 1;
+          if (nchunk >= 2) a_end = (int)rng.randint(1, nchunk - 1);
+          // (a_end == nchunk only when nchunk == 1, and then dps[cs] - fbase
+          // is cur: one lane read in every case)
+          la = __builtin_amdgcn_readlane(dps, cs + a_end - 1) - fbase;
+        } else {
+          j = find_fill([&](int k) { return len_at(first + k); }, cs, len, target, lane, &cur);
+          nchunk = j - cs + 1;
+          if (nchunk >= 2) a_end = (int)rng.randint(1, nchunk - 1);
+          la = a_end == nchunk ? cur : range_sum([&](int k) { return len_at(first + k); }, cs, cs + a_end, lane);
+        }
         PW_GSTAMP(7)
-        PairRec r;
-        r.fs0 = s0 + first + cs;
-        r.n0 = (uint16_t)a_end;
+        // the record's slot fields relative to s0, as the columns hold them
+        int fs1, n1;
         int lb;
         bool rn;
         int i_next;
@@ -796,25 +814,14 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
             for (int t = 1; t < 10 && rdi == di; ++t) rdi = (int)rng.randbelow((uint32_t)nd);
             if (rdi == di) rn = false;
           }
-          int rfirst, rlen;  // (one branch on the table's residence for both fields)
-          bool rdone = false;
-          if constexpr (!MASK) {
-            if (dres) {
-              rfirst = (int)DL.dfirst[rdi];
-              rlen = (int)DL.dn[rdi];
-              rdone = true;
-            }
-          }
-          if (!rdone) {
-            rfirst = doc_first(rdi);
-            rlen = doc_n(rdi);
-          }
+          int rfirst, rlen;
+          doc_at(rdi, rfirst, rlen);
           // a document of <= 64 sentences: its lengths are loaded before
           // rstart is drawn (the load flies during the draw), then the fill
           // from rstart is one scan + one compare per lane (lengths >= 1:
           // the sums from rstart rise strictly, lanes below rstart hold 0)
           const bool rreg = rlen <= 64;
-          const int rl = rreg && lane < rlen ? len_at(rfirst + lane) : 0;
+          const int rl = lane < rlen ? len_at(rfirst + lane) : 0;  // (unused when !rreg)
           const int rstart = (int)rng.randint(0, rlen - 1);
           int k;
           if (rreg) {
@@ -825,14 +832,14 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
           } else {
             k = find_fill([&](int q) { return len_at(rfirst + q); }, rstart, rlen, tb, lane, &lb);
           }
-          r.fs1 = s0 + rfirst + rstart;
-          r.n1 = (uint16_t)(k - rstart + 1);
-          i_next = j - (nchunk - a_end) + 1;
+          fs1 = rfirst + rstart;
+          n1 = k - rstart + 1;
+          i_next = cs + a_end;  // (= j - (nchunk - a_end) + 1: the unused B sentences go back)
         } else {
           rn = false;
           lb = cur - la;
-          r.fs1 = s0 + first + cs + a_end;
-          r.n1 = (uint16_t)(nchunk - a_end);
+          fs1 = first + cs + a_end;
+          n1 = nchunk - a_end;
           i_next = j + 1;
         }
         PW_GSTAMP(8)
@@ -882,25 +889,30 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
           }
         }
         PW_GSTAMP(9)
-        if (__builtin_amdgcn_readfirstlane((ahi - alo < 1 || bhi - blo < 1) ? 1 : 0)) { err = PACK_EASSERT; break; }
+        // the reference's assert.  Unmasked: the test stays a lane mask (the
+        // bounds are VGPR values), OR-ed into bad and looked at once per
+        // document -- the pairs after a failing one only fill record columns
+        // that the error discards.  Masked: at once (the masking code runs on
+        // the lengths).
+        if constexpr (MASK == 0) {
+          bad |= __ballot(ahi - alo < 1 || bhi - blo < 1);
+        } else {
+          if (__builtin_amdgcn_readfirstlane((ahi - alo < 1 || bhi - blo < 1) ? 1 : 0)) { err = PACK_EASSERT; break; }
+        }
         if constexpr (MASK != 0) {  // (the masking code wants them uniform)
           alo = __builtin_amdgcn_readfirstlane(alo);
           ahi = __builtin_amdgcn_readfirstlane(ahi);
           blo = __builtin_amdgcn_readfirstlane(blo);
           bhi = __builtin_amdgcn_readfirstlane(bhi);
         }
-        r.lo0 = (uint16_t)alo; r.hi0 = (uint16_t)ahi;
-        r.lo1 = (uint16_t)blo; r.hi1 = (uint16_t)bhi;
-        r.flags = (uint16_t)((rn ? 1 : 0) | 2);
-        r.num_tokens = (uint16_t)((ahi - alo) + (bhi - blo) + 3);
         int64_t mref = 0;
         if constexpr (MASK) {
           // ---- create_masked_lm_predictions (pretrain.py:182-238) ----------
           PW_STAMP(3)
           const int la2 = ahi - alo, lb2 = bhi - blo;
           const int ntp = max(1, (int)rint((double)(la2 + lb2 + 3) * P.mlm_ratio));
-          const int fa = first + cs, fb = (int)(r.fs1 - s0);
-          const bool expl = any_spec(fa, a_end) || any_spec(fb, r.n1);
+          const int fa = first + cs, fb = fs1;
+          const bool expl = any_spec(fa, a_end) || any_spec(fb, n1);
           // explicit candidate positions (pairs holding [CLS]/[SEP] tokens,
           // rare): global scratch of this partition, keeping the LDS lists
           // small for more resident waves
@@ -929,7 +941,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
               }
             };
             seg(fa, a_end, alo, ahi, 1);
-            seg(fb, r.n1, blo, bhi, 2 + la2);
+            seg(fb, n1, blo, bhi, 2 + la2);
             gsync();  // the list's global writes visible to the trace's reads (other lanes)
           }
           // random.shuffle(cand_indexes): record the swaps, then undo them
@@ -1076,25 +1088,26 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
         }
         {
           const bool me = lane == (np & 63);
-          c_fs0 = me ? (int)(r.fs0 - s0) : c_fs0;
-          c_fs1 = me ? (int)(r.fs1 - s0) : c_fs1;
+          c_fs0 = me ? first + cs : c_fs0;
+          c_fs1 = me ? fs1 : c_fs1;
           c_lo0 = me ? alo : c_lo0;
           c_hi0 = me ? ahi : c_hi0;
           c_lo1 = me ? blo : c_lo1;
           c_hi1 = me ? bhi : c_hi1;
-          c_n0 = me ? (int)r.n0 : c_n0;
-          c_n1 = me ? (int)r.n1 : c_n1;
+          c_n0 = me ? a_end : c_n0;
+          c_n1 = me ? n1 : c_n1;
           c_rn = me ? (rn ? 1 : 0) : c_rn;
         }
         if (MASK && lane == 0) P.mref[pb + np] = mref;
         ++np;
-        if ((np & 63) == 0) flush(np - 64, 64);
+        if ((np & 63) == 0) flush(np - 64, 64, true);
         i = i_next;
         PW_GSTAMP(10)
       }
+      if (MASK == 0 && bad) err = PACK_EASSERT;
     }
   }
-  if (!err && (np & 63)) flush(np & ~63, np & 63);
+  if (!err && (np & 63)) flush(np & ~63, np & 63, false);
   PW_STAMP(3)
   if (lane == 0) P.part_err[p] = err;
   if (err) {

@@ -467,9 +467,10 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
   int64_t* tile_sent;
   SplitParams S{};
   int rc;
+  const int64_t fb_cap = fb_list_cap(seg, n_sent);  // sentence ranges, two int64 each
   // (the entry / staging buffer: u16 per byte of a segment + the last
   // sentence's ids past its end)
-  if ((rc = ws_get(c, CW_TILE_SENT, nt + 1, &tile_sent)) || (rc = ws_get(c, CW_FB_LIST, (size_t)fb_list_cap(seg), &S.fb_list)) ||
+  if ((rc = ws_get(c, CW_TILE_SENT, nt + 1, &tile_sent)) || (rc = ws_get(c, CW_FB_LIST, (size_t)(2 * fb_cap), &S.fb_list)) ||
       (rc = ws_get(c, CW_FB_COUNT, 16, &S.fb_count)) ||
       (rc = ws_get(c, CW_ENT, (size_t)seg * 1024 + (size_t)max_tok + 4096, &S.ent)) ||
       (rc = ws_get(c, CW_SHARED_BSUM, (size_t)n_chunks + 16, &S.chunk_fill)) ||
@@ -492,6 +493,7 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
   S.chunk_ctr = S.chunk_fill + n_chunks;
   S.n_chunks = (uint32_t)n_chunks;
   S.seg_tiles = seg;
+  S.fb_cap = fb_cap;
   S.seg_sent_cap = n_sent;
   S.n_fallback = c->d_counter + 8;
   if (c->timing) {

@@ -49,16 +49,38 @@ int64_t tile_count(int64_t nbytes);
 // (t % seg) % sup == 0 and of n_tiles (what the split scan reads)
 hipError_t launch_tile_bounds(const int64_t* sent_off, int64_t n_sent, int64_t n_tiles, int64_t* tile_sent,
                               int64_t* tile_off, hipStream_t s, int64_t seg = 0, int sup = 1);
-// fb_list: *fb_count sentence ranges [fb_list[2k], fb_list[2k+1]) for the
-// exact serial path (a scan window or a tile it did not model)
-hipError_t launch_tokenize_fallback(const TokParams& P, const int64_t* fb_list, const int32_t* fb_count, int grid,
-                                    hipStream_t s);
+// fb_list: min(*fb_count, fb_cap) sentence ranges [fb_list[2k], fb_list[2k+1])
+// for the exact serial path (a scan window or a tile it did not model)
+hipError_t launch_tokenize_fallback(const TokParams& P, const int64_t* fb_list, const int32_t* fb_count,
+                                    int64_t fb_cap, int grid, hipStream_t s);
 const void* tokenize_fallback_kernel_ptr();
 // fb_list = the sentence range of every tile of [0, n_tiles), *fb_count = n_tiles
 hipError_t launch_list_all_tiles(int64_t n_tiles, const int64_t* tile_sent, int64_t* fb_list, int32_t* fb_count,
-                                 hipStream_t s);
-// fallback ranges a segment of seg_tiles tiles can list (its scan windows)
-int64_t fb_list_cap(int64_t seg_tiles);
+                                 int64_t fb_cap, hipStream_t s);
+// Sentence ranges a segment of seg_tiles tiles can list in a call of n_sent
+// sentences (fb_list holds two int64 per range).  The serial path and the lane
+// tokenizer list at most one range per tile.  The split scan lists windows
+// (tokenize_split.hip: up to 31 sentences of a super-tile of 16 tiles, all
+// ending within 2048 bytes of the first one's 16-B aligned start), and any
+// window may fall back.  A window closes for one of three reasons:
+//   - it holds 31 sentences: at most n_sent / 31 windows over the whole call;
+//     empty and one-byte sentences are legal, so bytes do not bound these;
+//   - the next sentence does not fit: that sentence then ends more than
+//     2048 - 15 bytes after this window's start and is the first of the next
+//     window, so the window after that starts more than 2032 bytes later.
+//     All starts lie in the super-tile's 16 KiB, hence at most 18 such windows
+//     per super-tile (every other one 2032 bytes further: 2 * 8 + 2);
+//   - its super-tile ends: 1 per super-tile.
+// A segment has at most seg_tiles / 16 + 1 super-tiles, so the last two kinds
+// give 19 * (seg_tiles / 16 + 1) <= 2 * seg_tiles + 64 ranges, which also
+// covers one per tile.  Sizing by n_sent alone instead (a range per sentence)
+// would cost 2.3 GB at the bench shape (2^23 tiles, 142 M sentences) for a
+// list that is nearly empty; this one is 342 MB there (268 MB without the
+// sentence term).  tests/test_fb_cap_host.py checks the bound against a
+// model of the windows.
+inline int64_t fb_list_cap(int64_t seg_tiles, int64_t n_sent) {
+  return 2 * seg_tiles + 64 + (n_sent + 30) / 31;
+}
 
 // v5 (tokenize_split.hip): the tile scan resolves whole-word vocab hits and
 // hands every other word to a WordPiece record queue; a full-occupancy
@@ -106,6 +128,7 @@ struct SplitParams {
   int64_t seg_sent_cap;    // bound on the sentences of a segment (the count scan's grid)
   int64_t* fb_list;        // sentence ranges for the serial path (pairs, launch_tokenize_fallback)
   int32_t* fb_count;       // ranges listed in this segment
+  int64_t fb_cap;          // ranges fb_list holds (fb_list_cap); a writer stores range k only if k < fb_cap
   uint32_t* n_fallback;    // tiles listed over the call (lddl_tokenize_stats)
   unsigned long long* n_rec;  // optional: records run by wp_kernel (summed over the call)
 };
@@ -140,6 +163,7 @@ struct LaneParams {
   uint32_t* ctr;          // [0] tile batches handed out
   int64_t* fb_list;       // sentence-range pairs (SplitParams::fb_list)
   int32_t* fb_count;
+  int64_t fb_cap;         // (SplitParams::fb_cap)
   uint32_t* n_fallback;
   uint64_t* stats;        // optional: [0] iterations x 64, [1] lane-iterations busy, [2] slow passes
 };

@@ -74,11 +74,11 @@ __global__ void tile_bounds_search_kernel(const int64_t* sent_off, int64_t n_sen
 // Exact serial path for the listed sentence ranges (a scan window or a tile
 // the split tokenizer did not model): lane per sentence (tokenize_serial.h).
 __global__ __launch_bounds__(256) void tokenize_fallback_kernel(TokParams P, const int64_t* fb_list,
-                                                                const int32_t* fb_count) {
+                                                                const int32_t* fb_count, int64_t fb_cap) {
   __shared__ uint32_t ascii_tab[128];
   if (threadIdx.x < 128) ascii_tab[threadIdx.x] = P.pages[(uint32_t)P.top[0] * 256u + threadIdx.x];
   __syncthreads();
-  const int n = *fb_count;
+  const int n = (int)min((int64_t)*fb_count, fb_cap);  // (the writers store no range past fb_cap)
   const LdsWordBuf wb{P.ovf + ((size_t)blockIdx.x * 256 + threadIdx.x) * WB_OVF};
   const int64_t base = P.sent_off[0];
   const int wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63;
@@ -101,17 +101,13 @@ __global__ __launch_bounds__(256) void tokenize_fallback_kernel(TokParams P, con
 }
 
 int64_t tile_count(int64_t nbytes) { return (nbytes >> TILE_SHIFT) + 1; }
-// (the scan's windows: two consecutive windows of a super-tile cover more
-// than 2 KiB - 16 B, a window longer than 2 KiB holds one sentence, plus a
-// partly filled last window per super-tile -> fewer than 2 per tile; the
-// serial path lists one range per tile)
-int64_t fb_list_cap(int64_t seg_tiles) { return 2 * (2 * seg_tiles + 64); }
 const void* tokenize_fallback_kernel_ptr() { return reinterpret_cast<const void*>(&tokenize_fallback_kernel); }
 
 
 __global__ void list_all_tiles_kernel(int64_t n_tiles, const int64_t* tile_sent, int64_t* fb_list,
-                                      int32_t* fb_count) {
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tiles; t += (int64_t)gridDim.x * blockDim.x) {
+                                      int32_t* fb_count, int64_t fb_cap) {
+  const int64_t n = min(n_tiles, fb_cap);
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x) {
     fb_list[2 * t] = tile_sent[t];
     fb_list[2 * t + 1] = tile_sent[t + 1];
   }
@@ -119,8 +115,9 @@ __global__ void list_all_tiles_kernel(int64_t n_tiles, const int64_t* tile_sent,
 }
 
 hipError_t launch_list_all_tiles(int64_t n_tiles, const int64_t* tile_sent, int64_t* fb_list, int32_t* fb_count,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(list_all_tiles_kernel, dim3(1024), dim3(256), 0, s, n_tiles, tile_sent, fb_list, fb_count);
+                                 int64_t fb_cap, hipStream_t s) {
+  hipLaunchKernelGGL(list_all_tiles_kernel, dim3(1024), dim3(256), 0, s, n_tiles, tile_sent, fb_list, fb_count,
+                     fb_cap);
   return hipGetLastError();
 }
 
@@ -139,9 +136,9 @@ hipError_t launch_tile_bounds(const int64_t* sent_off, int64_t n_sent, int64_t n
   return hipGetLastError();
 }
 
-hipError_t launch_tokenize_fallback(const TokParams& P, const int64_t* fb_list, const int32_t* fb_count, int grid,
-                                    hipStream_t s) {
-  hipLaunchKernelGGL(tokenize_fallback_kernel, dim3(grid), dim3(256), 0, s, P, fb_list, fb_count);
+hipError_t launch_tokenize_fallback(const TokParams& P, const int64_t* fb_list, const int32_t* fb_count,
+                                    int64_t fb_cap, int grid, hipStream_t s) {
+  hipLaunchKernelGGL(tokenize_fallback_kernel, dim3(grid), dim3(256), 0, s, P, fb_list, fb_count, fb_cap);
   return hipGetLastError();
 }
 

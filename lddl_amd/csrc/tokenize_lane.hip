@@ -59,8 +59,10 @@ struct DevEnv {
   }
   __device__ __forceinline__ void abort_tile(const LaneState& L) const {
     const int at = atomicAdd(Q.fb_count, 1);
-    Q.fb_list[2 * at] = Q.tile_sent[L.t];
-    Q.fb_list[2 * at + 1] = Q.tile_sent[L.t + 1];
+    if (at < Q.fb_cap) {  // (one range per tile at the most: never false unless the list is mis-sized)
+      Q.fb_list[2 * at] = Q.tile_sent[L.t];
+      Q.fb_list[2 * at + 1] = Q.tile_sent[L.t + 1];
+    }
     atomicAdd(Q.n_fallback, 1u);
   }
 };
@@ -275,6 +277,7 @@ hipError_t launch_tokenize_lane(const TokParams& P, int64_t nbytes, int64_t* til
   Q.ctr = S.chunk_ctr;
   Q.fb_list = S.fb_list;
   Q.fb_count = S.fb_count;
+  Q.fb_cap = S.fb_cap;
   Q.n_fallback = S.n_fallback;
   const int64_t seg = S.seg_tiles > 0 ? S.seg_tiles : SPLIT_SEG_TILES;
   const int grid = n_cu * tok6::lane_blocks_per_cu();
@@ -303,7 +306,7 @@ hipError_t finish_lane_segment(TokParams P, const SplitParams& S, const tok6::La
                                hipStream_t s) {
   TokParams F = P;
   F.out_ids = S.ent - (S.t0 << 10);  // the serial path writes at sent_off[s] - sent_off[0]
-  hipError_t e = launch_tokenize_fallback(F, S.fb_list, S.fb_count, fb_grid, s);
+  hipError_t e = launch_tokenize_fallback(F, S.fb_list, S.fb_count, S.fb_cap, fb_grid, s);
   if (e != hipSuccess) return e;
   if ((e = launch_scan_ntok_range(P.out_ntok, S.tile_sent + S.t0, S.tile_sent + S.t1, S.seg_sent_cap, P.out_tok_off,
                                   S.scan_bsum, s)) != hipSuccess)

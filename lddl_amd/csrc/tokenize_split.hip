@@ -520,8 +520,10 @@ __global__ __launch_bounds__(64 * WAVES, OCC) void scan_kernel(TokParams P, Spli
     auto fallback = [&]() {
       if (lane == 0) {
         const int at = atomicAdd(S.fb_count, 1);
-        S.fb_list[2 * at] = sa;
-        S.fb_list[2 * at + 1] = sb;
+        if (at < S.fb_cap) {  // (fb_list_cap bounds the windows: never false unless the list is mis-sized)
+          S.fb_list[2 * at] = sa;
+          S.fb_list[2 * at + 1] = sb;
+        }
         atomicAdd(S.n_fallback, 1u);
       }
       for (int j = lane_here(); j < ns; j += 64) {
@@ -1832,7 +1834,7 @@ hipError_t launch_tokenize_serial_dense(const TokParams& P, int64_t nbytes, int6
   S.tile_sent = tile_sent;
   S.t0 = 0;
   S.t1 = n_tiles;
-  if ((e = launch_list_all_tiles(n_tiles, tile_sent, S.fb_list, S.fb_count, s)) != hipSuccess) return e;
+  if ((e = launch_list_all_tiles(n_tiles, tile_sent, S.fb_list, S.fb_count, S.fb_cap, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(smeta_fallback_kernel, dim3(1024), dim3(256), 0, s, S.smeta, P.n_sent);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   return finish_segment(P, S, n_cu, fb_grid, s);
@@ -1877,7 +1879,7 @@ hipError_t launch_tokenize_split(const TokParams& P, int64_t nbytes, int64_t* ti
 hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_grid, hipStream_t s) {
   TokParams F = P;
   F.out_ids = S.ent - (S.t0 << 10);  // the serial path writes at sent_off[s] - sent_off[0]
-  hipError_t e = launch_tokenize_fallback(F, S.fb_list, S.fb_count, fb_grid, s);
+  hipError_t e = launch_tokenize_fallback(F, S.fb_list, S.fb_count, S.fb_cap, fb_grid, s);
   if (e != hipSuccess) return e;
 #ifndef LDDL_CNT_BLOCKS
 #define LDDL_CNT_BLOCKS 256

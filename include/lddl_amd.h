@@ -108,10 +108,8 @@ int lddl_set_special_flags(lddl_ctx *ctx, int on);
 
 /* The tokenizer algorithm of the following lddl_tokenize calls (A/B and
  * tests; every algorithm gives identical ids): 5 = the split tokenizer (the
- * default), 6 = the lane tokenizer, 0 = every tile through the exact serial
- * path.  An algorithm that does not model the loaded tables falls back to 0;
- * so does 6 on a ctx created without LDDL_TOKENIZE_ALGO=6 in the
- * environment (its trie is built only then).
+ * default), 0 = every tile through the exact serial path.  The split
+ * tokenizer falls back to 0 for loaded tables it does not model.
  * *out_algo (may be NULL) receives the one selected.  Scratch is kept across
  * a switch; each call allocates what its algorithm reads. */
 int lddl_set_tokenize_algo(lddl_ctx *ctx, int algo, int *out_algo);

@@ -87,9 +87,6 @@ enum PackWs {
 // entry points that never need a buffer at the same time share a slot (the
 // CW_SHARED_* ones: one allocation serves all their users); CW_SENT_SPEC is
 // handed from lddl_tokenize to the next masked lddl_pack_bert on purpose.
-// ("tokenize": algorithms 5 and 0; the lane tokenizer, 6, takes only
-// CW_TILE_SENT, CW_FB_LIST, CW_FB_COUNT, CW_ENT, CW_SHARED_BSUM, CW_SCAN_BSUM
-// and CW_TILE_OFF.)
 enum CtxWs {
   CW_BIN_HIST,     // lddl_bin: per chunk and bin, its rows
   CW_BIN_BASE,     // lddl_bin: exclusive scan of CW_BIN_HIST
@@ -111,7 +108,6 @@ enum CtxWs {
   CW_CNT8,         // tokenize: per record slot, the word's pieces
   CW_SCAN_BSUM,    // tokenize: block sums of the token-count scan
   CW_PCH,          // tokenize: WordPiece head per record slot
-  CW_TILE_OFF,     // lane tokenizer: [tiles + 1] first byte offset of each tile
   CW_CHUNK_PART,   // lddl_row_spans: the partition of every 64 rows
   CW_PART_PB,      // lddl_row_spans: per partition, launch_chunk_parts' pair base
   CW_COUNT
@@ -159,12 +155,6 @@ struct lddl_ctx {
   uint32_t vt_mask = 0;
   uint32_t* d_vbloom = nullptr;  // its Bloom filter
   bool scan_ok = false;          // the ASCII page fits the split scan's per-byte class table
-  // lane tokenizer (tokenize_lane.hip): the vocab trie, its roots, the byte classes
-  uint2* d_trie = nullptr;
-  uint32_t trie_base[2] = {0, 0};
-  uint16_t* d_lane_ctab = nullptr;
-  bool lane_ok = false;
-  uint64_t* d_lane_stats = nullptr;
   // per-kernel timing of the split tokenizer (lddl_set_timing)
   bool timing = false;
   SplitTiming* tm = nullptr;
@@ -184,7 +174,7 @@ struct lddl_ctx {
   uint64_t mlm_cap0 = 0;     // initial masking arena (LDDL_MLM_CAP, tests)
   // scratch
   int tok_grid = 0;
-  int tok_algo = 5;  // 5 = split tokenizer, 6 = lane tokenizer, 0 = every tile through the exact serial path
+  int tok_algo = 5;  // 5 = split tokenizer, 0 = every tile through the exact serial path
   uint8_t* d_ovf = nullptr;
   uint32_t* d_counter = nullptr;
   // debug counters of the tokenizer (LDDL_TOK_DEBUG=1) and of the packers
@@ -247,9 +237,6 @@ static void free_ctx(lddl_ctx* c) {
   (void)hipFree(c->d_counter);
   (void)hipFree(c->d_ctab);
   (void)hipFree(c->d_nrec);
-  (void)hipFree(c->d_trie);
-  (void)hipFree(c->d_lane_ctab);
-  (void)hipFree(c->d_lane_stats);
   if (c->tm) {
     for (int k = 0; k < 3; ++k)
       for (int j = 0; j < 2; ++j)
@@ -280,8 +267,6 @@ static int load_table(lddl_ctx* c, const char* path) {
   int rc = build_uni_tables(path, T, err);
   if (rc) return set_err(rc, "%s", err.c_str());
   c->scan_ok = T.scan_ok;
-  c->lane_ok = T.lane_ok;
-  if ((rc = upload(&c->d_lane_ctab, T.lane_ctab.data(), T.lane_ctab.size() * 2))) return rc;
   if ((rc = upload(&c->d_top, T.top.data(), T.top.size() * 2))) return rc;
   if ((rc = upload(&c->d_pages, T.pages.data(), T.pages.size() * 4))) return rc;
   if ((rc = upload(&c->d_multi, T.multi.data(), T.multi.size() * 4))) return rc;
@@ -293,10 +278,7 @@ static int load_table(lddl_ctx* c, const char* path) {
 static int load_vocab(lddl_ctx* c, const char* path) {
   VocabTables V;
   std::string err;
-  // the trie only for the lane tokenizer (its build is the bulk of the table
-  // setup)
-  const char* algo = getenv("LDDL_TOKENIZE_ALGO");
-  int rc = build_vocab_tables(path, V, err, algo && algo[0] == '6');
+  int rc = build_vocab_tables(path, V, err);
   if (rc) return set_err(rc, "%s", err.c_str());
   c->vocab_size = (int)V.vocab.size();
   for (int k = 0; k < 5; ++k) c->special[k] = V.special[k];
@@ -312,25 +294,15 @@ static int load_vocab(lddl_ctx* c, const char* path) {
   if ((rc = upload(&c->d_voff, V.voff.data(), V.voff.size() * 4))) return rc;
   if ((rc = upload(&c->d_rpool, V.rpool.data(), V.rpool.size()))) return rc;
   if ((rc = upload(&c->d_rinfo, V.rinfo.data(), V.rinfo.size() * 4))) return rc;
-  if (V.trie.empty()) {
-    c->lane_ok = false;
-  } else {
-    if ((rc = upload(&c->d_trie, V.trie.data(), V.trie.size() * sizeof(uint2)))) return rc;
-    c->trie_base[0] = V.trie_base[0];
-    c->trie_base[1] = V.trie_base[1];
-  }
   c->vocab = std::move(V.vocab);
   return 0;
 }
 
 // the tokenizer algorithm: the one asked for, or the serial path (0) when it
-// does not model the loaded tables (the lane tokenizer needs the trie and a
-// table in which no code point normalises to more chars than its UTF-8
-// bytes; the split one keeps ids below SPLIT_EDEF and derives its byte
-// classes from the ASCII page)
+// does not model the loaded tables (the split tokenizer keeps ids below
+// SPLIT_EDEF and derives its byte classes from the ASCII page)
 static void select_tok_algo(lddl_ctx* c, int algo) {
   c->tok_algo = algo;
-  if (c->tok_algo == 6 && !c->lane_ok) c->tok_algo = 0;
   if (c->tok_algo == 5 && (!c->scan_ok || c->vocab_size > (int)SPLIT_EDEF)) c->tok_algo = 0;
 }
 
@@ -348,12 +320,11 @@ extern "C" int lddl_create(const char* vocab_path, const char* table_path, int d
   if (hipGetDeviceProperties(&prop, device) != hipSuccess) { free_ctx(c); return set_err(LDDL_EHIP, "hipGetDeviceProperties"); }
   c->n_cu = prop.multiProcessorCount;
   if ((rc = load_table(c, table_path)) || (rc = load_vocab(c, vocab_path))) { free_ctx(c); return rc; }
-  // 5: the split tokenizer (default); 6: the lane tokenizer of round 5
-  // (measured slower; A/B); 0: every tile through the
-  // exact serial path -- LDDL_TOKENIZE_ALGO selects (tests); select_tok_algo
-  // falls back to 0 for tables the algorithm does not model
+  // 5: the split tokenizer (default); 0: every tile through the exact serial
+  // path -- LDDL_TOKENIZE_ALGO selects (tests); select_tok_algo falls back to
+  // 0 for tables the split tokenizer does not model
   const char* algo = getenv("LDDL_TOKENIZE_ALGO");
-  select_tok_algo(c, !algo ? 5 : algo[0] == '0' ? 0 : algo[0] == '6' ? 6 : 5);
+  select_tok_algo(c, algo && algo[0] == '0' ? 0 : 5);
   const char* mcap = getenv("LDDL_MLM_CAP");  // initial masking arena (tests force the regrow path)
   c->mlm_cap0 = mcap ? (uint64_t)atoll(mcap) : 0;
   c->own.device = device;
@@ -478,18 +449,14 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
     return rc;
   // (the serial path (0) runs the split path's finish: count / expand read
   // smeta, snslot, cnt8 and, unconditionally, pch[0] -- one chunk of them)
-  if (c->tok_algo != 6 &&
-      ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)slots * 4, &S.rec)) || (rc = ws_get(c, CW_PCS, (size_t)slots * 4, &S.pcs)) ||
-       (rc = ws_get(c, CW_PCH, (size_t)slots, &S.pch)) || (rc = ws_get(c, CW_SHARED_META, n_sent, &S.smeta)) ||
-       (rc = ws_get(c, CW_SNSLOT, n_sent, &S.snslot)) || (rc = ws_get(c, CW_CNT8, (size_t)slots, &S.cnt8))))
+  if ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)slots * 4, &S.rec)) || (rc = ws_get(c, CW_PCS, (size_t)slots * 4, &S.pcs)) ||
+      (rc = ws_get(c, CW_PCH, (size_t)slots, &S.pch)) || (rc = ws_get(c, CW_SHARED_META, n_sent, &S.smeta)) ||
+      (rc = ws_get(c, CW_SNSLOT, n_sent, &S.snslot)) || (rc = ws_get(c, CW_CNT8, (size_t)slots, &S.cnt8)))
     return rc;
-  // (the finish pass -- count_kernel and expand_kernel of algorithms 5 and 0
-  // -- reads these unconditionally: refuse to run it without them)
-  if (c->tok_algo != 6 && (!S.pch || !S.smeta || !S.snslot || !S.cnt8 || !S.rec || !S.pcs))
+  // (the finish pass -- count_kernel and expand_kernel -- reads these
+  // unconditionally: refuse to run it without them)
+  if (!S.pch || !S.smeta || !S.snslot || !S.cnt8 || !S.rec || !S.pcs)
     return set_err(LDDL_EINVAL, "tokenize: finish scratch not allocated");
-  int64_t* tile_off = nullptr;
-  if (c->tok_algo == 6 && (rc = ws_get(c, CW_TILE_OFF, nt + 1, &tile_off))) return rc;  // (the lane tokenizer's tile starts)
-  S.tile_off = tile_off;
   S.chunk_ctr = S.chunk_fill + n_chunks;
   S.n_chunks = (uint32_t)n_chunks;
   S.seg_tiles = seg;
@@ -504,27 +471,6 @@ extern "C" int lddl_tokenize(lddl_ctx* c, const uint8_t* d_bytes, int64_t nbytes
   c->last_tok_sent = n_sent;
   if (c->tok_algo == 0) {
     HIP_TRY(launch_tokenize_serial_dense(P, nbytes, tile_sent, S, c->n_cu, c->tok_grid, st));
-  } else if (c->tok_algo == 6) {
-    tok6::LaneParams Q{};
-    Q.trie = c->d_trie;
-    Q.rbase[0] = c->trie_base[0];
-    Q.rbase[1] = c->trie_base[1];
-    if (getenv("LDDL_LANE_STATS")) {
-      if (!c->d_lane_stats) HIP_TRY(hipMalloc((void**)&c->d_lane_stats, 64));
-      HIP_TRY(hipMemsetAsync(c->d_lane_stats, 0, 64, st));
-      Q.stats = c->d_lane_stats;
-    }
-    HIP_TRY(launch_tokenize_lane(P, nbytes, tile_sent, S, Q, c->d_lane_ctab, c->n_cu, c->tok_grid, st,
-                                 c->timing ? c->tm : nullptr));
-    if (Q.stats) {
-      uint64_t h[7];
-      HIP_TRY(hipMemcpyAsync(h, Q.stats, sizeof h, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      fprintf(stderr, "[lddl tok6] lane-iterations %llu busy %.4f slow passes %llu ticks handout %llu refill %llu "
-              "slow %llu step %llu\n", (unsigned long long)h[0], h[0] ? (double)h[1] / (double)h[0] : 0.0,
-              (unsigned long long)h[2], (unsigned long long)h[3], (unsigned long long)h[4], (unsigned long long)h[5],
-              (unsigned long long)h[6]);
-    }
   } else {
     HIP_TRY(launch_tokenize_split(P, nbytes, tile_sent, S, c->n_cu, c->tok_grid, st,
                                   c->timing ? c->tm : nullptr));
@@ -554,7 +500,7 @@ extern "C" int lddl_set_special_flags(lddl_ctx* c, int on) {
 
 extern "C" int lddl_set_tokenize_algo(lddl_ctx* c, int algo, int* out_algo) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
-  if (algo != 0 && algo != 5 && algo != 6) return set_err(LDDL_EINVAL, "tokenize algo must be 0, 5 or 6");
+  if (algo != 0 && algo != 5) return set_err(LDDL_EINVAL, "tokenize algo must be 0 or 5");
   select_tok_algo(c, algo);
   if (out_algo) *out_algo = c->tok_algo;
   return 0;

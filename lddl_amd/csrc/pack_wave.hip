@@ -1,9 +1,9 @@
 // BERT NSP packing with one WAVE per partition (default packer).
 //
-// Same contract and results as pack_bert_kernel in pack.hip (reference:
-// lddl/dask/bert/pretrain.py:241-365 create_pairs_from_document, :161-176
-// _truncate_seq_pair, :386-402 _to_partition_pairs; binning.py:63-93), but
-// the partition's serial decision chain runs out of LDS and uses the 64 lanes
+// Same contract and results as the reference (lddl/dask/bert/pretrain.py:
+// 241-365 create_pairs_from_document, :161-176 _truncate_seq_pair, :386-402
+// _to_partition_pairs; binning.py:63-93), but the partition's serial decision
+// chain runs out of LDS and uses the 64 lanes
 // wherever the reference's loops are data-parallel:
 //   * MT19937 state in LDS; the twist (in 64-word chunks, ascending -- the
 //     in-place dependences of the sequential generator hold chunk-wise) and
@@ -1240,8 +1240,8 @@ hipError_t launch_pack_bert_wave(const PackParams& P, hipStream_t s) {
 
 // ------------------------------------------------------------- CodeBERT ----
 // pretrain_codebert.py:343-442 create_pairs_from_document + :236-247
-// _truncate_seq, one wave per partition (same contract and results as
-// pack_codebert_kernel in pack.hip, the lane-serial variant).  The serial
+// _truncate_seq, one wave per partition (same contract and results as the
+// reference).  The serial
 // "accumulate segments until the chunk overflows" loops become wave prefix
 // sums + ballots, _truncate_seq decides 64 coins per round, the shuffle /
 // binning are the BERT wave packer's (global-memory arrays).

@@ -45,10 +45,10 @@ struct TokParams {
 };
 
 int64_t tile_count(int64_t nbytes);
-// tile_sent (and tile_off) of every tile, or with sup > 1 only of the tiles
+// tile_sent of every tile, or with sup > 1 only of the tiles
 // (t % seg) % sup == 0 and of n_tiles (what the split scan reads)
 hipError_t launch_tile_bounds(const int64_t* sent_off, int64_t n_sent, int64_t n_tiles, int64_t* tile_sent,
-                              int64_t* tile_off, hipStream_t s, int64_t seg = 0, int sup = 1);
+                              hipStream_t s, int64_t seg = 0, int sup = 1);
 // fb_list: min(*fb_count, fb_cap) sentence ranges [fb_list[2k], fb_list[2k+1])
 // for the exact serial path (a scan window or a tile it did not model)
 hipError_t launch_tokenize_fallback(const TokParams& P, const int64_t* fb_list, const int32_t* fb_count,
@@ -58,8 +58,8 @@ const void* tokenize_fallback_kernel_ptr();
 hipError_t launch_list_all_tiles(int64_t n_tiles, const int64_t* tile_sent, int64_t* fb_list, int32_t* fb_count,
                                  int64_t fb_cap, hipStream_t s);
 // Sentence ranges a segment of seg_tiles tiles can list in a call of n_sent
-// sentences (fb_list holds two int64 per range).  The serial path and the lane
-// tokenizer list at most one range per tile.  The split scan lists windows
+// sentences (fb_list holds two int64 per range).  The serial path lists at
+// most one range per tile.  The split scan lists windows
 // (tokenize_split.hip: up to 31 sentences of a super-tile of 16 tiles, all
 // ending within 2048 bytes of the first one's 16-B aligned start), and any
 // window may fall back.  A window closes for one of three reasons:
@@ -112,7 +112,6 @@ struct SplitParams {
   int64_t seg_tiles;       // tiles per segment (SPLIT_SEG_TILES; tests force small ones)
   int64_t t0, t1;          // the segment's tiles
   const int64_t* tile_sent;
-  const int64_t* tile_off;  // sent_off[tile_sent[t]] (the scan stages a tile's bounds in one round trip)
   uint16_t* ent;
   uint4* rec;              // 4 uint4 per slot
   uint4* pcs;              // WordPiece pieces 4.. per slot (64 B per slot; the extension slot continues it)
@@ -147,29 +146,5 @@ hipError_t launch_tokenize_serial_dense(const TokParams& P, int64_t nbytes, int6
 // record slots for a segment: 1 per 14 input bytes + a partly used chunk per
 // scanning wave of the scan's real grid on n_cu CUs
 int64_t split_seg_slots(int64_t seg_tiles, int n_cu);
-
-// lane tokenizer (tokenize_lane.hip, tokenize_lane.h)
-namespace tok6 {
-struct LaneParams {
-  const uint2* trie;
-  uint32_t rbase[2];      // children bases of the two roots
-  uint16_t* stage;        // ids at (sentence byte offset - segb)
-  int64_t segb;           // absolute byte offset of staging index 0 (the host passes t0 << 10;
-                          // the kernels add sent_off[0])
-  int64_t bytes_end;      // absolute end of the corpus (set on the device; ring loads start below it)
-  const int64_t* tile_sent;
-  const int64_t* tile_off;
-  int64_t t0, t1;         // the segment's tiles
-  uint32_t* ctr;          // [0] tile batches handed out
-  int64_t* fb_list;       // sentence-range pairs (SplitParams::fb_list)
-  int32_t* fb_count;
-  int64_t fb_cap;         // (SplitParams::fb_cap)
-  uint32_t* n_fallback;
-  uint64_t* stats;        // optional: [0] iterations x 64, [1] lane-iterations busy, [2] slow passes
-};
-}  // namespace tok6
-hipError_t launch_tokenize_lane(const TokParams& P, int64_t nbytes, int64_t* tile_sent, SplitParams S,
-                                tok6::LaneParams Q, const uint16_t* d_ctab, int n_cu, int fb_grid, hipStream_t s,
-                                SplitTiming* tm);
 
 }  // namespace lddl

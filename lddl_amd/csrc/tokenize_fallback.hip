@@ -32,7 +32,7 @@ constexpr int TILE_SHIFT = 10;  // nominal tile: sentences starting in 1 KiB
 // super-tile starts in each segment of seg tiles; sup = 1: every tile) and
 // t = n_tiles
 __global__ void tile_bounds_kernel(const int64_t* sent_off, int64_t n_sent, int64_t n_tiles, int64_t* tile_sent,
-                                   int64_t* tile_off, int64_t seg, int sup) {
+                                   int64_t seg, int sup) {
   const int64_t base = sent_off[0];
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= n_sent; s += (int64_t)gridDim.x * blockDim.x) {
     // tiles t with off[s-1] < t*TILE <= off[s] map to s (s = n_sent: the rest)
@@ -44,7 +44,6 @@ __global__ void tile_bounds_kernel(const int64_t* sent_off, int64_t n_sent, int6
     for (int64_t t = t0; t <= t1 && t <= n_tiles; ++t) {
       if ((t % seg) % sup != 0 && t != n_tiles) continue;
       tile_sent[t] = s;
-      if (tile_off) tile_off[t] = sent_off[s];
     }
   }
 }
@@ -53,7 +52,7 @@ __global__ void tile_bounds_kernel(const int64_t* sent_off, int64_t n_sent, int6
 // search per tile read (first s with sent_off[s] - base >= t * TILE; n_sent if
 // none) instead of a pass over every sentence offset -- ~1/16 of the tiles
 __global__ void tile_bounds_search_kernel(const int64_t* sent_off, int64_t n_sent, int64_t n_tiles, int64_t* tile_sent,
-                                          int64_t* tile_off, int64_t seg, int sup) {
+                                          int64_t seg, int sup) {
   const int64_t base = sent_off[0];
   const int64_t per_seg = (seg + sup - 1) / sup, nseg = n_tiles > 0 ? (n_tiles + seg - 1) / seg : 0;
   const int64_t core = nseg > 0 ? (nseg - 1) * per_seg + (n_tiles - (nseg - 1) * seg + sup - 1) / sup : 0;
@@ -67,7 +66,6 @@ __global__ void tile_bounds_search_kernel(const int64_t* sent_off, int64_t n_sen
       else hi = mid;
     }
     tile_sent[t] = lo;
-    if (tile_off) tile_off[t] = sent_off[lo];
   }
 }
 
@@ -122,16 +120,15 @@ hipError_t launch_list_all_tiles(int64_t n_tiles, const int64_t* tile_sent, int6
 }
 
 hipError_t launch_tile_bounds(const int64_t* sent_off, int64_t n_sent, int64_t n_tiles, int64_t* tile_sent,
-                              int64_t* tile_off, hipStream_t s, int64_t seg, int sup) {
+                              hipStream_t s, int64_t seg, int sup) {
   const int64_t sg = seg > 0 ? seg : n_tiles + 1;
   if (sup > 1) {
     const int64_t need = n_tiles / sup + (n_tiles + sg - 1) / sg + 1;  // (>= the tiles searched)
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((need + 255) / 256, 4096));
     hipLaunchKernelGGL(tile_bounds_search_kernel, dim3(grid), dim3(256), 0, s, sent_off, n_sent, n_tiles, tile_sent,
-                       tile_off, sg, sup);
+                       sg, sup);
   } else {
-    hipLaunchKernelGGL(tile_bounds_kernel, dim3(4096), dim3(256), 0, s, sent_off, n_sent, n_tiles, tile_sent, tile_off,
-                       sg, 1);
+    hipLaunchKernelGGL(tile_bounds_kernel, dim3(4096), dim3(256), 0, s, sent_off, n_sent, n_tiles, tile_sent, sg, 1);
   }
   return hipGetLastError();
 }

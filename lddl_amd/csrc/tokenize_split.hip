@@ -1829,7 +1829,7 @@ __global__ void smeta_fallback_kernel(uint2* smeta, int64_t n_sent) {
 hipError_t launch_tokenize_serial_dense(const TokParams& P, int64_t nbytes, int64_t* tile_sent, SplitParams S,
                                         int n_cu, int fb_grid, hipStream_t s) {
   const int64_t n_tiles = tile_count(nbytes);
-  hipError_t e = launch_tile_bounds(P.sent_off, P.n_sent, n_tiles, tile_sent, nullptr, s);
+  hipError_t e = launch_tile_bounds(P.sent_off, P.n_sent, n_tiles, tile_sent, s);
   if (e != hipSuccess || (e = hipMemsetAsync(P.out_tok_off, 0, sizeof(int64_t), s)) != hipSuccess) return e;
   S.tile_sent = tile_sent;
   S.t0 = 0;
@@ -1852,7 +1852,7 @@ hipError_t launch_tokenize_split(const TokParams& P, int64_t nbytes, int64_t* ti
   const int64_t n_tiles = tile_count(nbytes);
   const int64_t seg = S.seg_tiles > 0 ? S.seg_tiles : SPLIT_SEG_TILES;
   // (the scan reads tile_sent at its super-tile starts and the segment bounds only)
-  hipError_t e = launch_tile_bounds(P.sent_off, P.n_sent, n_tiles, tile_sent, nullptr, s, seg, tok5::SUPER);
+  hipError_t e = launch_tile_bounds(P.sent_off, P.n_sent, n_tiles, tile_sent, s, seg, tok5::SUPER);
   if (e != hipSuccess) return e;
   if ((e = hipMemsetAsync(P.out_tok_off, 0, sizeof(int64_t), s)) != hipSuccess) return e;
   S.tile_sent = tile_sent;

@@ -117,7 +117,7 @@ class Tokenizer:
 
   def set_algo(self, algo):
     """the tokenizer algorithm of the following calls (lddl_set_tokenize_algo:
-    5 split, the default; 6 lane; 0 the exact serial path -- identical ids);
+    5 split, the default; 0 the exact serial path -- identical ids);
     returns the one selected (0 when the tables rule the asked one out)"""
     out = ctypes.c_int(-1)
     _lib.check(_lib.lib().lddl_set_tokenize_algo(self.handle, int(algo), ctypes.byref(out)))

@@ -119,7 +119,7 @@ def test_windows_fit_the_list(host_fb_cap, name):
     per_seg = wm.windows(off, seg, al)
     assert sum(ns for ws in per_seg for _, ns in ws) == n_sent  # the windows partition the sentences
     assert all(1 <= ns <= wm.NS_MAX for ws in per_seg for _, ns in ws)
-    assert cap >= min(seg, nt)  # one range per tile: the serial path and the lane tokenizer
+    assert cap >= min(seg, nt)  # one range per tile: the serial path
     worst = max(len(ws) for ws in per_seg)
     assert worst <= cap, (name, seg, al, worst, cap)
 

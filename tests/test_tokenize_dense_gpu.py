@@ -158,9 +158,9 @@ def test_dense_fallbacks_one_segment(gpu, monkeypatch, dense_long, name):
     assert_listed(tok, dense_long, 1 << 40, len(LONG_WORD), dense=True)
 
 
-@pytest.mark.parametrize('algo', ['0', '6'])
+@pytest.mark.parametrize('algo', ['0'])
 def test_dense_corpus_other_algorithms(gpu, monkeypatch, dense_long, algo):
-  """the serial path and the lane tokenizer (a range per tile at the most) over the same corpus: ids"""
+  """the serial path (a range per tile at the most) over the same corpus: ids"""
   tok = make_tok(monkeypatch, 'bert', algo=algo, timing=False)
   for max_tok in (512, 3):
     assert_oracle(tok, dense_long, 'bert', max_tok)

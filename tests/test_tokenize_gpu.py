@@ -123,9 +123,8 @@ def adversarial_sentences(rng, n):
   return out
 
 
-# '0': every tile through the exact serial path; '5': the split tokenizer;
-# '6': the lane tokenizer
-ALGOS = ['0', '5', '6']
+# '0': every tile through the exact serial path; '5': the split tokenizer
+ALGOS = ['0', '5']
 
 
 def _set_algo(monkeypatch, algo):
@@ -188,11 +187,13 @@ def test_hip_tokenize_split_segments_and_capacity(gpu, monkeypatch, env, name):
 @pytest.mark.parametrize('seg', ['1', '97'])
 @pytest.mark.parametrize('name', ['bert', 'codebert'])
 def test_hip_tokenize_lane_segments(gpu, monkeypatch, seg, name):
-  """The lane tokenizer (v6) over many small segments: staging, offset scan
-  and compaction continue across segment seams; max_tok 512 and 5."""
+  """The split tokenizer (v5) over the smallest segments (one tile each) and
+  over many small ones: entries, the offset scan and expand continue across
+  segment seams; max_tok 512 and 5.  (Written for the lane tokenizer, which
+  is removed; the name stays so that the case ids do.)"""
   from lddl_amd import synth
   from lddl_amd.tokenizer import Tokenizer
-  monkeypatch.setenv('LDDL_TOKENIZE_ALGO', '6')
+  monkeypatch.setenv('LDDL_TOKENIZE_ALGO', '5')
   monkeypatch.setenv('LDDL_SPLIT_SEG', seg)
   c = synth.make_wiki(600_000, seed=33) if name == 'bert' else synth.make_code(600, seed=35)
   for max_tok in (512, 5):
@@ -298,20 +299,20 @@ def test_hip_tokenize_window_packing_edges(gpu, seed):
 
 
 def test_algorithms_switched_on_one_ctx(gpu, monkeypatch):
-  """Scratch reused across tokenizer algorithms on one ctx: the lane
-  tokenizer (6, which allocates no finish scratch of its own) then the
-  serial path (0) and the split tokenizer (5), whose finish pass reads
-  pch / smeta / snslot / cnt8, then back -- every call identical to the
-  oracle (the fault of round 5: the finish pass ran over scratch another
-  algorithm had not allocated)"""
+  """Scratch reused across tokenizer algorithms on one ctx: 0 and 5 share
+  the finish scratch (pch / smeta / snslot / cnt8, which the finish pass
+  reads unconditionally; the serial path sizes them for one record chunk,
+  the split tokenizer for the segment) -- after every switch the call is
+  identical to the oracle.  Algorithms that do not exist (3, and 6, the
+  retired lane tokenizer) are refused."""
   from lddl_amd import synth
   from lddl_amd.tokenizer import Tokenizer
   c = synth.make_wiki(400_000, seed=41)
   oids, ontok = OracleTokenizer(VOCABS['bert']).run(c.data, c.sent_off, 512, nthreads=8)
   exp = compact(oids, ontok, c.sent_off)
-  monkeypatch.setenv('LDDL_TOKENIZE_ALGO', '6')  # (the ctx builds the lane tokenizer's trie only when asked)
+  monkeypatch.delenv('LDDL_TOKENIZE_ALGO', raising=False)
   tok = Tokenizer(VOCABS['bert'])
-  for algo in (6, 0, 5, 6, 5, 0):
+  for algo in (5, 0, 5, 0, 0, 5):
     assert tok.set_algo(algo) == algo
     ids, ntok = run_hip(tok, c.data, c.sent_off)
     assert np.array_equal(ntok, ontok), algo
@@ -319,3 +320,5 @@ def test_algorithms_switched_on_one_ctx(gpu, monkeypatch):
     assert all(np.array_equal(a.astype(np.int64), b.astype(np.int64)) for a, b in zip(got, exp)), algo
   with pytest.raises(Exception):
     tok.set_algo(3)
+  with pytest.raises(Exception):
+    tok.set_algo(6)

@@ -143,7 +143,7 @@ int main(int argc, char** argv) {
   const int reps = argc > 3 ? atoi(argv[3]) : 5;
   VocabTables V;
   std::string err;
-  if (build_vocab_tables(argv[1], V, err, false) != 0) {
+  if (build_vocab_tables(argv[1], V, err) != 0) {
     fprintf(stderr, "vocab: %s\n", err.c_str());
     return 1;
   }

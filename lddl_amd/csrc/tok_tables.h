@@ -122,6 +122,27 @@ inline int build_uni_tables(const char* path, UniTables& T, std::string& err) {
   return 0;
 }
 
+// Length of a vocab.txt line without its trailing white space.  The reference's
+// tokenizer reads the file line by line and trims the end of each line of every
+// code point with the Unicode White_Space property (so "\r\n" files and lines
+// with trailing blanks give the same keys as clean ones); leading and inner
+// blanks stay.
+inline size_t vocab_line_trim(const std::string& s) {
+  size_t n = s.size();
+  for (;;) {
+    const unsigned char a = n >= 1 ? (unsigned char)s[n - 1] : 0, b = n >= 2 ? (unsigned char)s[n - 2] : 0,
+                        c = n >= 3 ? (unsigned char)s[n - 3] : 0;
+    if (n >= 1 && ((a >= 0x09 && a <= 0x0D) || a == 0x20)) n -= 1;
+    else if (n >= 2 && b == 0xC2 && (a == 0x85 || a == 0xA0)) n -= 2;  // U+0085, U+00A0
+    else if (n >= 3 && ((c == 0xE1 && b == 0x9A && a == 0x80) ||                                   // U+1680
+                        (c == 0xE2 && b == 0x80 && ((a >= 0x80 && a <= 0x8A) || a == 0xA8 || a == 0xA9 || a == 0xAF)) ||
+                        (c == 0xE2 && b == 0x81 && a == 0x9F) ||                                   // U+205F
+                        (c == 0xE3 && b == 0x80 && a == 0x80)))                                    // U+3000
+      n -= 3;
+    else return n;
+  }
+}
+
 inline int build_vocab_tables(const char* path, VocabTables& V, std::string& err) {
   FILE* f = fopen(path, "rb");
   if (!f) { err = std::string("cannot open vocab ") + path; return LDDL_EIO; }
@@ -129,14 +150,17 @@ inline int build_vocab_tables(const char* path, VocabTables& V, std::string& err
   int ch;
   while ((ch = fgetc(f)) != EOF) {
     if (ch == '\n') {
-      while (!cur.empty() && cur.back() == '\r') cur.pop_back();
+      cur.resize(vocab_line_trim(cur));
       V.vocab.push_back(cur);
       cur.clear();
     } else {
       cur.push_back((char)ch);
     }
   }
-  if (!cur.empty()) V.vocab.push_back(cur);
+  if (!cur.empty()) {
+    cur.resize(vocab_line_trim(cur));
+    V.vocab.push_back(cur);
+  }
   fclose(f);
   const size_t n = V.vocab.size();
   if (n == 0 || n > 65536) { err = "vocab size " + std::to_string(n) + " not in [1, 65536]"; return LDDL_EFORMAT; }
@@ -157,7 +181,8 @@ inline int build_vocab_tables(const char* path, VocabTables& V, std::string& err
     const uint32_t cont = (w.size() >= 2 && w[0] == '#' && w[1] == '#') ? 1u : 0u;
     const char* s = w.data() + 2 * cont;
     const uint32_t len = (uint32_t)w.size() - 2 * cont;
-    if (len > 255) { err = "vocab entry " + std::to_string(i) + " longer than 255 bytes"; return LDDL_EFORMAT; }
+    // the whole entry ("##" included): rinfo below keeps its size in 8 bits
+    if (w.size() > 255) { err = "vocab entry " + std::to_string(i) + " longer than 255 bytes"; return LDDL_EFORMAT; }
     V.voff[i] = (uint32_t)V.pool.size();
     vlen[i] = len;
     vcont[i] = cont;

@@ -91,7 +91,9 @@ inline int64_t fb_list_cap(int64_t seg_tiles, int64_t n_sent) {
 //          sent_off[s] - sent_off[0] - t0 * 1 KiB + k, one per unit (k = its
 //          rank in the sentence): a vocab id, SPLIT_EHOLE for an empty unit,
 //          or SPLIT_EDEF | (record slot - the tile's first slot) for a word of
-//          the queue (the serial path's ids of a fallback tile land here too)
+//          the queue (the serial path's ids of a fallback tile land here too:
+//          plain ids; when every tile is one -- the only way a vocabulary of
+//          more than SPLIT_EDEF entries runs -- expand takes every value as an id)
 //   rec    64-B record slots in chunks of SPLIT_CHUNK, chunk_fill[c] used;
 //          a tile's slots contiguous, in unit order
 //   smeta  per sentence: #entries | first slot relative to the tile's << 16,

@@ -1641,6 +1641,11 @@ struct ExpLds {
   uint32_t hf[64];   // hf[k] = the step's tag: some sentence's first entry is the step's entry k
 };
 
+// ALL_DIRECT: every entry is an id, whatever its value -- the serial path over
+// every tile (launch_tokenize_serial_dense), the only one a vocabulary of more
+// than SPLIT_EDEF entries runs: its ids reach the values that otherwise mean
+// "queued word" (>= SPLIT_EDEF) and "empty unit" (SPLIT_EHOLE).
+template <bool ALL_DIRECT>
 __global__ __launch_bounds__(256) void expand_kernel(TokParams P, SplitParams S) {
   __shared__ ExpLds X[4];
   const int lane = threadIdx.x & 63;
@@ -1724,7 +1729,7 @@ __global__ __launch_bounds__(256) void expand_kernel(TokParams P, SplitParams S)
       u32x3 xr[EXP_K];
 #pragma unroll
       for (int k = 0; k < EXP_K; ++k) {
-        const bool r = xin[k] && xv[k] >= SPLIT_EDEF && xv[k] != SPLIT_EHOLE;
+        const bool r = !ALL_DIRECT && xin[k] && xv[k] >= SPLIT_EDEF && xv[k] != SPLIT_EHOLE;
         xr[k] = u32x3{0u, 0u, 0u};
         if (st0 + 64 * k < T)
           xr[k] = *reinterpret_cast<const u32x3*>(pch + (r ? (size_t)(E.sn[xj[k]].qb + (xv[k] & 0xFFFu)) : 0));
@@ -1734,9 +1739,9 @@ __global__ __launch_bounds__(256) void expand_kernel(TokParams P, SplitParams S)
         const uint32_t st = st0 + 64 * k;
         if (st >= T) break;
         const uint32_t cj = xj[k], cv = xin[k] ? xv[k] : 0u;
-        const bool cin = xin[k], rec = cin && cv >= SPLIT_EDEF && cv != SPLIT_EHOLE;
+        const bool cin = xin[k], rec = !ALL_DIRECT && cin && cv >= SPLIT_EDEF && cv != SPLIT_EHOLE;
         // (a hole: an empty unit, no token; a direct id: one)
-        const u32x3 rq = rec ? xr[k] : u32x3{cin && cv != SPLIT_EHOLE ? 1u : 0u, 0u, 0u};
+        const u32x3 rq = rec ? xr[k] : u32x3{cin && (ALL_DIRECT || cv != SPLIT_EHOLE) ? 1u : 0u, 0u, 0u};
         const ExpSent sj = E.sn[cj];
         const size_t ri = (size_t)(sj.qb + (cv & 0xFFFu)) * 4;
         const uint32_t cnt = rq.x;
@@ -1755,7 +1760,7 @@ __global__ __launch_bounds__(256) void expand_kernel(TokParams P, SplitParams S)
         if (nw) {
           uint16_t* o = P.out_ids + sj.dst + p;
           // (the first token of a direct id and of a record in one store)
-          o[0] = (uint16_t)(cv < SPLIT_EDEF ? cv : rq.y & 0xFFFFu);
+          o[0] = (uint16_t)(ALL_DIRECT || cv < SPLIT_EDEF ? cv : rq.y & 0xFFFFu);
           if (nw > 1) o[1] = (uint16_t)(rq.y >> 16);
           if (nw > 2) o[2] = (uint16_t)(rq.z & 0xFFFFu);
           if (nw > 3) o[3] = (uint16_t)(rq.z >> 16);
@@ -1805,7 +1810,7 @@ static hipError_t launch_wp(const TokParams& P, const SplitParams& S, int n_cu, 
 }  // namespace tok5
 
 constexpr int SCAN_WAVES = 4, WP_WAVES = 12;
-hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_grid, hipStream_t s);
+hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_grid, hipStream_t s, bool all_direct = false);
 
 int64_t split_seg_slots(int64_t seg_tiles, int n_cu) {
   // 1 slot per 14 input bytes (the synthetic Wikipedia corpus queues ~0.02
@@ -1837,7 +1842,7 @@ hipError_t launch_tokenize_serial_dense(const TokParams& P, int64_t nbytes, int6
   if ((e = launch_list_all_tiles(n_tiles, tile_sent, S.fb_list, S.fb_count, S.fb_cap, s)) != hipSuccess) return e;
   hipLaunchKernelGGL(smeta_fallback_kernel, dim3(1024), dim3(256), 0, s, S.smeta, P.n_sent);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  return finish_segment(P, S, n_cu, fb_grid, s);
+  return finish_segment(P, S, n_cu, fb_grid, s, true);
 }
 
 hipError_t launch_tokenize_split(const TokParams& P, int64_t nbytes, int64_t* tile_sent, SplitParams S, int n_cu,
@@ -1875,8 +1880,8 @@ hipError_t launch_tokenize_split(const TokParams& P, int64_t nbytes, int64_t* ti
 // The end of a segment: the serial path over the tiles the scan listed (its
 // ids into the segment's entry buffer, as direct ids), the final counts, their
 // exclusive scan continuing the previous segment's (out_tok_off), and the
-// dense ids.
-hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_grid, hipStream_t s) {
+// dense ids.  all_direct: every tile of the call went through the serial path.
+hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_grid, hipStream_t s, bool all_direct) {
   TokParams F = P;
   F.out_ids = S.ent - (S.t0 << 10);  // the serial path writes at sent_off[s] - sent_off[0]
   hipError_t e = launch_tokenize_fallback(F, S.fb_list, S.fb_count, S.fb_cap, fb_grid, s);
@@ -1903,7 +1908,8 @@ hipError_t finish_segment(TokParams P, const SplitParams& S, int n_cu, int fb_gr
     return b > 0 && b <= 4096 ? b : 192;
   }();
   const int64_t exp_grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)n_cu * exp_blocks, (S.seg_sent_cap + 255) / 256));
-  hipLaunchKernelGGL(tok5::expand_kernel, dim3((unsigned)exp_grid), dim3(256), 0, s, P, S);
+  if (all_direct) hipLaunchKernelGGL(tok5::expand_kernel<true>, dim3((unsigned)exp_grid), dim3(256), 0, s, P, S);
+  else hipLaunchKernelGGL(tok5::expand_kernel<false>, dim3((unsigned)exp_grid), dim3(256), 0, s, P, S);
   return hipGetLastError();
 }
 

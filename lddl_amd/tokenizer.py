@@ -13,6 +13,9 @@ import torch
 
 from . import _lib
 
+# the Unicode White_Space code points (what the reference's tokenizer trims off a vocab line's end)
+_WHITE_SPACE = ''.join(map(chr, list(range(0x09, 0x0E)) + [0x20, 0x85, 0xA0, 0x1680] + list(range(0x2000, 0x200B)) +
+                           [0x2028, 0x2029, 0x202F, 0x205F, 0x3000]))
 TOKENS_MAX = 65534  # lddl_tokenize's max_tok bound (u16 per-sentence counts)
 
 
@@ -50,10 +53,16 @@ class Tokenizer:
     ids = (ctypes.c_int32 * 5)()
     _lib.check(L.lddl_special_ids(h, ids))
     self.pad_id, self.unk_id, self.cls_id, self.sep_id, self.mask_id = list(ids)
-    with open(vocab_file, encoding='utf-8') as f:
-      self.ids_to_tokens = [l.rstrip('\n').rstrip('\r') for l in f]
-    if self.ids_to_tokens and self.ids_to_tokens[-1] == '' and len(self.ids_to_tokens) > self.vocab_size:
-      self.ids_to_tokens.pop()
+    # the lines as the native tables read them (tok_tables.h): split at '\n'
+    # only, trailing White_Space trimmed; a duplicate line's last id wins
+    with open(vocab_file, 'rb') as f:
+      lines = f.read().split(b'\n')
+    if lines and lines[-1] == b'':
+      lines.pop()
+    self.ids_to_tokens = [l.decode('utf-8', 'replace').rstrip(_WHITE_SPACE) for l in lines]
+    if len(self.ids_to_tokens) != self.vocab_size:
+      raise RuntimeError('lddl_amd: %s has %d lines here and %d entries in the device tables (did the file change?)'
+                         % (vocab_file, len(self.ids_to_tokens), self.vocab_size))
     self.vocab = {t: i for i, t in enumerate(self.ids_to_tokens)}
 
   def close(self):

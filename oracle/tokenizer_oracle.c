@@ -85,6 +85,29 @@ static int vocab_find(const orc_tok_t *t, const char *s, int n) {
   }
 }
 
+/* n without the trailing code points that have the Unicode White_Space
+ * property (Rust's str::trim_end): U+0009-000D, 0020, 0085, 00A0, 1680,
+ * 2000-200A, 2028, 2029, 202F, 205F, 3000 */
+static int trim_white_space(const char *s, int n) {
+  for (;;) {
+    unsigned a = n >= 1 ? (unsigned char)s[n - 1] : 0, b = n >= 2 ? (unsigned char)s[n - 2] : 0;
+    unsigned c = n >= 3 ? (unsigned char)s[n - 3] : 0;
+    unsigned cp = 0xFFFFFFFFu;
+    int len = 0;
+    if (n >= 1 && a < 0x80) { cp = a; len = 1; }
+    else if (n >= 2 && (b & 0xE0) == 0xC0 && (a & 0xC0) == 0x80) { cp = (b & 0x1F) << 6 | (a & 0x3F); len = 2; }
+    else if (n >= 3 && (c & 0xF0) == 0xE0 && (b & 0xC0) == 0x80 && (a & 0xC0) == 0x80) {
+      cp = (c & 0x0F) << 12 | (b & 0x3F) << 6 | (a & 0x3F);
+      len = 3;
+    }
+    int ws = (cp >= 0x09 && cp <= 0x0D) || cp == 0x20 || cp == 0x85 || cp == 0xA0 || cp == 0x1680 ||
+             (cp >= 0x2000 && cp <= 0x200A) || cp == 0x2028 || cp == 0x2029 || cp == 0x202F || cp == 0x205F ||
+             cp == 0x3000;
+    if (!ws) return n;
+    n -= len;
+  }
+}
+
 void orc_tok_destroy(void *h) {
   orc_tok_t *t = (orc_tok_t *)h;
   if (!t) return;
@@ -116,7 +139,7 @@ void *orc_tok_create(const char *vocab_path, const char *table_path) {
   }
   fclose(f);
 
-  /* vocab.txt: line i -> id i, trailing whitespace trimmed */
+  /* vocab.txt: line i -> id i, trailing White_Space trimmed (the crate's WordPiece::read_file: trim_end) */
   f = fopen(vocab_path, "rb");
   if (!f) { orc_tok_destroy(t); return NULL; }
   int cap = 1024;
@@ -124,7 +147,8 @@ void *orc_tok_create(const char *vocab_path, const char *table_path) {
   char line[4096];
   while (fgets(line, sizeof line, f)) {
     int n = (int)strlen(line);
-    while (n > 0 && (line[n - 1] == '\n' || line[n - 1] == '\r' || line[n - 1] == ' ' || line[n - 1] == '\t')) --n;
+    if (n > 0 && line[n - 1] == '\n') --n;
+    n = trim_white_space(line, n);
     if (t->n_vocab == cap) { cap *= 2; t->vocab = (vent_t *)realloc(t->vocab, sizeof(vent_t) * cap); }
     t->vocab[t->n_vocab].str = (char *)malloc(n + 1);
     memcpy(t->vocab[t->n_vocab].str, line, n);

@@ -314,6 +314,52 @@ int lddl_mask_tokens(lddl_ctx *ctx, int64_t *d_inputs, const int64_t *d_special_
                      int64_t n_rows, int64_t seq_len, double mlm_probability, int64_t ignore_index, uint64_t seed,
                      uint64_t counter, void *stream);
 
+/* ---- collate straight from a pack result ---------------------------------
+ * The same lddl/torch/bert.py:69-153 `_to_encoded_inputs` (+ :156-196
+ * `_mask_tokens`) for rows that never became parquet: batch row r is row
+ * g = d_rows[r] (d_rows NULL: g = row0 + r) of a pack result's spans
+ * (lddl_row_spans over the dense ids), 0 <= g < n_total; any order, repeats
+ * allowed.  For users who pack and train in one job; the token ids are the
+ * ones lddl_collate_bert would look the rendered strings up to.
+ *
+ * lddl_collate_rows_seq_len: the batch's padded length = max over its rows of
+ * len0[g] + len1[g] + 3, rounded up to seq_align (bert.py:94-101; d_len0 /
+ * d_len1 = lddl_row_spans' outputs).  Synchronises the stream.  A row index
+ * outside [0, n_total) is LDDL_EINDEX (checked before any load through it),
+ * n_rows == 0 LDDL_EINVAL. */
+int lddl_collate_rows_seq_len(lddl_ctx *ctx, const uint16_t *d_len0, const uint16_t *d_len1, const int64_t *d_rows,
+                              int64_t row0, int64_t n_rows, int64_t n_total, int32_t seq_align,
+                              int64_t *out_seq_len, void *stream);
+
+/* Fill the [n_rows, seq_len] int64 outputs of lddl_collate_bert
+ * (bert.py:102-152) from the spans: with a = len0[g], b = len1[g],
+ * n = a + b + 3, input_ids[r] = [CLS] d_ids[src0[g] .. +a) [SEP]
+ * d_ids[src1[g] .. +b) [SEP] padded with 0, token_type_ids 1 on [a + 2, n),
+ * attention_mask 1 on [0, n), next_sentence_labels[r] = flags[g] & 1, and
+ * d_labels by mode, numbered as in lddl_collate_bert:
+ *   0  special_tokens_mask (columns 0, a + 1 and >= n - 1);
+ *   1  static masking from lddl_masked_lm_spans' arrays (required; NULL in the
+ *      other modes): for k in [mlm_off[g], mlm_off[g+1]) input_ids[r,
+ *      mlm_pos[k]] = mlm_token[k], labels[r, mlm_pos[k]] = mlm_label[k],
+ *      ignore_index elsewhere (bert.py:113-116);
+ *   2  mode 0 then lddl_mask_tokens (bert.py:156-196) with row = r: bit for
+ *      bit lddl_collate_bert mode 2 on the same rows, seed and counter.
+ * d_ids .. d_flags: the dense ids (with their 16 entries of padding) and
+ * lddl_row_spans' outputs, [n_total] each.  Synchronises the stream.
+ * Errors, first one wins, none faults: LDDL_EINDEX (a row index outside
+ * [0, n_total), checked before any load through it; a static position >=
+ * seq_len), LDDL_ECAPACITY (a row longer than seq_len, seq_len > 2048),
+ * LDDL_EINVAL (a row whose flags lack bit 1: a CodeBERT row without
+ * docstring has no [SEP] after segment 0, and bert.py has no CodeBERT
+ * loader). */
+int lddl_collate_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                      const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags, const int64_t *d_rows,
+                      int64_t row0, int64_t n_rows, int64_t n_total, const int64_t *d_mlm_off,
+                      const uint16_t *d_mlm_pos, const uint16_t *d_mlm_label, const uint16_t *d_mlm_token,
+                      int64_t seq_len, int32_t mode, int64_t ignore_index, double mlm_probability, uint64_t seed,
+                      uint64_t counter, int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_attention_mask,
+                      int64_t *d_labels, int64_t *d_next_sentence_labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

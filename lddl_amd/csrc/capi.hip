@@ -99,8 +99,8 @@ enum CtxWs {
   CW_ENT,          // tokenize: the segment's entry / staging buffer
   CW_SHARED_ROWS,  // tokenize: rec, the record slots; lddl_render_strings / _npy / _masked: lens, bytes per row
   CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan
-  CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate_seq_len: max_len
-  CW_COLLATE_ERR,  // lddl_collate_bert: the error word
+  CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len
+  CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len]: the error word
   CW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP]; written by lddl_tokenize (lddl_set_special_flags),
                    // read by the next masked lddl_pack_bert over the same buffers (pack_common)
   CW_PCS,          // tokenize: WordPiece pieces 4.. per record slot
@@ -1355,5 +1355,115 @@ extern "C" int lddl_mask_tokens(lddl_ctx* c, int64_t* d_inputs, const int64_t* d
   M.seed = seed;
   M.counter = counter;
   HIP_TRY(launch_mask_tokens(M, c->n_cu, (hipStream_t)stream));
+  return 0;
+}
+
+// ---------------------------------------------- collate from a pack result --
+static int collate_rows_error(uint32_t e, int64_t seq_len) {
+  const unsigned long long row = e >> 4;
+  switch (e & 15u) {
+    case CERR_ROW_INDEX: return set_err(LDDL_EINDEX, "batch row %llu: row index out of range", row);
+    case CERR_LONG: return set_err(LDDL_ECAPACITY, "batch row %llu longer than seq_len %lld", row, (long long)seq_len);
+    case CERR_POS_RANGE:
+      return set_err(LDDL_EINDEX, "batch row %llu: masked position out of range for seq_len %lld", row,
+                     (long long)seq_len);
+    default:
+      return set_err(LDDL_EINVAL, "batch row %llu has no [SEP] after its first segment (a CodeBERT row)", row);
+  }
+}
+
+extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                         const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                         int32_t seq_align, int64_t* out_seq_len, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0 || seq_align < 1 || !out_seq_len)
+    return set_err(LDDL_EINVAL, "bad n_rows / n_total / seq_align / out");
+  if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
+  if (!d_len0 || !d_len1) return set_err(LDDL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateRowsParams P{};
+  P.len0 = d_len0;
+  P.len1 = d_len1;
+  P.rows = d_rows;
+  P.row0 = row0;
+  P.n_rows = n_rows;
+  P.n_total = n_total;
+  int rc;
+  if ((rc = ws_get(c, CW_SHARED_META, 1, &P.max_len)) || (rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
+  HIP_TRY(hipMemsetAsync(P.max_len, 0, 4, st));
+  HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
+  HIP_TRY(launch_collate_rows_len(P, c->n_cu, st));
+  HIP_TRY(hipMemcpyAsync(&c->h_tot[6], P.max_len, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&c->h_tot[7], P.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t e = *(const uint32_t*)&c->h_tot[7];
+  if (e) return collate_rows_error(e, 0);
+  const int64_t m = *(const int32_t*)&c->h_tot[6];
+  *out_seq_len = ((m - 1) / seq_align + 1) * seq_align;
+  return 0;
+}
+
+extern "C" int lddl_collate_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                 const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                 const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                 const int64_t* d_mlm_off, const uint16_t* d_mlm_pos, const uint16_t* d_mlm_label,
+                                 const uint16_t* d_mlm_token, int64_t seq_len, int32_t mode, int64_t ignore_index,
+                                 double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                 int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
+                                 int64_t* d_next_sentence_labels, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0) return set_err(LDDL_EINVAL, "negative n_rows / n_total");
+  if (mode < COLLATE_SPECIAL_MASK || mode > COLLATE_DYNAMIC) return set_err(LDDL_EINVAL, "mode %d not in 0..2", mode);
+  if (seq_len < 3 || seq_len > COLLATE_MAX_LEN)
+    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [3, %d]", (long long)seq_len, COLLATE_MAX_LEN);
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  if (n_rows > 0 && (!d_ids || !d_src0 || !d_src1 || !d_len0 || !d_len1 || !d_flags || !d_input_ids ||
+                     !d_token_type_ids || !d_attention_mask || !d_labels || !d_next_sentence_labels))
+    return set_err(LDDL_EINVAL, "null pointer");
+  if (mode == COLLATE_STATIC && n_rows > 0 && (!d_mlm_off || !d_mlm_pos || !d_mlm_label || !d_mlm_token))
+    return set_err(LDDL_EINVAL, "static masking needs lddl_masked_lm_spans' arrays");
+  if (n_rows == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateRowsParams P{};
+  P.ids = d_ids;
+  P.src0 = d_src0;
+  P.src1 = d_src1;
+  P.len0 = d_len0;
+  P.len1 = d_len1;
+  P.flags = d_flags;
+  P.rows = d_rows;
+  P.row0 = row0;
+  P.n_rows = n_rows;
+  P.n_total = n_total;
+  P.mlm_off = d_mlm_off;
+  P.mlm_pos = d_mlm_pos;
+  P.mlm_label = d_mlm_label;
+  P.mlm_token = d_mlm_token;
+  P.cls = (int32_t)c->special[2];
+  P.sep = (int32_t)c->special[3];
+  P.mask_id = (int32_t)c->special[4];
+  P.n_random = c->vocab_size;
+  P.seq_len = (int32_t)seq_len;
+  P.ignore_index = ignore_index;
+  P.mlm_probability = mlm_probability;
+  P.seed = seed;
+  P.counter = counter;
+  P.input_ids = d_input_ids;
+  P.token_type_ids = d_token_type_ids;
+  P.attention_mask = d_attention_mask;
+  P.labels = d_labels;
+  P.next_sentence_labels = d_next_sentence_labels;
+  int rc;
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
+  HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
+  HIP_TRY(launch_collate_rows(P, mode, c->n_cu, st));
+  uint32_t* h_err = (uint32_t*)&c->h_tot[7];
+  HIP_TRY(hipMemcpyAsync(h_err, P.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (*h_err) return collate_rows_error(*h_err, seq_len);
   return 0;
 }

@@ -57,12 +57,43 @@ struct MaskParams {
   uint64_t seed, counter;
 };
 
-// error codes in CollateParams::err (low 4 bits)
-enum : uint32_t { CERR_LONG = 1, CERR_POS_RANGE = 2, CERR_NPY = 3, CERR_NLAB = 4 };
+// lddl_collate_rows_seq_len / lddl_collate_rows: batch row r is row
+// g = rows[r] (rows NULL: row0 + r) of a pack result's spans over the dense ids
+struct CollateRowsParams {
+  const uint16_t* ids;    // the dense ids (16 entries of padding behind the last)
+  const int64_t* src0;    // [n_total] lddl_row_spans' outputs
+  const int64_t* src1;
+  const uint16_t* len0;
+  const uint16_t* len1;
+  const uint8_t* flags;
+  const int64_t* rows;    // [n_rows] or NULL
+  int64_t row0, n_rows, n_total;
+  const int64_t* mlm_off;     // COLLATE_STATIC: lddl_masked_lm_spans' outputs
+  const uint16_t* mlm_pos;
+  const uint16_t* mlm_label;
+  const uint16_t* mlm_token;
+  int32_t cls, sep, mask_id, n_random;
+  int32_t seq_len;
+  int64_t ignore_index;
+  double mlm_probability;
+  uint64_t seed, counter;
+  int64_t* input_ids;        // [n_rows, seq_len]
+  int64_t* token_type_ids;
+  int64_t* attention_mask;
+  int64_t* labels;
+  int64_t* next_sentence_labels;  // [n_rows]
+  int32_t* max_len;          // [1] (seq-len pass)
+  uint32_t* err;             // [1] as CollateParams::err
+};
+
+// error codes in CollateParams::err / CollateRowsParams::err (low 4 bits)
+enum : uint32_t { CERR_LONG = 1, CERR_POS_RANGE = 2, CERR_NPY = 3, CERR_NLAB = 4, CERR_ROW_INDEX = 5, CERR_NO_SEP = 6 };
 
 constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
 
 uint32_t collate_hash_host(const uint8_t* p, int n);
+hipError_t launch_collate_rows_len(const CollateRowsParams& P, int n_cu, hipStream_t s);
+hipError_t launch_collate_rows(const CollateRowsParams& P, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);

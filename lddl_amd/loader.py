@@ -155,6 +155,60 @@ class BertCollate:
     rn = np.asarray(table.column('is_random_next').to_numpy(zero_copy_only=False), dtype=np.uint8)
     return self._run(cols, rn, static)
 
+  def collate_rows(self, res, rows=None, row0=0, n_rows=None, mode=None):
+    """A batch straight from a pack result on the GPU (lddl_collate_rows):
+    the rows ``rows`` (an int64 CUDA tensor, or anything torch.as_tensor
+    takes; any order, repeats allowed) of ``res``, a PackResult with spans
+    (``Packer.pack(..., spans=True)``) -- or rows [row0, row0 + n_rows)
+    (default: all from row0 on).  Returns the dict of ``__call__`` (mode 0:
+    'special_tokens_mask' in place of 'labels', as ``to_encoded_inputs``) and
+    advances the batch counter as ``__call__`` does.  mode defaults to static
+    when the result carries static masks, else dynamic.  Nothing is staged on
+    the host: the kernel reads the packer's own buffers.  ``res`` must have
+    been packed with this collate's vocab, on its device; a CodeBERT result
+    (rows without the [SEP] after segment 0) is refused by the C call."""
+    if not res.spans:
+      raise ValueError('collate_rows needs a PackResult with spans (Packer.pack(..., spans=True))')
+    if mode is None:
+      mode = MODE_STATIC if res.mlm_token is not None else MODE_DYNAMIC
+    if mode not in (MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC):
+      raise ValueError('mode %r not in 0..2' % (mode,))
+    if mode == MODE_STATIC and res.mlm_token is None:
+      raise ValueError('static mode needs a result packed with masking=True')
+    if rows is not None:
+      rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device).contiguous().view(-1)
+      n, row0 = rows.numel(), 0
+    else:
+      row0 = int(row0)
+      n = res.n_pairs - row0 if n_rows is None else int(n_rows)
+    if n <= 0:
+      raise ValueError('empty batch')  # max() of an empty sequence in bert.py:94-95
+    L = _lib.lib()
+    st = _stream()
+    P = ctypes.c_void_p
+    p = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+    seq = ctypes.c_int64()
+    rc = L.lddl_collate_rows_seq_len(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
+                                     self.sequence_length_alignment, ctypes.byref(seq), st)
+    if rc == -7:
+      raise IndexError(L.lddl_last_error().decode())
+    _lib.check(rc)
+    S = int(seq.value)
+    out = torch.empty((4, n, S), dtype=torch.int64, device=self.device)
+    nsl = torch.empty(n, dtype=torch.int64, device=self.device)
+    mlm = (res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token) if mode == MODE_STATIC else (None,) * 4
+    rc = L.lddl_collate_rows(self.tok.handle, p(res.ids), p(res.src0), p(res.src1), p(res.len0), p(res.len1),
+                             p(res.flags), p(rows), row0, n, res.n_pairs, p(mlm[0]), p(mlm[1]), p(mlm[2]), p(mlm[3]),
+                             S, mode, self.ignore_index, self.mlm_probability, self.seed, self.counter,
+                             p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nsl), st)
+    if mode != MODE_SPECIAL_MASK:
+      self.counter += 1
+    if rc == -7:
+      raise IndexError(L.lddl_last_error().decode())
+    _lib.check(rc)
+    return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2], 'next_sentence_labels': nsl,
+            'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
+
   # ---- the reference's two steps, separately ----------------------------------
   def to_encoded_inputs(self, batch):
     """bert.py:69-153 as is: with static masks 'labels', else
@@ -201,3 +255,63 @@ class BertCollate:
                                            S, self.mlm_probability, self.ignore_index, self.seed, counter,
                                            _stream()))
     return inputs, labels
+
+
+def plan_row_batches(bins, batch_size, seed=12345, epoch=0, drop_last=False, n_rows=None):
+  """The batches of one epoch over binned rows, on the host: a list of int64
+  index arrays.  bins: the bin id of every row (None: n_rows rows of one bin).
+  Each bin's rows are permuted and cut into batches of batch_size (a bin's
+  last short batch is kept unless drop_last; an empty bin gives none), then
+  the batch list is permuted; every draw comes from one generator seeded by
+  (seed, epoch).  A batch never mixes bins, so its padded length tracks its
+  bin (the point of binning, lddl/torch/bert.py's per-bin data loaders)."""
+  batch_size = int(batch_size)
+  if batch_size < 1:
+    raise ValueError('batch_size %d < 1' % batch_size)
+  if bins is None:
+    bins = np.zeros(int(n_rows), dtype=np.int64)
+  bins = np.asarray(bins).reshape(-1)
+  rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed) & ((1 << 64) - 1), int(epoch)])))
+  order = np.argsort(bins, kind='stable').astype(np.int64)
+  counts = np.bincount(bins.astype(np.int64)) if bins.size else np.zeros(0, np.int64)
+  batches, lo = [], 0
+  for c in counts:  # ascending bin id; empty bins add nothing
+    rows = order[lo:lo + c][rng.permutation(int(c))]
+    lo += c
+    full = (int(c) // batch_size) * batch_size
+    batches.extend(rows[i:i + batch_size] for i in range(0, full, batch_size))
+    if full < c and not drop_last:
+      batches.append(rows[full:])
+  return [batches[i] for i in rng.permutation(len(batches))]
+
+
+class RowBatches:
+  """Iterable of int64 row-index tensors (on the result's device), one per
+  batch, over a PackResult: ``for idx in RowBatches(res, 256): batch =
+  collate.collate_rows(res, idx)``.  The plan is plan_row_batches over a host
+  copy of res.bins (an unbinned result is one bin); set_epoch(e) reshuffles."""
+
+  def __init__(self, res, batch_size, seed=12345, epoch=0, drop_last=False):
+    self.batch_size, self.seed, self.epoch, self.drop_last = int(batch_size), seed, epoch, drop_last
+    self.device = res.len0.device
+    self.n_rows = res.n_pairs
+    self.bins = res.bins[:res.n_pairs].cpu().numpy() if res.nbins > 1 else None
+
+  def set_epoch(self, epoch):
+    self.epoch = epoch
+
+  def plan(self):
+    return plan_row_batches(self.bins, self.batch_size, self.seed, self.epoch, self.drop_last, n_rows=self.n_rows)
+
+  def __len__(self):
+    return len(self.plan())
+
+  def __iter__(self):
+    plan = self.plan()
+    if not plan:
+      return
+    flat = torch.from_numpy(np.concatenate(plan)).to(self.device)  # the indices only: one copy per epoch
+    lo = 0
+    for b in plan:
+      yield flat[lo:lo + len(b)]
+      lo += len(b)

@@ -1076,6 +1076,7 @@ extern "C" int lddl_render_strings(lddl_ctx* c, const uint16_t* d_tokens, const 
   int rc;
   if ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)n_rows, &R.lens))) return rc;
   if ((rc = ws_get(c, CW_SHARED_BSUM, (size_t)scan_blocks(n_rows) + 1, &bsum))) return rc;
+  if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   HIP_TRY(launch_render_len(R, c->n_cu, st));
   HIP_TRY(launch_scan_ntok(R.lens, n_rows, d_out_off, bsum, st));
   HIP_TRY(hipMemcpyAsync(&c->h_tot[6], d_out_off + n_rows, 8, hipMemcpyDeviceToHost, st));
@@ -1161,6 +1162,7 @@ extern "C" int lddl_render_masked(lddl_ctx* c, const uint16_t* d_ids, const int6
   int rc;
   if ((rc = ws_get(c, CW_SHARED_ROWS, (size_t)n_rows, &R.lens))) return rc;
   if ((rc = ws_get(c, CW_SHARED_BSUM, (size_t)scan_blocks(n_rows) + 1, &bsum))) return rc;
+  if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
   HIP_TRY(launch_render_len(R, c->n_cu, st));
   HIP_TRY(launch_scan_ntok(R.lens, n_rows, d_out_off, bsum, st));
   HIP_TRY(hipMemcpyAsync(&c->h_tot[6], d_out_off + n_rows, 8, hipMemcpyDeviceToHost, st));

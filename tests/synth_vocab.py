@@ -4,8 +4,9 @@ pack_wave.hip that bert_vocab.txt and codebert_52000_vocab.txt never reach
 (DESIGN.md section 4 lists them).  Everything is a deterministic function of
 the vocabulary's name.  The small ones are also committed under
 tests/golden/vocabs/ (tests/test_vocab_oracle.py checks they still match);
-the large ones are generated at test time.  Plain helper module: no fixtures,
-no pytest settings.
+the large ones are generated at test time, and so is 'widths' (the render
+tests' vocabulary: no tokenizer golden, not one of NAMES).  Plain helper
+module: no fixtures, no pytest settings.
 
   vocab_bytes(name)   the vocab.txt bytes
   vocab_path(name)    a file holding them (golden/vocabs/ or a temp dir)
@@ -249,7 +250,29 @@ def _sized(V):
   return v, words
 
 
+# ---- widths: an entry of every byte length the rendering tables hold ------------
+# (tests/test_render_gpu.py; vinfo keeps a length in 8 bits and a pool offset,
+# the pool is 4-aligned: every length 0..255 and every offset residue occurs)
+WIDTHS_EMPTY = len(SPECIALS)  # the id of the empty line
+
+
+def _widths():
+  v = SPECIALS + ['']
+  v += [_pat(n, 700 + n) for n in range(1, 256)]  # id 5 + n: n ASCII bytes, no period (a shifted offset shows)
+  v += ['##' + _pat(253, 999)]                    # 255 bytes with its '##'
+  v += ['ab' + CYR[0], 'abc' + HIRA[0], 'a' + GOTH[0]]  # ending in a 2-, 3- and 4-byte character
+  v += [_pat(251, 998) + GOTH[1], HIRA[1] + CYR[1] * 124 + HIRA[2]]  # 255 bytes ending in 4; 254 of 3- and 2-byte ones
+  return v, []
+
+
+def widths_id(nbytes):
+  """the id of widths' ASCII entry of nbytes bytes (0: the empty line)"""
+  return WIDTHS_EMPTY + nbytes
+
+
 def _build(name):
+  if name == 'widths':
+    return _widths()
   if name == 'collide':
     return _collide()
   if name in ('long_a', 'long_b'):

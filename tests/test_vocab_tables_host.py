@@ -162,3 +162,14 @@ def test_longest_accepted_entries(host_tables, tmp_path, case):
     assert f[k] == '0', (k, f)
   if n == 7:
     assert len(entries[5]) == 255 and entries[6] == b'b'
+
+
+def test_widths_vocab_renders_every_length(host_tables):
+  """the render tests' vocabulary (tests/test_render_gpu.py): the rendering tables give back an entry of
+  every length 0..255, the empty line included"""
+  f, entries = host_tables(sv.vocab_path('widths'), '--dump')
+  assert f['rc'] == '0' and f['render_bad'] == '0' and int(f['n']) == sv.vocab_size('widths') == len(entries)
+  lines = sv.vocab_bytes('widths').split(b'\n')[:-1]
+  assert [entries[i] for i in range(len(lines))] == lines
+  assert [len(entries[sv.widths_id(k)]) for k in range(256)] == list(range(256))
+  assert (f['maxb0'], f['maxb1']) == ('255', '253')

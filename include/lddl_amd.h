@@ -360,6 +360,57 @@ int lddl_collate_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src
                       uint64_t counter, int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_attention_mask,
                       int64_t *d_labels, int64_t *d_next_sentence_labels, void *stream);
 
+/* ---- padding-free collate straight from a pack result ---------------------
+ * The same batch for a model with variable-length attention: the rows
+ * concatenated into one token stream, batch row r at tokens [cu_seqlens[r],
+ * cu_seqlens[r + 1]), no pad columns and no attention_mask.  Rows are picked
+ * as in lddl_collate_rows: batch row r is row g = d_rows[r] (d_rows NULL:
+ * g = row0 + r) of a pack result's spans, 0 <= g < n_total; any order,
+ * repeats allowed; for users who pack and train in one job.  This output has
+ * no counterpart in the reference (lddl/torch/bert.py:69-153 pads every
+ * batch): it is defined as lddl_collate_rows at the same seed and counter
+ * with every column j >= n_r = len0[g] + len1[g] + 3 of row r dropped, bit
+ * for bit in all three modes (the dynamic draw is keyed by (seed, counter, r,
+ * j), not by seq_len).
+ *
+ * lddl_collate_rows_cu_seqlens: d_cu_seqlens[0] = 0, d_cu_seqlens[r + 1] =
+ * d_cu_seqlens[r] + n_r as int32 [n_rows + 1] on the device (what varlen
+ * attention kernels take); *out_total = the batch's tokens T =
+ * cu_seqlens[n_rows], *out_max_seqlen = max over its rows of n_r.
+ * Synchronises the stream.  A row index outside [0, n_total) is LDDL_EINDEX
+ * (checked before any load through it), n_rows == 0 LDDL_EINVAL, a batch of
+ * 2^31 tokens or more LDDL_ECAPACITY (summed in 64 bits; d_cu_seqlens is then
+ * left unwritten). */
+int lddl_collate_rows_cu_seqlens(lddl_ctx *ctx, const uint16_t *d_len0, const uint16_t *d_len1,
+                                 const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                 int32_t *d_cu_seqlens, int64_t *out_total, int64_t *out_max_seqlen, void *stream);
+
+/* Fill the int64 outputs: for t = cu_seqlens[r] + j, 0 <= j < n_r,
+ * input_ids[t], token_type_ids[t] and d_labels[t] are column j of row r of
+ * lddl_collate_rows (d_labels by mode 0 / 1 / 2 as there; the static arrays
+ * required in mode 1, NULL otherwise), position_ids[t] = j, and
+ * next_sentence_labels[r] = flags[g] & 1.  The four token outputs are
+ * [total] (total = the T of lddl_collate_rows_cu_seqlens, or more),
+ * next_sentence_labels [n_rows]; d_cu_seqlens is that call's output and is
+ * checked, not trusted.  The caller's sequence_length_alignment has no
+ * meaning here.  Synchronises the stream.
+ * Errors, first one wins, none faults, the row is left unwritten and no row
+ * stores outside its own tokens: LDDL_EINVAL (a row with cu_seqlens[r] < 0,
+ * cu_seqlens[r + 1] - cu_seqlens[r] != n_r or cu_seqlens[r] + n_r > total; a
+ * row whose flags lack bit 1, a CodeBERT row; mode not in 0..2), LDDL_EINDEX
+ * (a row index outside [0, n_total), checked before any load through it; a
+ * static position >= n_r -- stricter than lddl_collate_rows' >= seq_len,
+ * since a position in [n_r, seq_len) would land in the next row here),
+ * LDDL_ECAPACITY (a row longer than 2048 tokens, total >= 2^31). */
+int lddl_collate_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                               const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                               const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                               const int64_t *d_mlm_off, const uint16_t *d_mlm_pos, const uint16_t *d_mlm_label,
+                               const uint16_t *d_mlm_token, const int32_t *d_cu_seqlens, int64_t total, int32_t mode,
+                               int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
+                               int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
+                               int64_t *d_labels, int64_t *d_next_sentence_labels, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

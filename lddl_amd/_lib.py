@@ -67,6 +67,10 @@ SIGNATURES = {
                                           ctypes.POINTER(c_int64), c_void_p]),
     'lddl_collate_rows': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 4 +
                           [c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] + [c_void_p] * 6),
+    'lddl_collate_rows_cu_seqlens': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64,
+                                             c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p]),
+    'lddl_collate_rows_unpadded': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 5 +
+                                   [c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] + [c_void_p] * 6),
 }
 
 _lib = None

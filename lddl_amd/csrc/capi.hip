@@ -98,9 +98,11 @@ enum CtxWs {
   CW_FB_COUNT,     // tokenize: ranges listed in the segment
   CW_ENT,          // tokenize: the segment's entry / staging buffer
   CW_SHARED_ROWS,  // tokenize: rec, the record slots; lddl_render_strings / _npy / _masked: lens, bytes per row
-  CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan
-  CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len
-  CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len]: the error word
+  CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan;
+                   // lddl_collate_rows_cu_seqlens: chunk sums of its scan
+  CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len;
+                   // lddl_collate_rows_cu_seqlens: total, max_len
+  CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded]: the error word
   CW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP]; written by lddl_tokenize (lddl_set_special_flags),
                    // read by the next masked lddl_pack_bert over the same buffers (pack_common)
   CW_PCS,          // tokenize: WordPiece pieces 4.. per record slot
@@ -1369,6 +1371,8 @@ static int collate_rows_error(uint32_t e, int64_t seq_len) {
     case CERR_POS_RANGE:
       return set_err(LDDL_EINDEX, "batch row %llu: masked position out of range for seq_len %lld", row,
                      (long long)seq_len);
+    case CERR_CU_SEQLENS:
+      return set_err(LDDL_EINVAL, "batch row %llu: cu_seqlens do not hold the row's tokens within [0, total)", row);
     default:
       return set_err(LDDL_EINVAL, "batch row %llu has no [SEP] after its first segment (a CodeBERT row)", row);
   }
@@ -1467,5 +1471,126 @@ extern "C" int lddl_collate_rows(lddl_ctx* c, const uint16_t* d_ids, const int64
   HIP_TRY(hipMemcpyAsync(h_err, P.err, 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (*h_err) return collate_rows_error(*h_err, seq_len);
+  return 0;
+}
+
+// ------------------------------------- padding-free collate from a pack result --
+// collate_rows_error with the unpadded calls' wording where seq_len has no meaning
+static int collate_unpadded_error(uint32_t e) {
+  const unsigned long long row = e >> 4;
+  switch (e & 15u) {
+    case CERR_LONG: return set_err(LDDL_ECAPACITY, "batch row %llu longer than %d tokens", row, COLLATE_MAX_LEN);
+    case CERR_POS_RANGE: return set_err(LDDL_EINDEX, "batch row %llu: masked position beyond the row's tokens", row);
+    default: return collate_rows_error(e, 0);
+  }
+}
+
+extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                            const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                            int32_t* d_cu_seqlens, int64_t* out_total, int64_t* out_max_seqlen,
+                                            void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0 || !out_total || !out_max_seqlen)
+    return set_err(LDDL_EINVAL, "bad n_rows / n_total / out");
+  if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
+  if (!d_len0 || !d_len1 || !d_cu_seqlens) return set_err(LDDL_EINVAL, "null pointer");
+  // every row has its three special tokens at least
+  if (n_rows > INT32_MAX / 3) return set_err(LDDL_ECAPACITY, "%lld rows hold 2^31 tokens or more", (long long)n_rows);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateUnpaddedParams P{};
+  P.R.len0 = d_len0;
+  P.R.len1 = d_len1;
+  P.R.rows = d_rows;
+  P.R.row0 = row0;
+  P.R.n_rows = n_rows;
+  P.R.n_total = n_total;
+  P.cu_seqlens = d_cu_seqlens;
+  P.n_chunks = collate_cu_chunks(n_rows);
+  int rc;
+  int64_t* meta;  // total, then max_len in the low half of meta[1]
+  if ((rc = ws_get(c, CW_SHARED_META, 2, &meta)) || (rc = ws_get(c, CW_SHARED_BSUM, (size_t)P.n_chunks, &P.chunk_sum)) ||
+      (rc = ws_get(c, CW_COLLATE_ERR, 1, &P.R.err)))
+    return rc;
+  P.total_out = meta;
+  P.R.max_len = (int32_t*)(meta + 1);
+  if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
+  HIP_TRY(hipMemsetAsync(meta, 0, 16, st));
+  HIP_TRY(hipMemsetAsync(P.R.err, 0, 4, st));
+  HIP_TRY(launch_collate_cu_seqlens(P, st));
+  HIP_TRY(hipMemcpyAsync(&c->h_tot[5], meta, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(&c->h_tot[7], P.R.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint32_t e = *(const uint32_t*)&c->h_tot[7];
+  if (e) return collate_unpadded_error(e);
+  if (c->h_tot[5] > INT32_MAX)
+    return set_err(LDDL_ECAPACITY, "the batch holds %lld tokens: cu_seqlens are int32", (long long)c->h_tot[5]);
+  *out_total = c->h_tot[5];
+  *out_max_seqlen = *(const int32_t*)&c->h_tot[6];
+  return 0;
+}
+
+extern "C" int lddl_collate_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                          const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                          const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                          int64_t n_total, const int64_t* d_mlm_off, const uint16_t* d_mlm_pos,
+                                          const uint16_t* d_mlm_label, const uint16_t* d_mlm_token,
+                                          const int32_t* d_cu_seqlens, int64_t total, int32_t mode,
+                                          int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
+                                          int64_t* d_input_ids, int64_t* d_token_type_ids, int64_t* d_position_ids,
+                                          int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0) return set_err(LDDL_EINVAL, "negative n_rows / n_total");
+  if (mode < COLLATE_SPECIAL_MASK || mode > COLLATE_DYNAMIC) return set_err(LDDL_EINVAL, "mode %d not in 0..2", mode);
+  if (total < 0) return set_err(LDDL_EINVAL, "negative total");
+  if (total > INT32_MAX) return set_err(LDDL_ECAPACITY, "total %lld: cu_seqlens are int32", (long long)total);
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  if (n_rows > 0 && (!d_ids || !d_src0 || !d_src1 || !d_len0 || !d_len1 || !d_flags || !d_cu_seqlens || !d_input_ids ||
+                     !d_token_type_ids || !d_position_ids || !d_labels || !d_next_sentence_labels))
+    return set_err(LDDL_EINVAL, "null pointer");
+  if (mode == COLLATE_STATIC && n_rows > 0 && (!d_mlm_off || !d_mlm_pos || !d_mlm_label || !d_mlm_token))
+    return set_err(LDDL_EINVAL, "static masking needs lddl_masked_lm_spans' arrays");
+  if (n_rows == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateUnpaddedParams P{};
+  P.R.ids = d_ids;
+  P.R.src0 = d_src0;
+  P.R.src1 = d_src1;
+  P.R.len0 = d_len0;
+  P.R.len1 = d_len1;
+  P.R.flags = d_flags;
+  P.R.rows = d_rows;
+  P.R.row0 = row0;
+  P.R.n_rows = n_rows;
+  P.R.n_total = n_total;
+  P.R.mlm_off = d_mlm_off;
+  P.R.mlm_pos = d_mlm_pos;
+  P.R.mlm_label = d_mlm_label;
+  P.R.mlm_token = d_mlm_token;
+  P.R.cls = (int32_t)c->special[2];
+  P.R.sep = (int32_t)c->special[3];
+  P.R.mask_id = (int32_t)c->special[4];
+  P.R.n_random = c->vocab_size;
+  P.R.ignore_index = ignore_index;
+  P.R.mlm_probability = mlm_probability;
+  P.R.seed = seed;
+  P.R.counter = counter;
+  P.R.input_ids = d_input_ids;
+  P.R.token_type_ids = d_token_type_ids;
+  P.R.labels = d_labels;
+  P.R.next_sentence_labels = d_next_sentence_labels;
+  P.cu_seqlens = const_cast<int32_t*>(d_cu_seqlens);  // read only by the fill pass
+  P.position_ids = d_position_ids;
+  P.total = total;
+  int rc;
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.R.err))) return rc;
+  if (!c->h_tot) HIP_TRY(hipHostMalloc((void**)&c->h_tot, 8 * sizeof(int64_t)));
+  HIP_TRY(hipMemsetAsync(P.R.err, 0, 4, st));
+  HIP_TRY(launch_collate_unpadded(P, mode, c->n_cu, st));
+  uint32_t* h_err = (uint32_t*)&c->h_tot[7];
+  HIP_TRY(hipMemcpyAsync(h_err, P.R.err, 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (*h_err) return collate_unpadded_error(*h_err);
   return 0;
 }

@@ -86,14 +86,39 @@ struct CollateRowsParams {
   uint32_t* err;             // [1] as CollateParams::err
 };
 
+// lddl_collate_rows_cu_seqlens / lddl_collate_rows_unpadded (collate_unpadded.hip):
+// the same batch without its pad columns, row r at tokens [cu_seqlens[r],
+// cu_seqlens[r + 1]).  R.seq_len and R.attention_mask are unused; R.max_len is
+// the offsets pass's max over the rows of len0 + len1 + 3.
+struct CollateUnpaddedParams {
+  CollateRowsParams R;     // input_ids, token_type_ids, labels: [total]
+  int32_t* cu_seqlens;     // [n_rows + 1]: written by the offsets pass, checked by the fill pass
+  int64_t* position_ids;   // [total]
+  int64_t total;           // fill pass: the capacity of the token outputs
+  uint32_t* chunk_sum;     // offsets pass: [n_chunks] tokens of each chunk of rows
+  int64_t* total_out;      // offsets pass: [1] tokens of the batch
+  int64_t n_chunks;        // collate_cu_chunks(n_rows)
+};
+
 // error codes in CollateParams::err / CollateRowsParams::err (low 4 bits)
-enum : uint32_t { CERR_LONG = 1, CERR_POS_RANGE = 2, CERR_NPY = 3, CERR_NLAB = 4, CERR_ROW_INDEX = 5, CERR_NO_SEP = 6 };
+enum : uint32_t {
+  CERR_LONG = 1,
+  CERR_POS_RANGE = 2,
+  CERR_NPY = 3,
+  CERR_NLAB = 4,
+  CERR_ROW_INDEX = 5,
+  CERR_NO_SEP = 6,
+  CERR_CU_SEQLENS = 7  // collate_unpadded.hip: a row's cu_seqlens are not its [c, c + n) within the outputs
+};
 
 constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
 
 uint32_t collate_hash_host(const uint8_t* p, int n);
 hipError_t launch_collate_rows_len(const CollateRowsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_rows(const CollateRowsParams& P, int32_t mode, int n_cu, hipStream_t s);
+int64_t collate_cu_chunks(int64_t n_rows);
+hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, hipStream_t s);
+hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);

@@ -1,5 +1,6 @@
 // Device helpers shared by the collate kernels (collate.hip: rows from parquet
-// strings; collate_rows.hip: rows from a pack result's spans): the error word
+// strings; collate_rows.hip / collate_unpadded.hip: rows from a pack result's
+// spans, padded and padding-free): the error word
 // and the counter-based draws of `_mask_tokens`.
 #pragma once
 #include <hip/hip_runtime.h>

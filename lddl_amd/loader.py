@@ -209,6 +209,63 @@ class BertCollate:
     return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2], 'next_sentence_labels': nsl,
             'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
 
+  def collate_rows_unpadded(self, res, rows=None, row0=0, n_rows=None, mode=None):
+    """The batch of ``collate_rows`` without its padding
+    (lddl_collate_rows_cu_seqlens + lddl_collate_rows_unpadded), for a model
+    with variable-length attention: the rows concatenated into one stream of
+    T tokens, row r at [cu_seqlens[r], cu_seqlens[r + 1]).  Arguments and mode
+    defaults as ``collate_rows``.  Returns input_ids, token_type_ids,
+    position_ids and labels (mode 0: special_tokens_mask) as int64 [T],
+    next_sentence_labels as int64 [n], cu_seqlens as int32 [n + 1] and
+    max_seqlen as a Python int; there is no attention_mask.  The reference
+    has no such output: it is ``collate_rows`` at the same seed and counter
+    with the pad columns dropped, bit for bit.  The batch counter advances as
+    in ``collate_rows``.  ``sequence_length_alignment`` has no effect here:
+    nothing is padded."""
+    if not res.spans:
+      raise ValueError('collate_rows_unpadded needs a PackResult with spans (Packer.pack(..., spans=True))')
+    if mode is None:
+      mode = MODE_STATIC if res.mlm_token is not None else MODE_DYNAMIC
+    if mode not in (MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC):
+      raise ValueError('mode %r not in 0..2' % (mode,))
+    if mode == MODE_STATIC and res.mlm_token is None:
+      raise ValueError('static mode needs a result packed with masking=True')
+    if rows is not None:
+      rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device).contiguous().view(-1)
+      n, row0 = rows.numel(), 0
+    else:
+      row0 = int(row0)
+      n = res.n_pairs - row0 if n_rows is None else int(n_rows)
+    if n <= 0:
+      raise ValueError('empty batch')
+    L = _lib.lib()
+    st = _stream()
+    P = ctypes.c_void_p
+    p = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+    cu = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+    total, longest = ctypes.c_int64(), ctypes.c_int64()
+    rc = L.lddl_collate_rows_cu_seqlens(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
+                                        p(cu), ctypes.byref(total), ctypes.byref(longest), st)
+    if rc == -7:
+      raise IndexError(L.lddl_last_error().decode())
+    _lib.check(rc)
+    T = int(total.value)
+    out = torch.empty((4, T), dtype=torch.int64, device=self.device)
+    nsl = torch.empty(n, dtype=torch.int64, device=self.device)
+    mlm = (res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token) if mode == MODE_STATIC else (None,) * 4
+    rc = L.lddl_collate_rows_unpadded(self.tok.handle, p(res.ids), p(res.src0), p(res.src1), p(res.len0),
+                                      p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs, p(mlm[0]), p(mlm[1]),
+                                      p(mlm[2]), p(mlm[3]), p(cu), T, mode, self.ignore_index, self.mlm_probability,
+                                      self.seed, self.counter, p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nsl), st)
+    if mode != MODE_SPECIAL_MASK:
+      self.counter += 1
+    if rc == -7:
+      raise IndexError(L.lddl_last_error().decode())
+    _lib.check(rc)
+    return {'input_ids': out[0], 'token_type_ids': out[1], 'position_ids': out[2], 'next_sentence_labels': nsl,
+            'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3], 'cu_seqlens': cu,
+            'max_seqlen': int(longest.value)}
+
   # ---- the reference's two steps, separately ----------------------------------
   def to_encoded_inputs(self, batch):
     """bert.py:69-153 as is: with static masks 'labels', else
@@ -285,22 +342,77 @@ def plan_row_batches(bins, batch_size, seed=12345, epoch=0, drop_last=False, n_r
   return [batches[i] for i in rng.permutation(len(batches))]
 
 
+def plan_token_batches(lengths, max_tokens, max_rows=None, seed=12345, epoch=0):
+  """The batches of one epoch for a padding-free collate, on the host: a list
+  of int64 index arrays.  lengths: the tokens of every row (len0 + len1 + 3).
+  All rows are permuted by a generator seeded by (seed, epoch), built as in
+  plan_row_batches, and the permutation is cut in order: a batch is closed
+  when the next row would take it over max_tokens tokens or max_rows rows.
+  With no padding a bin means nothing, and what a step holds constant is its
+  tokens.  Every row appears once and no batch is empty; a row longer than
+  max_tokens raises ValueError."""
+  max_tokens = int(max_tokens)
+  if max_tokens < 1:
+    raise ValueError('max_tokens %d < 1' % max_tokens)
+  if max_rows is not None:
+    max_rows = int(max_rows)
+    if max_rows < 1:
+      raise ValueError('max_rows %d < 1' % max_rows)
+  lengths = np.asarray(lengths).reshape(-1).astype(np.int64)
+  if lengths.size and int(lengths.max()) > max_tokens:
+    raise ValueError('row %d has %d tokens, max_tokens %d' % (int(lengths.argmax()), int(lengths.max()), max_tokens))
+  rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed) & ((1 << 64) - 1), int(epoch)])))
+  order = rng.permutation(lengths.size).astype(np.int64)
+  # token t of the permuted stream starts its row at csum; a batch that starts at row i ends in front of the first
+  # row whose end passes csum[i] + max_tokens
+  csum = np.concatenate([np.zeros(1, np.int64), np.cumsum(lengths[order])])
+  batches, i, n = [], 0, int(lengths.size)
+  while i < n:
+    j = int(np.searchsorted(csum, csum[i] + max_tokens, side='right')) - 1
+    if max_rows is not None:
+      j = min(j, i + max_rows)
+    batches.append(order[i:j])
+    i = j
+  return batches
+
+
 class RowBatches:
   """Iterable of int64 row-index tensors (on the result's device), one per
   batch, over a PackResult: ``for idx in RowBatches(res, 256): batch =
   collate.collate_rows(res, idx)``.  The plan is plan_row_batches over a host
-  copy of res.bins (an unbinned result is one bin); set_epoch(e) reshuffles."""
+  copy of res.bins (an unbinned result is one bin); set_epoch(e) reshuffles.
 
-  def __init__(self, res, batch_size, seed=12345, epoch=0, drop_last=False):
-    self.batch_size, self.seed, self.epoch, self.drop_last = int(batch_size), seed, epoch, drop_last
+  With ``max_tokens`` in place of ``batch_size`` (exactly one of the two) the
+  batches are for ``collate_rows_unpadded``: plan_token_batches over a host
+  copy of len0 + len1 + 3, at most max_tokens tokens (and max_rows rows) each;
+  bins are ignored and drop_last has no meaning."""
+
+  def __init__(self, res, batch_size=None, seed=12345, epoch=0, drop_last=False, max_tokens=None, max_rows=None):
+    if (batch_size is None) == (max_tokens is None):
+      raise ValueError('give exactly one of batch_size and max_tokens')
+    if max_rows is not None and max_tokens is None:
+      raise ValueError('max_rows goes with max_tokens')
+    self.seed, self.epoch, self.drop_last = seed, epoch, drop_last
+    self.batch_size = int(batch_size) if batch_size is not None else None
+    self.max_tokens = int(max_tokens) if max_tokens is not None else None
+    self.max_rows = max_rows
     self.device = res.len0.device
     self.n_rows = res.n_pairs
-    self.bins = res.bins[:res.n_pairs].cpu().numpy() if res.nbins > 1 else None
+    self.bins = self.lengths = None
+    if self.max_tokens is not None:
+      n = res.n_pairs
+      l0 = res.len0[:n].cpu().numpy().view(np.uint16).astype(np.int64)  # int16 views of uint16
+      l1 = res.len1[:n].cpu().numpy().view(np.uint16).astype(np.int64)
+      self.lengths = l0 + l1 + 3
+    elif res.nbins > 1:
+      self.bins = res.bins[:res.n_pairs].cpu().numpy()
 
   def set_epoch(self, epoch):
     self.epoch = epoch
 
   def plan(self):
+    if self.max_tokens is not None:
+      return plan_token_batches(self.lengths, self.max_tokens, self.max_rows, self.seed, self.epoch)
     return plan_row_batches(self.bins, self.batch_size, self.seed, self.epoch, self.drop_last, n_rows=self.n_rows)
 
   def __len__(self):

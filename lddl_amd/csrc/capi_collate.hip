@@ -1,0 +1,356 @@
+// C-ABI, host side of the training-time collate (kernels: collate.hip,
+// collate_rows.hip, collate_unpadded.hip).
+#include "capi_ctx.h"
+
+static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
+  if (!c->d_ctab) {
+    const size_t n = c->vocab.size();
+    uint32_t sz = 1024;
+    while (sz < 4 * n) sz <<= 1;
+    std::vector<uint2> tab(sz, make_uint2(0u, 0xFFFFFFFFu));
+    for (size_t i = 0; i < n; ++i) {
+      const std::string& w = c->vocab[i];
+      const uint32_t h = collate_hash_host((const uint8_t*)w.data(), (int)w.size());
+      for (uint32_t s = h & (sz - 1);; s = (s + 1) & (sz - 1)) {
+        if (tab[s].y == 0xFFFFFFFFu) {
+          tab[s] = make_uint2(h, (uint32_t)i);
+          break;
+        }
+        if (tab[s].x == h && c->vocab[tab[s].y] == w) {  // duplicate line: last id wins
+          tab[s].y = (uint32_t)i;
+          break;
+        }
+      }
+    }
+    int rc;
+    if ((rc = upload(&c->d_ctab, tab.data(), tab.size() * sizeof(uint2)))) return rc;
+    c->ctab_mask = sz - 1;
+  }
+  V->slots = c->d_ctab;
+  V->mask = c->ctab_mask;
+  V->vinfo = c->d_rinfo;
+  V->vpool = c->d_rpool;
+  V->unk = (int32_t)c->special[1];
+  V->cls = (int32_t)c->special[2];
+  V->sep = (int32_t)c->special[3];
+  V->mask_id = (int32_t)c->special[4];
+  V->n_random = c->vocab_size;
+  return 0;
+}
+
+extern "C" int lddl_collate_seq_len(lddl_ctx* c, const uint8_t* d_a, const int64_t* d_a_off, const uint8_t* d_b,
+                                    const int64_t* d_b_off, int64_t n_rows, int32_t seq_align, int64_t* out_seq_len,
+                                    void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || seq_align < 1 || !out_seq_len) return set_err(LDDL_EINVAL, "bad n_rows / seq_align / out");
+  if (n_rows > 0 && (!d_a || !d_a_off || !d_b || !d_b_off)) return set_err(LDDL_EINVAL, "null column pointer");
+  if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateParams P{};
+  int rc;
+  if ((rc = collate_vocab(c, &P.V))) return rc;
+  P.a = d_a;
+  P.a_off = d_a_off;
+  P.b = d_b;
+  P.b_off = d_b_off;
+  P.n_rows = n_rows;
+  if ((rc = ws_get(c, CW_SHARED_META, 1, &P.max_len))) return rc;
+  HIP_TRY(hipMemsetAsync(P.max_len, 0, 4, st));
+  HIP_TRY(launch_collate_len(P, c->n_cu, st));
+  HIP_TRY(fetch_word(c, HW_MAX_LEN, P.max_len, 4, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t m = *(const int32_t*)&c->h_tot[HW_MAX_LEN];
+  *out_seq_len = ((m - 1) / seq_align + 1) * seq_align;
+  return 0;
+}
+
+extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t* d_a_off, const uint8_t* d_b,
+                                 const int64_t* d_b_off, const uint8_t* d_is_random_next, const uint8_t* d_pos,
+                                 const int64_t* d_pos_off, const uint8_t* d_lab, const int64_t* d_lab_off,
+                                 int64_t n_rows, int64_t seq_len, int32_t mode, int64_t ignore_index,
+                                 double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                 int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
+                                 int64_t* d_next_sentence_labels, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0) return set_err(LDDL_EINVAL, "negative n_rows");
+  if (mode < COLLATE_SPECIAL_MASK || mode > COLLATE_DYNAMIC) return set_err(LDDL_EINVAL, "mode %d not in 0..2", mode);
+  if (seq_len < 3 || seq_len > COLLATE_MAX_LEN)
+    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [3, %d]", (long long)seq_len, COLLATE_MAX_LEN);
+  if (ignore_index < INT32_MIN || ignore_index > INT32_MAX) return set_err(LDDL_EINVAL, "ignore_index out of int32");
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  if (n_rows > 0 && (!d_a || !d_a_off || !d_b || !d_b_off || !d_is_random_next || !d_input_ids ||
+                     !d_token_type_ids || !d_attention_mask || !d_labels || !d_next_sentence_labels))
+    return set_err(LDDL_EINVAL, "null pointer");
+  if (mode == COLLATE_STATIC && n_rows > 0 && (!d_pos || !d_pos_off || !d_lab || !d_lab_off))
+    return set_err(LDDL_EINVAL, "static masking needs positions and labels");
+  if (n_rows == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateParams P{};
+  int rc;
+  if ((rc = collate_vocab(c, &P.V))) return rc;
+  P.a = d_a;
+  P.a_off = d_a_off;
+  P.b = d_b;
+  P.b_off = d_b_off;
+  P.is_random_next = d_is_random_next;
+  P.pos = d_pos;
+  P.pos_off = d_pos_off;
+  P.lab = d_lab;
+  P.lab_off = d_lab_off;
+  P.n_rows = n_rows;
+  P.seq_len = (int32_t)seq_len;
+  P.mode = mode;
+  P.ignore_index = ignore_index;
+  P.mlm_probability = mlm_probability;
+  P.seed = seed;
+  P.counter = counter;
+  P.input_ids = d_input_ids;
+  P.token_type_ids = d_token_type_ids;
+  P.attention_mask = d_attention_mask;
+  P.labels = d_labels;
+  P.next_sentence_labels = d_next_sentence_labels;
+  uint32_t e;
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
+  HIP_TRY(launch_collate_fill(P, c->n_cu, st));
+  if ((rc = read_err(c, P.err, st, &e))) return rc;
+  if (e) {
+    const unsigned long long row = e >> 4;
+    switch (e & 15u) {
+      case CERR_LONG: return set_err(LDDL_ECAPACITY, "row %llu longer than seq_len %lld", row, (long long)seq_len);
+      case CERR_POS_RANGE:
+        return set_err(LDDL_EINDEX, "row %llu: masked_lm_positions index out of range for seq_len %lld", row,
+                       (long long)seq_len);
+      case CERR_NPY: return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions is not np.save bytes", row);
+      default:
+        return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions and masked_lm_labels differ in length", row);
+    }
+  }
+  return 0;
+}
+
+extern "C" int lddl_mask_tokens(lddl_ctx* c, int64_t* d_inputs, const int64_t* d_special_tokens_mask,
+                                int64_t* d_labels, int64_t n_rows, int64_t seq_len, double mlm_probability,
+                                int64_t ignore_index, uint64_t seed, uint64_t counter, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || seq_len < 0 || seq_len >= (1 << 20)) return set_err(LDDL_EINVAL, "bad shape");
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  if (n_rows * seq_len > 0 && (!d_inputs || !d_special_tokens_mask || !d_labels))
+    return set_err(LDDL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  MaskParams M{};
+  M.inputs = d_inputs;
+  M.special = d_special_tokens_mask;
+  M.labels = d_labels;
+  M.n_rows = n_rows;
+  M.seq_len = (int32_t)seq_len;
+  M.mask_id = (int32_t)c->special[4];
+  M.n_random = c->vocab_size;
+  M.ignore_index = ignore_index;
+  M.mlm_probability = mlm_probability;
+  M.seed = seed;
+  M.counter = counter;
+  HIP_TRY(launch_mask_tokens(M, c->n_cu, (hipStream_t)stream));
+  return 0;
+}
+
+// ---------------------------------------------- collate from a pack result --
+static int collate_rows_error(uint32_t e, int64_t seq_len) {
+  const unsigned long long row = e >> 4;
+  switch (e & 15u) {
+    case CERR_ROW_INDEX: return set_err(LDDL_EINDEX, "batch row %llu: row index out of range", row);
+    case CERR_LONG: return set_err(LDDL_ECAPACITY, "batch row %llu longer than seq_len %lld", row, (long long)seq_len);
+    case CERR_POS_RANGE:
+      return set_err(LDDL_EINDEX, "batch row %llu: masked position out of range for seq_len %lld", row,
+                     (long long)seq_len);
+    case CERR_CU_SEQLENS:
+      return set_err(LDDL_EINVAL, "batch row %llu: cu_seqlens do not hold the row's tokens within [0, total)", row);
+    default:
+      return set_err(LDDL_EINVAL, "batch row %llu has no [SEP] after its first segment (a CodeBERT row)", row);
+  }
+}
+
+// collate_rows_error with the unpadded calls' wording where seq_len has no meaning
+static int collate_unpadded_error(uint32_t e) {
+  const unsigned long long row = e >> 4;
+  switch (e & 15u) {
+    case CERR_LONG: return set_err(LDDL_ECAPACITY, "batch row %llu longer than %d tokens", row, COLLATE_MAX_LEN);
+    case CERR_POS_RANGE: return set_err(LDDL_EINDEX, "batch row %llu: masked position beyond the row's tokens", row);
+    default: return collate_rows_error(e, 0);
+  }
+}
+
+// the row selection that every lddl_collate_rows* call takes
+static void collate_rows_index(CollateRowsParams* P, const uint16_t* d_len0, const uint16_t* d_len1, const int64_t* d_rows,
+                               int64_t row0, int64_t n_rows, int64_t n_total) {
+  P->len0 = d_len0;
+  P->len1 = d_len1;
+  P->rows = d_rows;
+  P->row0 = row0;
+  P->n_rows = n_rows;
+  P->n_total = n_total;
+}
+
+extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                         const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                         int32_t seq_align, int64_t* out_seq_len, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0 || seq_align < 1 || !out_seq_len)
+    return set_err(LDDL_EINVAL, "bad n_rows / n_total / seq_align / out");
+  if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
+  if (!d_len0 || !d_len1) return set_err(LDDL_EINVAL, "null pointer");
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateRowsParams P{};
+  collate_rows_index(&P, d_len0, d_len1, d_rows, row0, n_rows, n_total);
+  int rc;
+  uint32_t e;
+  if ((rc = ws_get(c, CW_SHARED_META, 1, &P.max_len)) || (rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  HIP_TRY(hipMemsetAsync(P.max_len, 0, 4, st));
+  HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
+  HIP_TRY(launch_collate_rows_len(P, c->n_cu, st));
+  HIP_TRY(fetch_word(c, HW_MAX_LEN, P.max_len, 4, st));
+  if ((rc = read_err(c, P.err, st, &e))) return rc;
+  if (e) return collate_rows_error(e, 0);
+  const int64_t m = *(const int32_t*)&c->h_tot[HW_MAX_LEN];
+  *out_seq_len = ((m - 1) / seq_align + 1) * seq_align;
+  return 0;
+}
+
+// lddl_collate_rows (unpadded 0: seq_len, d_attention_mask) and lddl_collate_rows_unpadded (1: d_cu_seqlens,
+// total, d_position_ids) validate their arguments and fill CollateRowsParams here, once.  The range check
+// between the mode and the probability checks, the launch and the wording of the device's errors are each
+// call's own; the arguments of the other call arrive as 0 / NULL and are passed on as that.
+static int collate_rows_common(lddl_ctx* c, int unpadded, const uint16_t* d_ids, const int64_t* d_src0,
+                               const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                               const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                               int64_t n_total, const int64_t* d_mlm_off, const uint16_t* d_mlm_pos,
+                               const uint16_t* d_mlm_label, const uint16_t* d_mlm_token, int64_t seq_len,
+                               const int32_t* d_cu_seqlens, int64_t total, int32_t mode, int64_t ignore_index,
+                               double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                               int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_position_ids,
+                               int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0) return set_err(LDDL_EINVAL, "negative n_rows / n_total");
+  if (mode < COLLATE_SPECIAL_MASK || mode > COLLATE_DYNAMIC) return set_err(LDDL_EINVAL, "mode %d not in 0..2", mode);
+  if (!unpadded && (seq_len < 3 || seq_len > COLLATE_MAX_LEN))
+    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [3, %d]", (long long)seq_len, COLLATE_MAX_LEN);
+  if (unpadded && total < 0) return set_err(LDDL_EINVAL, "negative total");
+  if (unpadded && total > INT32_MAX) return set_err(LDDL_ECAPACITY, "total %lld: cu_seqlens are int32", (long long)total);
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  if (n_rows > 0 && (!d_ids || !d_src0 || !d_src1 || !d_len0 || !d_len1 || !d_flags || !d_input_ids || !d_token_type_ids ||
+                     (unpadded ? !d_cu_seqlens || !d_position_ids : !d_attention_mask) || !d_labels || !d_next_sentence_labels))
+    return set_err(LDDL_EINVAL, "null pointer");
+  if (mode == COLLATE_STATIC && n_rows > 0 && (!d_mlm_off || !d_mlm_pos || !d_mlm_label || !d_mlm_token))
+    return set_err(LDDL_EINVAL, "static masking needs lddl_masked_lm_spans' arrays");
+  if (n_rows == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateUnpaddedParams U{};
+  CollateRowsParams& P = U.R;
+  collate_rows_index(&P, d_len0, d_len1, d_rows, row0, n_rows, n_total);
+  P.ids = d_ids;
+  P.src0 = d_src0;
+  P.src1 = d_src1;
+  P.flags = d_flags;
+  P.mlm_off = d_mlm_off;
+  P.mlm_pos = d_mlm_pos;
+  P.mlm_label = d_mlm_label;
+  P.mlm_token = d_mlm_token;
+  P.cls = (int32_t)c->special[2];
+  P.sep = (int32_t)c->special[3];
+  P.mask_id = (int32_t)c->special[4];
+  P.n_random = c->vocab_size;
+  P.seq_len = (int32_t)seq_len;
+  P.ignore_index = ignore_index;
+  P.mlm_probability = mlm_probability;
+  P.seed = seed;
+  P.counter = counter;
+  P.input_ids = d_input_ids;
+  P.token_type_ids = d_token_type_ids;
+  P.attention_mask = d_attention_mask;
+  P.labels = d_labels;
+  P.next_sentence_labels = d_next_sentence_labels;
+  U.cu_seqlens = const_cast<int32_t*>(d_cu_seqlens);  // read only by the fill pass
+  U.position_ids = d_position_ids;
+  U.total = total;
+  int rc;
+  uint32_t e;
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
+  HIP_TRY(unpadded ? launch_collate_unpadded(U, mode, c->n_cu, st) : launch_collate_rows(P, mode, c->n_cu, st));
+  if ((rc = read_err(c, P.err, st, &e))) return rc;
+  if (e) return unpadded ? collate_unpadded_error(e) : collate_rows_error(e, seq_len);
+  return 0;
+}
+
+extern "C" int lddl_collate_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                 const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                 const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                 const int64_t* d_mlm_off, const uint16_t* d_mlm_pos, const uint16_t* d_mlm_label,
+                                 const uint16_t* d_mlm_token, int64_t seq_len, int32_t mode, int64_t ignore_index,
+                                 double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                 int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
+                                 int64_t* d_next_sentence_labels, void* stream) {
+  return collate_rows_common(c, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
+                             d_mlm_pos, d_mlm_label, d_mlm_token, seq_len, nullptr, 0, mode, ignore_index, mlm_probability,
+                             seed, counter, d_input_ids, d_token_type_ids, d_attention_mask, nullptr, d_labels,
+                             d_next_sentence_labels, stream);
+}
+
+// ------------------------------------- padding-free collate from a pack result --
+extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                            const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                            int32_t* d_cu_seqlens, int64_t* out_total, int64_t* out_max_seqlen,
+                                            void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0 || !out_total || !out_max_seqlen)
+    return set_err(LDDL_EINVAL, "bad n_rows / n_total / out");
+  if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
+  if (!d_len0 || !d_len1 || !d_cu_seqlens) return set_err(LDDL_EINVAL, "null pointer");
+  // every row has its three special tokens at least
+  if (n_rows > INT32_MAX / 3) return set_err(LDDL_ECAPACITY, "%lld rows hold 2^31 tokens or more", (long long)n_rows);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  CollateUnpaddedParams P{};
+  collate_rows_index(&P.R, d_len0, d_len1, d_rows, row0, n_rows, n_total);
+  P.cu_seqlens = d_cu_seqlens;
+  P.n_chunks = collate_cu_chunks(n_rows);
+  int rc;
+  uint32_t e;
+  int64_t* meta;  // total, then max_len in the low half of meta[1]: the layout of HW_CU_TOTAL, HW_MAX_LEN
+  if ((rc = ws_get(c, CW_SHARED_META, 2, &meta)) || (rc = ws_get(c, CW_SHARED_BSUM, (size_t)P.n_chunks, &P.chunk_sum)) ||
+      (rc = ws_get(c, CW_COLLATE_ERR, 1, &P.R.err)))
+    return rc;
+  P.total_out = meta;
+  P.R.max_len = (int32_t*)(meta + 1);
+  HIP_TRY(hipMemsetAsync(meta, 0, 16, st));
+  HIP_TRY(hipMemsetAsync(P.R.err, 0, 4, st));
+  HIP_TRY(launch_collate_cu_seqlens(P, st));
+  HIP_TRY(fetch_word(c, HW_CU_TOTAL, meta, 16, st));
+  if ((rc = read_err(c, P.R.err, st, &e))) return rc;
+  if (e) return collate_unpadded_error(e);
+  const int64_t total = c->h_tot[HW_CU_TOTAL];
+  if (total > INT32_MAX)
+    return set_err(LDDL_ECAPACITY, "the batch holds %lld tokens: cu_seqlens are int32", (long long)total);
+  *out_total = total;
+  *out_max_seqlen = *(const int32_t*)&c->h_tot[HW_MAX_LEN];
+  return 0;
+}
+
+extern "C" int lddl_collate_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                          const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                          const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                          int64_t n_total, const int64_t* d_mlm_off, const uint16_t* d_mlm_pos,
+                                          const uint16_t* d_mlm_label, const uint16_t* d_mlm_token,
+                                          const int32_t* d_cu_seqlens, int64_t total, int32_t mode,
+                                          int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
+                                          int64_t* d_input_ids, int64_t* d_token_type_ids, int64_t* d_position_ids,
+                                          int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream) {
+  return collate_rows_common(c, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
+                             d_mlm_pos, d_mlm_label, d_mlm_token, 0, d_cu_seqlens, total, mode, ignore_index,
+                             mlm_probability, seed, counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids,
+                             d_labels, d_next_sentence_labels, stream);
+}

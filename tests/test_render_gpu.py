@@ -1,5 +1,5 @@
 """lddl_render_strings (its four segment modes), lddl_render_masked and
-lddl_row_docs (lddl_amd/csrc/render.hip, capi.hip) on hand-made row tables.
+lddl_row_docs (lddl_amd/csrc/render.hip, capi_render.hip, capi_pack.hip) on hand-made row tables.
 
 Every parquet string column goes through render_len_kernel (bytes per row),
 the offset scan and render_bytes_kernel; the other tests reach them only
@@ -420,7 +420,8 @@ def test_render_masked_two_phase_and_guard_bytes(gpu, seg):
 # ---- g. a new ctx ---------------------------------------------------------------------------
 def test_render_is_the_first_call_of_a_new_ctx(gpu):
   """lddl_render_strings / lddl_render_masked read the byte total back through the ctx's pinned words,
-  which they allocate themselves when no pack, bin or collate call has yet (capi.hip)"""
+  which lddl_create allocates: no pack, bin or collate call need have run (capi.hip, capi_render.hip;
+  the other readers of those words: test_capi_first_call_gpu.py)"""
   from lddl_amd import pipeline, writer
   t = masked_table()
   path = sv.vocab_path('widths')

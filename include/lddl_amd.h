@@ -411,6 +411,70 @@ int lddl_collate_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64
                                int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
                                int64_t *d_labels, int64_t *d_next_sentence_labels, void *stream);
 
+/* ---- a row table from the shards on disk ----------------------------------
+ * The bridge from parquet shards to lddl_collate_rows[_unpadded]: the string
+ * columns of a shard (A, B, is_random_next and, with static masking,
+ * masked_lm_positions / masked_lm_labels; the layout lddl_collate_bert takes)
+ * become what lddl_row_spans + lddl_masked_lm_spans leave behind for a pack
+ * result, once per shard instead of once per batch per epoch.  This is the
+ * decode-and-lookup half of the reference's loader: lddl/torch/bert.py:42-60
+ * `_decode_record_batch`, :83-89 and :109-124 (`split()` and
+ * `convert_tokens_to_ids`) and lddl/utils.py `deserialize_np_array`; the
+ * padding half (bert.py:90-149) stays in lddl_collate_rows[_unpadded].
+ * d_pos .. d_lab_off are all four NULL without static masking, and then so
+ * are the d_*mlm_* arrays; anything in between is LDDL_EINVAL.
+ *
+ * lddl_rows_from_strings_len: per row r, d_out_len0[r] = a = tokens of
+ * A.split(), d_out_len1[r] = b = tokens of B.split(); with n_r = a + b + 3 and
+ * k_r = the row's positions, the exclusive scans (64-bit) d_out_src0[r] =
+ * sum of a + b over the rows before r, d_out_src1[r] = d_out_src0[r] + a,
+ * d_out_tok_off (optional, [n_rows + 1]) of n_r and d_out_mlm_off (static
+ * masking, [n_rows + 1]) of k_r.  out_totals = {ids = sum of a + b, masked
+ * entries = sum of k_r, row tokens = sum of n_r}.  Synchronises the stream
+ * once.
+ * Errors, first one wins, none faults: LDDL_ECAPACITY (a segment of more than
+ * 65535 tokens: len0 / len1 are 16 bits, so no row exceeds 2 * 65535 + 3
+ * tokens; more positions than that), LDDL_EFORMAT (positions that are not
+ * np.save bytes of a uint16 array, a label count different from the position
+ * count), LDDL_EINDEX (a position >= n_r: lddl_collate_bert refuses only
+ * >= seq_len, which depends on the batch; a table has no batch and takes the
+ * stricter rule of lddl_collate_rows_unpadded), LDDL_EINVAL (n_rows <= 0, a
+ * NULL required pointer, static outputs without static inputs or the reverse,
+ * a vocabulary of more than 65536 entries: an id would not fit 16 bits). */
+int lddl_rows_from_strings_len(lddl_ctx *ctx, const uint8_t *d_a, const int64_t *d_a_off, const uint8_t *d_b,
+                               const int64_t *d_b_off, const uint8_t *d_pos, const int64_t *d_pos_off,
+                               const uint8_t *d_lab, const int64_t *d_lab_off, int64_t n_rows, uint16_t *d_out_len0,
+                               uint16_t *d_out_len1, int64_t *d_out_src0, int64_t *d_out_src1, int64_t *d_out_tok_off,
+                               int64_t *d_out_mlm_off, int64_t out_totals[3], void *stream);
+
+/* Fill the table (same seam: bert.py:83-89, :109-124): d_out_ids[src0[r] ..
+ * + a) = the ids of A's tokens, d_out_ids[src1[r] .. + b) = of B's ([UNK] for
+ * a miss), d_out_flags[r] = (is_random_next[r] ? 1 : 0) | 2, and with static
+ * masking for j < k_r at e = mlm_off[r] + j: d_out_mlm_pos[e] = the j-th
+ * position, d_out_mlm_label[e] = the id of the j-th label token,
+ * d_out_mlm_token[e] = what the row shows there ([CLS], [SEP] or the A / B
+ * id: A and B of a masked shard hold the masked tokens already).  d_len0 ..
+ * d_mlm_off are lddl_rows_from_strings_len's outputs and are checked, not
+ * trusted: every row's tokens are counted again.  ids_cap / mlm_cap: the
+ * entries of d_out_ids / of each d_out_mlm_* array that may be written, at
+ * least that call's totals.  The caller keeps d_out_ids 16-B aligned with 16
+ * zeroed entries behind the total (not counted in ids_cap, never written
+ * here): lddl_collate_rows expects that padding.  Synchronises the stream.
+ * Errors as lddl_rows_from_strings_len, and: LDDL_ECAPACITY (the table ends
+ * beyond ids_cap or mlm_cap: nothing is written), LDDL_EINVAL (a row whose
+ * len0 / len1 / src0 / src1 / mlm_off are not what its strings give, or whose
+ * span leaves the capacities).  A refused row is left unwritten and a row
+ * stores only inside [src0[r], src0[r] + a + b) and [mlm_off[r], mlm_off[r +
+ * 1]) as given, within the capacities; a src0 altered to another value inside
+ * the capacity is not detected (a row cannot know the running sum). */
+int lddl_rows_from_strings(lddl_ctx *ctx, const uint8_t *d_a, const int64_t *d_a_off, const uint8_t *d_b,
+                           const int64_t *d_b_off, const uint8_t *d_pos, const int64_t *d_pos_off, const uint8_t *d_lab,
+                           const int64_t *d_lab_off, const uint8_t *d_is_random_next, int64_t n_rows,
+                           const uint16_t *d_len0, const uint16_t *d_len1, const int64_t *d_src0, const int64_t *d_src1,
+                           const int64_t *d_mlm_off, uint16_t *d_out_ids, int64_t ids_cap, uint8_t *d_out_flags,
+                           uint16_t *d_out_mlm_pos, uint16_t *d_out_mlm_label, uint16_t *d_out_mlm_token,
+                           int64_t mlm_cap, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

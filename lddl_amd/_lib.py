@@ -71,6 +71,10 @@ SIGNATURES = {
                                              c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p]),
     'lddl_collate_rows_unpadded': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 5 +
                                    [c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] + [c_void_p] * 6),
+    'lddl_rows_from_strings_len': (c_int, [c_void_p] * 9 + [c_int64] + [c_void_p] * 6 +
+                                   [ctypes.POINTER(c_int64), c_void_p]),
+    'lddl_rows_from_strings': (c_int, [c_void_p] * 10 + [c_int64] + [c_void_p] * 6 + [c_int64] + [c_void_p] * 4 +
+                               [c_int64, c_void_p]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 // C-ABI, host side of the training-time collate (kernels: collate.hip,
-// collate_rows.hip, collate_unpadded.hip).
+// collate_rows.hip, collate_unpadded.hip, rows_from_strings.hip).
 #include "capi_ctx.h"
 
 static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
@@ -353,4 +353,120 @@ extern "C" int lddl_collate_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, co
                              d_mlm_pos, d_mlm_label, d_mlm_token, 0, d_cu_seqlens, total, mode, ignore_index,
                              mlm_probability, seed, counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids,
                              d_labels, d_next_sentence_labels, stream);
+}
+
+// ------------------------------------------- a row table from a shard's strings --
+static int rows_from_strings_error(uint32_t e) {
+  const unsigned long long row = e >> 4;
+  switch (e & 15u) {
+    case CERR_LONG: return set_err(LDDL_ECAPACITY, "row %llu: a segment of more than 65535 tokens", row);
+    case CERR_NMASK: return set_err(LDDL_ECAPACITY, "row %llu: more masked_lm_positions than a row has tokens", row);
+    case CERR_TABLE_CAP: return set_err(LDDL_ECAPACITY, "the table's ids or masked entries exceed ids_cap / mlm_cap");
+    case CERR_POS_RANGE: return set_err(LDDL_EINDEX, "row %llu: masked_lm_positions index beyond the row's tokens", row);
+    case CERR_NPY: return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions is not np.save bytes", row);
+    case CERR_NLAB:
+      return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions and masked_lm_labels differ in length", row);
+    default:
+      return set_err(LDDL_EINVAL, "row %llu: len0 / len1 / src0 / src1 / mlm_off are not what its strings give", row);
+  }
+}
+
+// lddl_rows_from_strings_len (fill 0: the outputs d_len0 .. d_mlm_off, d_tok_off, out_totals) and
+// lddl_rows_from_strings (fill 1: the same arrays as inputs, d_is_random_next and the table) validate their
+// arguments and fill RowsFromStringsParams here, once; the arguments of the other call arrive as 0 / NULL.
+static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, const int64_t* d_a_off,
+                                    const uint8_t* d_b, const int64_t* d_b_off, const uint8_t* d_pos,
+                                    const int64_t* d_pos_off, const uint8_t* d_lab, const int64_t* d_lab_off,
+                                    const uint8_t* d_is_random_next, int64_t n_rows, uint16_t* d_len0, uint16_t* d_len1,
+                                    int64_t* d_src0, int64_t* d_src1, int64_t* d_tok_off, int64_t* d_mlm_off,
+                                    int64_t* out_totals, uint16_t* d_ids, int64_t ids_cap, uint8_t* d_flags,
+                                    uint16_t* d_mlm_pos, uint16_t* d_mlm_label, uint16_t* d_mlm_token, int64_t mlm_cap,
+                                    void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows <= 0) return set_err(LDDL_EINVAL, "n_rows %lld: a table has one row at least", (long long)n_rows);
+  if (!d_a || !d_a_off || !d_b || !d_b_off) return set_err(LDDL_EINVAL, "null column pointer");
+  if (!d_len0 || !d_len1 || !d_src0 || !d_src1 || (fill ? !d_is_random_next || !d_ids || !d_flags : !out_totals))
+    return set_err(LDDL_EINVAL, "null pointer");
+  const int n_static = (d_pos != nullptr) + (d_pos_off != nullptr) + (d_lab != nullptr) + (d_lab_off != nullptr);
+  if (n_static != 0 && n_static != 4)
+    return set_err(LDDL_EINVAL, "static masking needs positions and labels, all four pointers or none");
+  const int n_out = (d_mlm_off != nullptr) + (fill ? (d_mlm_pos != nullptr) + (d_mlm_label != nullptr) + (d_mlm_token != nullptr) : 0);
+  if (n_out != (n_static ? (fill ? 4 : 1) : 0))
+    return set_err(LDDL_EINVAL, n_static ? "static inputs without the static outputs" : "static outputs without static inputs");
+  if (fill && (ids_cap < 0 || mlm_cap < 0)) return set_err(LDDL_EINVAL, "negative capacity");
+  if (c->vocab_size > 65536) return set_err(LDDL_EINVAL, "a vocabulary of %d entries: an id would not fit 16 bits", c->vocab_size);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  RowsFromStringsParams P{};
+  int rc;
+  if (fill && (rc = collate_vocab(c, &P.V))) return rc;
+  P.a = d_a;
+  P.a_off = d_a_off;
+  P.b = d_b;
+  P.b_off = d_b_off;
+  P.pos = d_pos;
+  P.pos_off = d_pos_off;
+  P.lab = d_lab;
+  P.lab_off = d_lab_off;
+  P.is_random_next = d_is_random_next;
+  P.n_rows = n_rows;
+  P.len0 = d_len0;
+  P.len1 = d_len1;
+  P.src0 = d_src0;
+  P.src1 = d_src1;
+  P.tok_off = d_tok_off;
+  P.mlm_off = d_mlm_off;
+  P.ids = d_ids;
+  P.ids_cap = ids_cap;
+  P.flags = d_flags;
+  P.mlm_pos = d_mlm_pos;
+  P.mlm_label = d_mlm_label;
+  P.mlm_token = d_mlm_token;
+  P.mlm_cap = mlm_cap;
+  uint32_t e;
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
+  if (fill) {
+    HIP_TRY(launch_rows_from_strings(P, c->n_cu, st));
+    if ((rc = read_err(c, P.err, st, &e))) return rc;
+    return e ? rows_from_strings_error(e) : 0;
+  }
+  P.n_chunks = rows_from_strings_chunks(n_rows);
+  if ((rc = ws_get(c, CW_SHARED_META, 3, &P.totals)) || (rc = ws_get(c, CW_SHARED_BSUM, (size_t)P.n_chunks, &P.chunk_sum)))
+    return rc;
+  HIP_TRY(hipMemsetAsync(P.chunk_sum, 0, (size_t)P.n_chunks * sizeof(*P.chunk_sum), st));
+  HIP_TRY(launch_rows_from_strings_len(P, c->n_cu, st));
+  HIP_TRY(fetch_word(c, HW_NTOK, P.totals, 24, st));  // ids, row tokens, masked: HW_NTOK, HW_PACK_ERR, HW_NMASK
+  if ((rc = read_err(c, P.err, st, &e))) return rc;
+  if (e) return rows_from_strings_error(e);
+  out_totals[0] = c->h_tot[HW_NTOK];
+  out_totals[1] = c->h_tot[HW_NMASK];
+  out_totals[2] = c->h_tot[HW_PACK_ERR];
+  return 0;
+}
+
+extern "C" int lddl_rows_from_strings_len(lddl_ctx* c, const uint8_t* d_a, const int64_t* d_a_off, const uint8_t* d_b,
+                                          const int64_t* d_b_off, const uint8_t* d_pos, const int64_t* d_pos_off,
+                                          const uint8_t* d_lab, const int64_t* d_lab_off, int64_t n_rows,
+                                          uint16_t* d_out_len0, uint16_t* d_out_len1, int64_t* d_out_src0,
+                                          int64_t* d_out_src1, int64_t* d_out_tok_off, int64_t* d_out_mlm_off,
+                                          int64_t out_totals[3], void* stream) {
+  return rows_from_strings_common(c, 0, d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off, nullptr, n_rows,
+                                  d_out_len0, d_out_len1, d_out_src0, d_out_src1, d_out_tok_off, d_out_mlm_off, out_totals,
+                                  nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int lddl_rows_from_strings(lddl_ctx* c, const uint8_t* d_a, const int64_t* d_a_off, const uint8_t* d_b,
+                                      const int64_t* d_b_off, const uint8_t* d_pos, const int64_t* d_pos_off,
+                                      const uint8_t* d_lab, const int64_t* d_lab_off, const uint8_t* d_is_random_next,
+                                      int64_t n_rows, const uint16_t* d_len0, const uint16_t* d_len1,
+                                      const int64_t* d_src0, const int64_t* d_src1, const int64_t* d_mlm_off,
+                                      uint16_t* d_out_ids, int64_t ids_cap, uint8_t* d_out_flags, uint16_t* d_out_mlm_pos,
+                                      uint16_t* d_out_mlm_label, uint16_t* d_out_mlm_token, int64_t mlm_cap, void* stream) {
+  // read only by the fill pass
+  return rows_from_strings_common(c, 1, d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off, d_is_random_next,
+                                  n_rows, const_cast<uint16_t*>(d_len0), const_cast<uint16_t*>(d_len1),
+                                  const_cast<int64_t*>(d_src0), const_cast<int64_t*>(d_src1), nullptr,
+                                  const_cast<int64_t*>(d_mlm_off), nullptr, d_out_ids, ids_cap, d_out_flags, d_out_mlm_pos,
+                                  d_out_mlm_label, d_out_mlm_token, mlm_cap, stream);
 }

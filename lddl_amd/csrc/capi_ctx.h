@@ -91,10 +91,11 @@ enum CtxWs {
   CW_ENT,          // tokenize: the segment's entry / staging buffer
   CW_SHARED_ROWS,  // tokenize: rec, the record slots; lddl_render_strings / _npy / _masked: lens, bytes per row
   CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan;
-                   // lddl_collate_rows_cu_seqlens: chunk sums of its scan
+                   // lddl_collate_rows_cu_seqlens / lddl_rows_from_strings_len: chunk sums of their scans
   CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len;
-                   // lddl_collate_rows_cu_seqlens: total, max_len
-  CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded]: the error word
+                   // lddl_collate_rows_cu_seqlens: total, max_len; lddl_rows_from_strings_len: its three totals
+  CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded] / lddl_rows_from_strings[_len]:
+                   // the error word
   CW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP]; written by lddl_tokenize (lddl_set_special_flags),
                    // read by the next masked lddl_pack_bert over the same buffers (pack_common)
   CW_PCS,          // tokenize: WordPiece pieces 4.. per record slot
@@ -112,18 +113,21 @@ enum CtxWs {
 // on purpose: the eight fill one cache line.  A value narrower than 8 bytes fills the word's low bytes.
 enum HostWord {
   HW_NPAIRS,        // lddl_pack_bert / _codebert: the rows of the pack
-  HW_NTOK,          // lddl_pack_bert / _codebert: their tokens
-  HW_PACK_ERR,      // lddl_pack_bert / _codebert: the partitions' PACK_E* flags or-ed (int32)
-  HW_NMASK,         // lddl_pack_bert (masking): the masked entries
+  HW_NTOK,          // lddl_pack_bert / _codebert: their tokens; lddl_rows_from_strings_len: the table's ids
+  HW_PACK_ERR,      // lddl_pack_bert / _codebert: the partitions' PACK_E* flags or-ed (int32);
+                    // lddl_rows_from_strings_len: the table's row tokens (one 24-byte copy with its neighbours)
+  HW_NMASK,         // lddl_pack_bert (masking): the masked entries; lddl_rows_from_strings_len: the same of the table
   HW_MARENA_USED,   // lddl_pack_bert (masking): the arena entries the bump allocator handed out
   HW_NDENSE,        // lddl_pack_bert / _codebert: the tokenizer's dense ids
   HW_CU_TOTAL = HW_NDENSE,  // the same word; lddl_collate_rows_cu_seqlens: the batch's tokens (one 16-byte copy with HW_MAX_LEN)
   HW_MAX_LEN,       // lddl_collate_seq_len / lddl_collate_rows_seq_len / lddl_collate_rows_cu_seqlens: the longest row (int32)
   HW_RENDER_BYTES = HW_MAX_LEN,  // the same word; lddl_render_strings / _npy / _masked: the bytes of the rendered column
-  HW_ERR,           // lddl_bin, lddl_render_npy, lddl_collate_bert, lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded]: the error word
+  HW_ERR,           // lddl_bin, lddl_render_npy, lddl_collate_bert, lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded],
+                    // lddl_rows_from_strings[_len]: the error word
   HW_COUNT
 };
 static_assert(HW_MAX_LEN == HW_CU_TOTAL + 1, "lddl_collate_rows_cu_seqlens reads total and max_len with one copy");
+static_assert(HW_PACK_ERR == HW_NTOK + 1 && HW_NMASK == HW_NTOK + 2, "lddl_rows_from_strings_len reads its three totals with one copy");
 
 // The result of one lddl_pack_* call, owned by the caller (lddl_pack_new):
 // the pair records, their shuffled / binned order, the per-partition counts

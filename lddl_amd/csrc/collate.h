@@ -100,6 +100,41 @@ struct CollateUnpaddedParams {
   int64_t n_chunks;        // collate_cu_chunks(n_rows)
 };
 
+// lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
+// the string columns of a shard into the row table that lddl_row_spans +
+// lddl_masked_lm_spans leave behind.  pos .. lab_off are NULL without static
+// masking, and so are mlm_off .. mlm_token then.
+struct RowsFromStringsParams {
+  CollateVocab V;         // fill pass only
+  const uint8_t* a;
+  const int64_t* a_off;   // [n_rows + 1]
+  const uint8_t* b;
+  const int64_t* b_off;
+  const uint8_t* pos;     // np.save bytes per row
+  const int64_t* pos_off;
+  const uint8_t* lab;     // space-joined label tokens
+  const int64_t* lab_off;
+  const uint8_t* is_random_next;  // [n_rows] (bool bytes; fill pass)
+  int64_t n_rows;
+  uint16_t* len0;         // [n_rows] written by the length pass, checked by the fill pass
+  uint16_t* len1;
+  int64_t* src0;          // [n_rows] written by the scan, checked by the fill pass
+  int64_t* src1;
+  int64_t* tok_off;       // [n_rows + 1] or NULL (length pass)
+  int64_t* mlm_off;       // [n_rows + 1]: the length kernel leaves k_r in [r + 1], the scan sums in place
+  uint16_t* ids;          // fill pass: [ids_cap]
+  int64_t ids_cap;
+  uint8_t* flags;         // [n_rows]
+  uint16_t* mlm_pos;      // [mlm_cap]
+  uint16_t* mlm_label;
+  uint16_t* mlm_token;
+  int64_t mlm_cap;
+  unsigned long long* chunk_sum;  // length pass: [n_chunks] ids (low half) | masked entries (high half) of each chunk of rows
+  int64_t* totals;        // length pass: [3] ids, row tokens and masked entries of the table
+  int64_t n_chunks;       // rows_from_strings_chunks(n_rows)
+  uint32_t* err;          // [1] as CollateParams::err
+};
+
 // error codes in CollateParams::err / CollateRowsParams::err (low 4 bits)
 enum : uint32_t {
   CERR_LONG = 1,
@@ -108,7 +143,10 @@ enum : uint32_t {
   CERR_NLAB = 4,
   CERR_ROW_INDEX = 5,
   CERR_NO_SEP = 6,
-  CERR_CU_SEQLENS = 7  // collate_unpadded.hip: a row's cu_seqlens are not its [c, c + n) within the outputs
+  CERR_CU_SEQLENS = 7,  // collate_unpadded.hip: a row's cu_seqlens are not its [c, c + n) within the outputs
+  CERR_ROW_COUNTS = 8,  // rows_from_strings.hip: a row's len / src / mlm_off are not what its strings give
+  CERR_TABLE_CAP = 9,   // rows_from_strings.hip: the table ends beyond ids_cap / mlm_cap
+  CERR_NMASK = 10       // rows_from_strings.hip: more masked positions than the longest row has tokens
 };
 
 constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
@@ -121,6 +159,9 @@ hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, hipStream_t
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
+int64_t rows_from_strings_chunks(int64_t n_rows);
+hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
+hipError_t launch_rows_from_strings(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);
 
 }  // namespace lddl

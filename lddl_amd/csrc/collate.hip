@@ -33,111 +33,10 @@
 
 namespace lddl {
 
-static constexpr uint32_t kEmpty = 0xFFFFFFFFu;
-
-__host__ __device__ __forceinline__ uint32_t chash_step(uint32_t h, uint32_t b) {
-  h ^= b;
-  return h * 0x01000193u;  // FNV-1a 32
-}
-
-__host__ __device__ __forceinline__ uint32_t chash_final(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x7feb352du;
-  h ^= h >> 15;
-  h *= 0x846ca68bu;
-  h ^= h >> 16;
-  return h;
-}
-
 uint32_t collate_hash_host(const uint8_t* p, int n) {
   uint32_t h = 0x811c9dc5u;
   for (int i = 0; i < n; ++i) h = chash_step(h, p[i]);
   return chash_final(h);
-}
-
-// Python str.isspace() for the characters str.split() splits on
-__device__ __forceinline__ bool py_space(uint32_t c) {
-  if (c < 0x80) return (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x20);
-  return c == 0x85 || c == 0xa0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200a) || c == 0x2028 || c == 0x2029 ||
-         c == 0x202f || c == 0x205f || c == 0x3000;
-}
-
-// decode the UTF-8 character starting at p[i] (a lead byte), i < e
-__device__ __forceinline__ uint32_t decode_at(const uint8_t* p, int64_t i, int64_t e, int& n) {
-  const uint32_t b = p[i];
-  if (b < 0x80) {
-    n = 1;
-    return b;
-  }
-  n = b >= 0xF0 ? 4 : b >= 0xE0 ? 3 : 2;
-  uint32_t c = b & (0x7Fu >> n);
-  for (int k = 1; k < n; ++k) c = (c << 6) | (i + k < e ? (p[i + k] & 0x3Fu) : 0u);
-  return c;
-}
-
-// does byte i (s <= i < e) belong to a whitespace character?
-__device__ __forceinline__ bool ws_byte(const uint8_t* p, int64_t i, int64_t s, int64_t e) {
-  const uint32_t b = p[i];
-  if (b < 0x80) return py_space(b);
-  int64_t j = i;
-  while (j > s && j > i - 3 && (p[j] & 0xC0u) == 0x80u) --j;
-  int n;
-  return py_space(decode_at(p, j, e, n));
-}
-
-__device__ __forceinline__ int32_t vocab_lookup(const CollateVocab& V, const uint8_t* p, int64_t i, int64_t e,
-                                                int64_t& end) {
-  uint32_t h = 0x811c9dc5u;
-  int64_t j = i;
-  while (j < e) {
-    const uint32_t b = p[j];
-    if (b < 0x80) {
-      if (py_space(b)) break;
-      h = chash_step(h, b);
-      ++j;
-      continue;
-    }
-    int n;
-    const uint32_t c = decode_at(p, j, e, n);
-    if (py_space(c)) break;
-    for (int k = 0; k < n && j + k < e; ++k) h = chash_step(h, p[j + k]);
-    j += n;
-  }
-  if (j > e) j = e;
-  end = j;
-  h = chash_final(h);
-  const uint32_t len = (uint32_t)(j - i);
-  for (uint32_t s = h & V.mask;; s = (s + 1) & V.mask) {
-    const uint2 t = V.slots[s];
-    if (t.y == kEmpty) return V.unk;
-    if (t.x != h) continue;
-    const uint32_t vi = V.vinfo[t.y];
-    if ((vi & 0xFFu) != len) continue;
-    const uint8_t* q = V.vpool + (vi >> 8);
-    uint32_t k = 0;
-    while (k < len && q[k] == p[i + k]) ++k;
-    if (k == len) return (int32_t)t.y;
-  }
-}
-
-// Walk the tokens of bytes [s, e): calls f(ordinal, start) on the owning lane
-// (ordinal in token order); returns the token count (wave-uniform).
-template <class F>
-__device__ __forceinline__ int32_t scan_tokens(const uint8_t* p, int64_t s, int64_t e, F f) {
-  const int lane = threadIdx.x & 63;
-  int32_t count = 0;
-  for (int64_t base = s; base < e; base += 64) {
-    const int64_t i = base + lane;
-    bool st = false;
-    if (i < e) {
-      const uint32_t b = p[i];
-      st = (b & 0xC0u) != 0x80u && !ws_byte(p, i, s, e) && (i == s || ws_byte(p, i - 1, s, e));
-    }
-    const uint64_t m = __ballot(st);
-    if (st) f(count + (int32_t)__popcll(m & ((1ull << lane) - 1ull)), i);
-    count += (int32_t)__popcll(m);
-  }
-  return count;
 }
 
 // max_len = max over rows of len(A) + len(B) + 3
@@ -182,18 +81,13 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
     if (P.mode == COLLATE_STATIC) {
       for (int32_t j = lane; j < L; j += 64) lab[j] = -1;
       // positions: np.save v1.x bytes of a 1-D '<u2' array
-      const uint8_t* q = P.pos + P.pos_off[r];
-      const int64_t qn = P.pos_off[r + 1] - P.pos_off[r];
-      bool ok = qn >= 10 && q[0] == 0x93 && q[1] == 'N' && q[2] == 'U' && q[3] == 'M' && q[4] == 'P' &&
-                q[5] == 'Y' && q[6] == 1;
-      const int64_t hl = ok ? (int64_t)q[8] | ((int64_t)q[9] << 8) : 0;
-      ok = ok && 10 + hl <= qn && ((qn - 10 - hl) & 1) == 0;
-      if (!ok) {
+      const uint8_t* d;
+      int64_t np64;
+      if (!npy_u16_payload(P.pos + P.pos_off[r], P.pos_off[r + 1] - P.pos_off[r], d, np64)) {
         if (lane == 0) set_err(P.err, CERR_NPY, r);
         continue;
       }
-      const int32_t np = (int32_t)((qn - 10 - hl) >> 1);
-      const uint8_t* d = q + 10 + hl;
+      const int32_t np = (int32_t)np64;
       __builtin_amdgcn_wave_barrier();
       // labels[positions[k]] = id(masked_lm_labels.split()[k])
       const int64_t l0 = P.lab_off[r], l1 = P.lab_off[r + 1];

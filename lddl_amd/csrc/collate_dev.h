@@ -1,10 +1,14 @@
 // Device helpers shared by the collate kernels (collate.hip: rows from parquet
-// strings; collate_rows.hip / collate_unpadded.hip: rows from a pack result's
-// spans, padded and padding-free): the error word
-// and the counter-based draws of `_mask_tokens`.
+// strings; rows_from_strings.hip: a row table from parquet strings;
+// collate_rows.hip / collate_unpadded.hip: rows from a pack result's
+// spans, padded and padding-free): the error word, the counter-based draws of
+// `_mask_tokens`, and what reads a string column: Python's str.split(), the
+// whole-token vocab lookup and the np.save header of masked_lm_positions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "collate.h"
 
 namespace lddl {
 
@@ -37,6 +41,121 @@ __device__ __forceinline__ int64_t mask_one(int64_t id, bool special, int64_t ro
   const uint64_t g = splitmix64(k + idx + 2);
   if (unit53(g) < 0.5) return (int64_t)(((g & 0xFFFFFFFFull) * (uint64_t)n_random) >> 32);
   return id;
+}
+
+static constexpr uint32_t kEmpty = 0xFFFFFFFFu;
+
+__host__ __device__ __forceinline__ uint32_t chash_step(uint32_t h, uint32_t b) {
+  h ^= b;
+  return h * 0x01000193u;  // FNV-1a 32
+}
+
+__host__ __device__ __forceinline__ uint32_t chash_final(uint32_t h) {
+  h ^= h >> 16;
+  h *= 0x7feb352du;
+  h ^= h >> 15;
+  h *= 0x846ca68bu;
+  h ^= h >> 16;
+  return h;
+}
+
+// Python str.isspace() for the characters str.split() splits on
+__device__ __forceinline__ bool py_space(uint32_t c) {
+  if (c < 0x80) return (c >= 9 && c <= 13) || (c >= 0x1c && c <= 0x20);
+  return c == 0x85 || c == 0xa0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200a) || c == 0x2028 || c == 0x2029 ||
+         c == 0x202f || c == 0x205f || c == 0x3000;
+}
+
+// decode the UTF-8 character starting at p[i] (a lead byte), i < e
+__device__ __forceinline__ uint32_t decode_at(const uint8_t* p, int64_t i, int64_t e, int& n) {
+  const uint32_t b = p[i];
+  if (b < 0x80) {
+    n = 1;
+    return b;
+  }
+  n = b >= 0xF0 ? 4 : b >= 0xE0 ? 3 : 2;
+  uint32_t c = b & (0x7Fu >> n);
+  for (int k = 1; k < n; ++k) c = (c << 6) | (i + k < e ? (p[i + k] & 0x3Fu) : 0u);
+  return c;
+}
+
+// does byte i (s <= i < e) belong to a whitespace character?
+__device__ __forceinline__ bool ws_byte(const uint8_t* p, int64_t i, int64_t s, int64_t e) {
+  const uint32_t b = p[i];
+  if (b < 0x80) return py_space(b);
+  int64_t j = i;
+  while (j > s && j > i - 3 && (p[j] & 0xC0u) == 0x80u) --j;
+  int n;
+  return py_space(decode_at(p, j, e, n));
+}
+
+__device__ __forceinline__ int32_t vocab_lookup(const CollateVocab& V, const uint8_t* p, int64_t i, int64_t e,
+                                                int64_t& end) {
+  uint32_t h = 0x811c9dc5u;
+  int64_t j = i;
+  while (j < e) {
+    const uint32_t b = p[j];
+    if (b < 0x80) {
+      if (py_space(b)) break;
+      h = chash_step(h, b);
+      ++j;
+      continue;
+    }
+    int n;
+    const uint32_t c = decode_at(p, j, e, n);
+    if (py_space(c)) break;
+    for (int k = 0; k < n && j + k < e; ++k) h = chash_step(h, p[j + k]);
+    j += n;
+  }
+  if (j > e) j = e;
+  end = j;
+  h = chash_final(h);
+  const uint32_t len = (uint32_t)(j - i);
+  for (uint32_t s = h & V.mask;; s = (s + 1) & V.mask) {
+    const uint2 t = V.slots[s];
+    if (t.y == kEmpty) return V.unk;
+    if (t.x != h) continue;
+    const uint32_t vi = V.vinfo[t.y];
+    if ((vi & 0xFFu) != len) continue;
+    const uint8_t* q = V.vpool + (vi >> 8);
+    uint32_t k = 0;
+    while (k < len && q[k] == p[i + k]) ++k;
+    if (k == len) return (int32_t)t.y;
+  }
+}
+
+// Walk the tokens of bytes [s, e): calls f(ordinal, start) on the owning lane
+// (ordinal in token order); returns the token count (wave-uniform).
+template <class F>
+__device__ __forceinline__ int32_t scan_tokens(const uint8_t* p, int64_t s, int64_t e, F f) {
+  const int lane = threadIdx.x & 63;
+  int32_t count = 0;
+  for (int64_t base = s; base < e; base += 64) {
+    const int64_t i = base + lane;
+    bool st = false;
+    if (i < e) {
+      const uint32_t b = p[i];
+      st = (b & 0xC0u) != 0x80u && !ws_byte(p, i, s, e) && (i == s || ws_byte(p, i - 1, s, e));
+    }
+    const uint64_t m = __ballot(st);
+    if (st) f(count + (int32_t)__popcll(m & ((1ull << lane) - 1ull)), i);
+    count += (int32_t)__popcll(m);
+  }
+  return count;
+}
+
+// np.save v1.x bytes q[0, qn) of a 1-D '<u2' array (masked_lm_positions,
+// lddl/utils.py deserialize_np_array): d = its payload, np = its entries;
+// false when the bytes are not that
+__device__ __forceinline__ bool npy_u16_payload(const uint8_t* q, int64_t qn, const uint8_t*& d, int64_t& np) {
+  bool ok = qn >= 10 && q[0] == 0x93 && q[1] == 'N' && q[2] == 'U' && q[3] == 'M' && q[4] == 'P' && q[5] == 'Y' &&
+            q[6] == 1;
+  const int64_t hl = ok ? (int64_t)q[8] | ((int64_t)q[9] << 8) : 0;
+  ok = ok && 10 + hl <= qn && ((qn - 10 - hl) & 1) == 0;
+  if (!ok) return false;
+  np = (qn - 10 - hl) >> 1;
+  d = q + 10 + hl;
+  return true;
 }
 
 }  // namespace lddl

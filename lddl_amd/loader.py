@@ -10,6 +10,12 @@ one HIP kernel (``lddl_collate_bert``, csrc/collate.hip): the batch's string
 columns are staged in one pinned buffer, copied once, split / looked up /
 padded / masked on the device, and the outputs stay in HBM for the model.
 
+``BertCollate.load_rows`` / ``load_shards`` do the split and the vocabulary
+lookup once per shard instead (``lddl_rows_from_strings``,
+csrc/rows_from_strings.hip): the shard's rows become a ``PackResult`` with
+spans on the GPU, and ``collate_rows`` / ``collate_rows_unpadded`` /
+``RowBatches`` then serve files on disk as they serve a pack result.
+
 Differences from the reference, by design:
 * dynamic masking draws from a counter-based hash of (seed, batch counter, row,
   column), not torch's CPU generator: the same distribution (mask rate
@@ -19,6 +25,8 @@ Differences from the reference, by design:
   training loop moves with ``.to(device)``).
 """
 import ctypes
+import os
+import re
 
 import numpy as np
 import torch
@@ -52,6 +60,117 @@ def _arrow_column(arr):
   off = np.frombuffer(bufs[1], dtype=odt)[arr.offset:arr.offset + len(arr) + 1].astype(np.int64)
   data = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
   return data, off
+
+
+def _merge_columns(parts):
+  """[(bytes, offsets), ...] of consecutive row ranges -> one (bytes, offsets from 0)"""
+  if len(parts) == 1:
+    return parts[0]
+  data = np.concatenate([d[int(o[0]):int(o[-1])] for d, o in parts])
+  off, base = [np.zeros(1, np.int64)], 0
+  for _, o in parts:
+    off.append(o[1:] - o[0] + base)
+    base += int(o[-1] - o[0])
+  return data, np.concatenate(off)
+
+
+def _shard_columns(table):
+  """load_rows' input -> ([A, B(, positions, labels)] as (bytes, offsets), is_random_next bytes, static)"""
+  if hasattr(table, 'schema'):
+    table = [table]
+  table = list(table)
+  if not table:
+    raise ValueError('no rows')
+  if not hasattr(table[0], 'schema'):  # the reference's samples
+    static = len(table[0]) > 3
+    if any(len(s) != (5 if static else 3) for s in table):
+      raise ValueError('samples of 3 fields, or of 5 with static masks')
+    cols = [_column([s[0] for s in table], True), _column([s[1] for s in table], True)]
+    if static:
+      cols += [_column([s[3] for s in table], False), _column([s[4] for s in table], True)]
+    return cols, np.fromiter((bool(s[2]) for s in table), dtype=np.uint8, count=len(table)), static
+  names = ['A', 'B']
+  for t in table:
+    if 'A' not in t.schema.names or 'B' not in t.schema.names:
+      raise ValueError('not a BERT shard (columns %s): CodeBERT shards have no loader' % (t.schema.names,))
+  static = 'masked_lm_positions' in table[0].schema.names
+  if static:
+    names += ['masked_lm_positions', 'masked_lm_labels']
+  for t in table:
+    if ('masked_lm_positions' in t.schema.names) != static or (static and 'masked_lm_labels' not in t.schema.names):
+      raise ValueError('shards with and without static masks')
+  cols = [_merge_columns([_arrow_column(t.column(k)) for t in table]) for k in names]
+  rn = np.concatenate([np.asarray(t.column('is_random_next').to_numpy(zero_copy_only=False), dtype=np.uint8)
+                       for t in table])
+  return cols, rn, static
+
+
+_SHARD_NAME = re.compile(r'^(?:(?:part\.|shard-)(\d+)(?=\.parquet)|[^/]*?)\.parquet(?:_(\d+))?$')
+
+
+def shard_files(names):
+  """The parquet files among ``names`` as [(name, partition, bin)] in
+  (partition, bin) order.  A parquet file ends in ``.parquet`` (bin None) or
+  ``.parquet_<b>`` (bin b, the convention of lddl/utils.py:54-75); other names
+  are skipped.  The partition is the p of the preprocessor's
+  ``part.<p>.parquet[_<b>]`` or the k of the load balancer's
+  ``shard-<k>.parquet[_<b>]``; when some file is named otherwise, partitions
+  are the ranks of the distinct stems in sorted order instead.  The bins found
+  must be 0 .. nbins - 1 and a directory is binned or unbinned, not both."""
+  out, stems = [], []
+  for name in names:
+    base = os.path.basename(name)
+    m = _SHARD_NAME.match(base)
+    if not m:
+      continue
+    out.append([name, None if m.group(1) is None else int(m.group(1)), None if m.group(2) is None else int(m.group(2))])
+    stems.append(base[:base.rindex('.parquet')])
+  if any(f[1] is None for f in out) or len({s.split('.')[0].split('-')[0] for s in stems}) > 1:
+    rank = {s: i for i, s in enumerate(sorted(set(stems)))}
+    for f, s in zip(out, stems):
+      f[1] = rank[s]
+  found = sorted(set(f[2] for f in out if f[2] is not None))
+  if found != list(range(len(found))):
+    raise ValueError('the bin suffixes %s are not 0 .. %d' % (found, len(found) - 1))
+  if found and any(f[2] is None for f in out):
+    raise ValueError('binned and unbinned files together')
+  return sorted((tuple(f) for f in out), key=lambda f: (f[1], -1 if f[2] is None else f[2], f[0]))
+
+
+def load_shards(collate, path_or_paths):
+  """Every ``*.parquet`` / ``*.parquet_<b>`` file under a directory (or the
+  files of a list) as one GPU row table: read with pyarrow in (partition, bin)
+  order (shard_files), each row's bin from its file's suffix and its partition
+  from ``part.<p>`` (the preprocessor's sink) or ``shard-<k>`` (the load
+  balancer's output), then one ``collate.load_rows``.  Files without A / B
+  columns (CodeBERT shards) raise ValueError."""
+  import pyarrow.parquet as pq
+  if isinstance(path_or_paths, (str, bytes, os.PathLike)):
+    path = os.fspath(path_or_paths)
+    if os.path.isdir(path):
+      names = [os.path.join(r, f) for r, _, fs in os.walk(path) for f in fs]
+    else:
+      names = [path]
+  else:
+    names = [os.fspath(x) for x in path_or_paths]
+  files = shard_files(names)
+  if not files:
+    raise ValueError('no parquet files in %r' % (path_or_paths,))
+  tables, bins, part = [], [], []
+  for name, pt, b in files:
+    t = pq.read_table(name)
+    if 'A' not in t.schema.names or 'B' not in t.schema.names:
+      raise ValueError('%s is not a BERT shard (columns %s): CodeBERT shards have no loader' % (name, t.schema.names))
+    if t.num_rows == 0:
+      continue  # every bin is written, even when empty
+    tables.append(t)
+    bins.append(np.full(t.num_rows, b or 0, np.uint8))
+    part.append(np.full(t.num_rows, pt, np.int64))
+  if not tables:
+    raise ValueError('no rows in %r' % (path_or_paths,))
+  binned = files[0][2] is not None
+  nbins = max(b for _, _, b in files) + 1 if binned else None
+  return collate.load_rows(tables, np.concatenate(bins) if binned else None, np.concatenate(part), nbins)
 
 
 class BertCollate:
@@ -265,6 +384,82 @@ class BertCollate:
     return {'input_ids': out[0], 'token_type_ids': out[1], 'position_ids': out[2], 'next_sentence_labels': nsl,
             'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3], 'cu_seqlens': cu,
             'max_seqlen': int(longest.value)}
+
+  def load_rows(self, table, bins=None, part=None, nbins=None):
+    """The rows of a shard as a GPU row table, once (lddl_rows_from_strings_len
+    + lddl_rows_from_strings): the decode-and-lookup half of the reference's
+    loader (bert.py:42-60, :83-89, :109-124) done per shard instead of per
+    batch.  Returns a ``pipeline.PackResult`` with spans, so ``collate_rows``,
+    ``collate_rows_unpadded``, ``RowBatches``, ``rows()`` and
+    ``host_tokens()`` serve files on disk as they serve a pack result.
+
+    table: a pyarrow Table / RecordBatch of the shard schema (string or
+    large_string columns), a list of such tables, or a list of the reference's
+    3- or 5-tuples.  Shards with masked_lm_positions / masked_lm_labels give a
+    result with static masks.  bins / part: the bin and the partition of every
+    row (default zeros); without bins the result is unbinned (nbins 1), with
+    them nbins defaults to max(bins) + 1.  The columns are staged in one pinned
+    buffer and copied once; the staging is released when the call returns.
+    Fields that only a pack has stay None: tokens, ntok, ids_off, pack."""
+    from .pipeline import PackResult
+    cols, rn, static = _shard_columns(table)
+    n = len(rn)
+    if n == 0:
+      raise ValueError('no rows')
+    L = _lib.lib()
+    st = _stream()
+    P = ctypes.c_void_p
+    p = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+    dev, host, ptrs = self._upload(cols, rn)
+    inp = [P(x) for x in ptrs[:8]] if static else [P(x) for x in ptrs[:4]] + [P(0)] * 4
+
+    def buf(m, dtype):
+      return torch.empty(max(m, 1), dtype=dtype, device=self.device)
+    len0, len1 = buf(n, torch.int16), buf(n, torch.int16)
+    src0, src1 = buf(n, torch.int64), buf(n, torch.int64)
+    tok_off = buf(n + 1, torch.int64)
+    mlm_off = buf(n + 1, torch.int64) if static else None
+    tot = (ctypes.c_int64 * 3)()
+
+    def check(rc):
+      if rc == -7:
+        raise IndexError(L.lddl_last_error().decode())
+      _lib.check(rc)
+    try:
+      check(L.lddl_rows_from_strings_len(self.tok.handle, *inp, n, p(len0), p(len1), p(src0), p(src1), p(tok_off),
+                                         p(mlm_off), tot, st))
+    except Exception:
+      torch.cuda.current_stream().synchronize()  # a call refused before its launch leaves the staging copy queued
+      raise
+    n_ids, n_masked, n_tokens = int(tot[0]), int(tot[1]), int(tot[2])
+    ids = torch.empty(n_ids + 16, dtype=torch.int16, device=self.device)  # 16 zeroed entries behind the last id
+    ids[n_ids:].zero_()
+    flags = buf(n, torch.uint8)
+    mlm = [buf(n_masked, torch.int16) for _ in range(3)] if static else [None] * 3
+    check(L.lddl_rows_from_strings(self.tok.handle, *inp, P(ptrs[-1]), n, p(len0), p(len1), p(src0), p(src1),
+                                   p(mlm_off), p(ids), n_ids, p(flags), p(mlm[0]), p(mlm[1]), p(mlm[2]), n_masked, st))
+    del dev, host  # the length call synchronised the stream behind the staging copy
+    part_h = np.zeros(n, np.int64) if part is None else np.ascontiguousarray(part, dtype=np.int64).reshape(-1)
+    bins_h = np.zeros(n, np.uint8) if bins is None else np.ascontiguousarray(bins, dtype=np.uint8).reshape(-1)
+    if len(part_h) != n or len(bins_h) != n:
+      raise ValueError('bins / part: one entry per row')
+    if bins is None:
+      nbins = 1
+    elif nbins is None:
+      nbins = int(bins_h.max()) + 1
+    if int(bins_h.max()) >= nbins:
+      raise ValueError('a bin id >= nbins %d' % nbins)
+    n_part = int(part_h.max()) + 1
+    bin_count = np.bincount(part_h * nbins + bins_h, minlength=n_part * nbins).reshape(n_part, nbins).astype(np.int64)
+    h2d = lambda a: torch.from_numpy(a).to(self.device)  # noqa: E731
+    res = PackResult(n, n_tokens, int(nbins), None, tok_off, len0, len1, flags, h2d(bins_h), h2d(part_h),
+                     h2d(bin_count))
+    res.ids, res.src0, res.src1 = ids, src0, src1
+    res.cls_id, res.sep_id = self.tok.cls_id, self.tok.sep_id
+    if static:
+      res.n_masked = n_masked
+      res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token = mlm_off, mlm[0], mlm[1], mlm[2]
+    return res
 
   # ---- the reference's two steps, separately ----------------------------------
   def to_encoded_inputs(self, batch):

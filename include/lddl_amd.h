@@ -309,7 +309,22 @@ int lddl_collate_bert(lddl_ctx *ctx, const uint8_t *d_a, const int64_t *d_a_off,
  * [0, vocab size) (p 0.5), else kept; labels = the original id where
  * selected, ignore_index elsewhere.  Draws are a counter-based hash of
  * (seed, counter, row, column): the reference's distribution, not torch's
- * CPU generator stream. */
+ * CPU generator stream.
+ *
+ * The draw, in uint64 arithmetic that wraps (tests/mask_model.py is this in
+ * numpy; every entry point with a dynamic mode draws the same way):
+ *   sm(x)   = splitmix64's output function: x += 0x9E3779B97F4A7C15;
+ *             x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *             x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31
+ *   unit(h) = (double)(h >> 11) * 2^-53, exact, in [0, 1)
+ *   key   k = sm(seed ^ sm(counter))
+ *   index i = ((row << 20) | column) * 3, row = the row of the batch (not of
+ *             a row table), column < 2^20
+ *   selected  iff special_tokens_mask == 0 and unit(sm(k + i)) < mlm_probability
+ *   [MASK]    iff selected and unit(sm(k + i + 1)) < 0.8
+ *   otherwise, with g = sm(k + i + 2): the id ((g & 0xFFFFFFFF) * vocab size) >> 32
+ *             iff unit(g) < 0.5, else the input id unchanged.
+ * Ids and labels pass through as 64-bit values. */
 int lddl_mask_tokens(lddl_ctx *ctx, int64_t *d_inputs, const int64_t *d_special_tokens_mask, int64_t *d_labels,
                      int64_t n_rows, int64_t seq_len, double mlm_probability, int64_t ignore_index, uint64_t seed,
                      uint64_t counter, void *stream);

@@ -490,6 +490,75 @@ int lddl_rows_from_strings(lddl_ctx *ctx, const uint8_t *d_a, const int64_t *d_a
                            uint16_t *d_out_mlm_pos, uint16_t *d_out_mlm_label, uint16_t *d_out_mlm_token,
                            int64_t mlm_cap, void *stream);
 
+/* ---- BART: sentence aggregation --------------------------------------------
+ * The reference's third preprocessor (lddl/dask/bart/pretrain.py) cuts every
+ * document into chunks of whole sentences and saves one string column,
+ * `sentences`.  Input: the sentence-split corpus of lddl_tokenize (d_data,
+ * d_sent_off [n_sent + 1], d_doc_sent_off [n_doc + 1]); a document is one
+ * input line taken whole (the reference does not split off a leading id here,
+ * pretrain.py:82-86, so the id is part of the first sentence), its sentences
+ * stripped and the empty ones dropped by the front end.  No vocabulary is
+ * read and nothing is drawn at random.  The offsets are checked, not trusted:
+ * none of these calls loads or stores through an offset outside its array.
+ *
+ * lddl_bart_count: d_out_nwords[s] = len(sentence.split()) of bytes
+ * [sent_off[s], sent_off[s + 1]) as int32 (pretrain.py:113), with Python's
+ * whitespace rule for str (the characters str.isspace() accepts).  A
+ * sentence's first character starts a word whenever it is not whitespace,
+ * whatever byte precedes it in d_data; no byte outside the sentence is read.
+ * Synchronises the stream.  LDDL_EINVAL: a NULL pointer, a negative count, a
+ * sentence whose offsets run backwards or leave [0, nbytes] (its count is 0). */
+int lddl_bart_count(lddl_ctx *ctx, const uint8_t *d_data, int64_t nbytes, const int64_t *d_sent_off, int64_t n_sent,
+                    int32_t *d_out_nwords, void *stream);
+
+/* The chunk plan, length pass (pretrain.py:88-128 `_aggregate_sentences`):
+ * with T = target_seq_length - 3, a document's sentences are walked in order;
+ * each adds its d_nwords to a running count, and when the count reaches >= T
+ * the chunk closes and the count restarts at 0; after the last sentence the
+ * remainder is a chunk only when its count is > 0 (a remainder of 0-word
+ * sentences is dropped with its text; a document of only such sentences, or
+ * of none, yields nothing unless T <= 0, where every sentence closes a chunk
+ * as the reference's `>=` has it).  d_out_doc_chunk_off [n_doc + 1] (int64) =
+ * the chunks per document in exclusive-scan form; out_totals = {n_chunks, the
+ * bytes of all chunk texts}, a chunk's bytes being the sum of 1 + len(sentence)
+ * over its sentences (pretrain.py:112), summed in 64 bits.  Synchronises the
+ * stream once.  LDDL_EINVAL: a NULL pointer, a negative count, d_doc_sent_off
+ * not ending at n_sent, a document or sentence whose offsets run backwards or
+ * leave their array; LDDL_ECAPACITY: a chunk of 2^31 bytes or more. */
+int lddl_bart_plan_len(lddl_ctx *ctx, const int32_t *d_nwords, const int64_t *d_sent_off,
+                       const int64_t *d_doc_sent_off, int64_t n_doc, int64_t n_sent, int32_t target_seq_length,
+                       int64_t *d_out_doc_chunk_off, int64_t out_totals[2], void *stream);
+
+/* The chunk plan, fill pass: per chunk c (document-major, in the reference's
+ * order) d_out_chunk_sent0[c] = its first sentence (int64), d_out_chunk_nsent[c]
+ * = its sentences, d_out_chunk_num_tokens[c] = the reference's num_tokens
+ * (pretrain.py:115-119; int32 both), and d_out_chunk_off [n_chunks + 1] = the
+ * Arrow offsets of the chunk texts (int64).  d_doc_chunk_off and n_chunks are
+ * lddl_bart_plan_len's and are checked against the walk, not trusted.
+ * Synchronises the stream.  Errors as lddl_bart_plan_len, and LDDL_EINVAL when
+ * d_doc_chunk_off / n_chunks are not what that call gives. */
+int lddl_bart_plan(lddl_ctx *ctx, const int32_t *d_nwords, const int64_t *d_sent_off, const int64_t *d_doc_sent_off,
+                   const int64_t *d_doc_chunk_off, int64_t n_doc, int64_t n_sent, int32_t target_seq_length,
+                   int64_t n_chunks, int64_t *d_out_chunk_sent0, int32_t *d_out_chunk_nsent,
+                   int32_t *d_out_chunk_num_tokens, int64_t *d_out_chunk_off, void *stream);
+
+/* The `sentences` column of chunks [c0, c0 + n) (pretrain.py:112 `chunk += " "
+ * + sentence`, :136-147): d_out_off [n + 1] = their Arrow offsets rebased to
+ * 0, d_out_bytes = each chunk's sentences with one space in front of every
+ * sentence.  Two-phase like lddl_render_strings: with d_out_bytes == NULL only
+ * d_out_off and *out_nbytes are produced; out_cap < *out_nbytes is
+ * LDDL_ECAPACITY with no byte written.  The chunk arrays (n_chunks entries,
+ * d_chunk_off n_chunks + 1) are checked, not trusted: before it stores, a
+ * chunk checks that its sentences lie in [0, n_sent), that their offsets run
+ * forward inside [0, nbytes], that bytes + spaces equal chunk_off[c + 1] -
+ * chunk_off[c] and that its span lies in [0, out_cap).  A refused chunk is
+ * left unwritten, no chunk stores outside its own span, and the call returns
+ * LDDL_EINVAL naming the lowest refused chunk.  Synchronises the stream. */
+int lddl_bart_render(lddl_ctx *ctx, const uint8_t *d_data, int64_t nbytes, const int64_t *d_sent_off, int64_t n_sent,
+                     const int64_t *d_chunk_sent0, const int32_t *d_chunk_nsent, const int64_t *d_chunk_off,
+                     int64_t n_chunks, int64_t c0, int64_t n, int64_t *d_out_off, uint8_t *d_out_bytes,
+                     int64_t out_cap, int64_t *out_nbytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,6 +75,13 @@ SIGNATURES = {
                                    [ctypes.POINTER(c_int64), c_void_p]),
     'lddl_rows_from_strings': (c_int, [c_void_p] * 10 + [c_int64] + [c_void_p] * 6 + [c_int64] + [c_void_p] * 4 +
                                [c_int64, c_void_p]),
+    'lddl_bart_count': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
+    'lddl_bart_plan_len': (c_int, [c_void_p] * 4 + [c_int64, c_int64, c_int32, c_void_p, ctypes.POINTER(c_int64),
+                                                   c_void_p]),
+    'lddl_bart_plan': (c_int, [c_void_p] * 5 + [c_int64, c_int64, c_int32, c_int64] + [c_void_p] * 5),
+    'lddl_bart_render': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                 c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64),
+                                 c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,182 @@
+"""BART pretraining data: the reference's ``preprocess_bart_pretrain``
+(lddl/dask/bart/pretrain.py) on MI355X.
+
+The reference cuts every document into chunks of whole sentences close to
+``target_seq_length - 3`` words (``_aggregate_sentences``, pretrain.py:88-128)
+and saves the chunk text as the one column ``sentences`` (:136-152).  Here
+the sentence-split corpus sits in HBM (a pipeline.ShardSet, as for BERT) and
+liblddl_amd.so counts the words (lddl_bart_count), plans the chunks
+(lddl_bart_plan_len / lddl_bart_plan) and renders the column
+(lddl_bart_render); this module moves buffers and writes the files.
+
+A document is one input line taken whole: unlike the BERT path the reference
+does not split off the leading id here (pretrain.py:82-86), so the id is part
+of the first sentence.  Nothing is drawn at random and no vocabulary is read;
+rows are in input order.
+"""
+import ctypes
+import dataclasses
+import os
+
+import numpy as np
+import pyarrow as pa
+import torch
+
+from . import _lib
+from .tokenizer import _ptr, _stream
+
+SCHEMA = pa.schema([('sentences', pa.string())])  # pretrain.py:144-146
+
+
+def _handle(tokenizer_or_ctx):
+  """the lddl_ctx of a Tokenizer, a pipeline.Packer or a raw handle"""
+  t = getattr(tokenizer_or_ctx, 'tok', tokenizer_or_ctx)
+  return getattr(t, 'handle', t)
+
+
+@dataclasses.dataclass
+class BartResult:
+  """The chunk plan of one aggregate() call, on the device.  Chunk c (chunks
+  are document-major, in input order) is sentences [chunk_sent0[c],
+  chunk_sent0[c] + chunk_nsent[c]) and holds num_tokens[c] words; its text is
+  bytes [chunk_off[c], chunk_off[c + 1]) of the column."""
+  ctx: object
+  shards: object               # the pipeline.ShardSet aggregated
+  target_seq_length: int
+  n_chunks: int
+  nbytes: int                  # bytes of the whole column
+  nwords: torch.Tensor         # int32 [n_sent]
+  doc_chunk_off: torch.Tensor  # int64 [n_doc + 1]
+  chunk_sent0: torch.Tensor    # int64 [n_chunks]
+  chunk_nsent: torch.Tensor    # int32 [n_chunks]
+  num_tokens: torch.Tensor     # int32 [n_chunks]
+  chunk_off: torch.Tensor      # int64 [n_chunks + 1]
+  part_chunk_off: np.ndarray   # int64 [n_part + 1] (host): doc_chunk_off taken at part_doc_off
+
+  def render(self, c0=0, n=None, stream=None, host=True):
+    """(offsets int64 [n + 1] from 0, bytes uint8) of chunks [c0, c0 + n):
+    numpy arrays, or device tensors with host=False"""
+    n = self.n_chunks - c0 if n is None else n
+    sh = self.shards
+    dev = sh.data.device
+    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    nb = ctypes.c_int64(0)
+    s = _stream(stream)
+    args = (_handle(self.ctx), _ptr(sh.data), sh.nbytes, _ptr(sh.sent_off), sh.n_sent, _ptr(self.chunk_sent0),
+            _ptr(self.chunk_nsent), _ptr(self.chunk_off), self.n_chunks, c0, n, _ptr(off))
+    L = _lib.lib()
+    _lib.check(L.lddl_bart_render(*args, None, 0, ctypes.byref(nb), s))
+    data = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
+    _lib.check(L.lddl_bart_render(*args, _ptr(data), nb.value, ctypes.byref(nb), s))
+    if not host:
+      return off, data[:nb.value]
+    from .writer import _host
+    return _host(off, stream), _host(data[:nb.value], stream)
+
+
+def aggregate(corpus_on_device, part_doc_off=None, target_seq_length=128, tokenizer_or_ctx=None, stream=None):
+  """_aggregate_sentences over every document of a sentence-split corpus on
+  the device (a pipeline.ShardSet).  part_doc_off: the partitions as document
+  offsets (default: the ShardSet's).  tokenizer_or_ctx: a Tokenizer, Packer or
+  lddl_ctx handle (any vocabulary: it is not read)."""
+  sh = corpus_on_device
+  if tokenizer_or_ctx is None:
+    raise ValueError('aggregate needs a Tokenizer, a Packer or an lddl_ctx handle')
+  if part_doc_off is None:
+    part_doc_off = sh.part_doc_off
+  pdo = part_doc_off.cpu().numpy() if isinstance(part_doc_off, torch.Tensor) else np.asarray(part_doc_off, np.int64)
+  n_sent, n_doc = sh.n_sent, sh.n_doc
+  if len(pdo) < 1 or pdo[0] != 0 or pdo[-1] != n_doc or np.any(np.diff(pdo) < 0):
+    raise ValueError('part_doc_off must be a non-decreasing cover of [0, n_doc]')
+  L, h, s = _lib.lib(), _handle(tokenizer_or_ctx), _stream(stream)
+  dev = sh.data.device
+  nwords = torch.empty(max(n_sent, 1), dtype=torch.int32, device=dev)
+  _lib.check(L.lddl_bart_count(h, _ptr(sh.data), sh.nbytes, _ptr(sh.sent_off), n_sent, _ptr(nwords), s))
+  dco = torch.empty(n_doc + 1, dtype=torch.int64, device=dev)
+  tot = (ctypes.c_int64 * 2)()
+  _lib.check(L.lddl_bart_plan_len(h, _ptr(nwords), _ptr(sh.sent_off), _ptr(sh.doc_sent_off), n_doc, n_sent,
+                                  target_seq_length, _ptr(dco), tot, s))
+  nc = int(tot[0])
+  sent0 = torch.empty(max(nc, 1), dtype=torch.int64, device=dev)
+  nsent = torch.empty(max(nc, 1), dtype=torch.int32, device=dev)
+  ntok = torch.empty(max(nc, 1), dtype=torch.int32, device=dev)
+  coff = torch.empty(nc + 1, dtype=torch.int64, device=dev)
+  _lib.check(L.lddl_bart_plan(h, _ptr(nwords), _ptr(sh.sent_off), _ptr(sh.doc_sent_off), _ptr(dco), n_doc, n_sent,
+                              target_seq_length, nc, _ptr(sent0), _ptr(nsent), _ptr(ntok), _ptr(coff), s))
+  pco = dco[torch.from_numpy(pdo).to(dev)].cpu().numpy()
+  return BartResult(tokenizer_or_ctx, sh, target_seq_length, nc, int(tot[1]), nwords[:n_sent], dco, sent0[:nc],
+                    nsent[:nc], ntok[:nc], coff, pco)
+
+
+def _file_batches(part_chunk_off, max_parts, batch_rows):
+  """runs of whole partitions of about batch_rows chunks: (p0, p1) pairs"""
+  n_part = len(part_chunk_off) - 1
+  if max_parts is not None:
+    n_part = min(n_part, max_parts)
+  p = 0
+  while p < n_part:
+    q = p + 1
+    while q < n_part and part_chunk_off[q + 1] - part_chunk_off[p] <= batch_rows:
+      q += 1
+    yield p, q
+    p = q
+
+
+def write_bart_shards(result, out_dir, part_base=0, compression='snappy', batch_rows=1 << 16, max_parts=None,
+                      stream=None, executor=None, pending=None):
+  """``to_parquet`` of the reference (pretrain.py:137-147): partition p of the
+  result becomes ``part.{part_base + p}.parquet`` with the one string column
+  ``sentences``; every partition's file is created, empty ones included.
+  executor / pending as writer.write_shards: a writer.ProcessEncoder or a
+  thread pool takes the encodes and their futures go to `pending`; without
+  one the files are written before the call returns.  Returns the files."""
+  import concurrent.futures
+  import pyarrow.parquet as pq
+  from . import writer
+  os.makedirs(out_dir, exist_ok=True)
+  pco = result.part_chunk_off
+  own = executor is None
+  proc = isinstance(executor, writer.ProcessEncoder)
+  pool = concurrent.futures.ThreadPoolExecutor(writer.encode_workers()) if own else executor
+  files, mine = [], []
+  for p0, p1 in _file_batches(pco, max_parts, batch_rows):
+    c0, n = int(pco[p0]), int(pco[p1] - pco[p0])
+    flist = [(os.path.join(out_dir, 'part.%d.parquet' % (part_base + p)), int(pco[p] - c0), int(pco[p + 1] - c0))
+             for p in range(p0, p1)]
+    if proc:
+      off, data = result.render(c0, n, stream, host=False)
+      mine.extend(executor.submit_batch(n, [('sentences', 'str', off, data)], SCHEMA, flist, compression, [], stream))
+    else:
+      off, data = result.render(c0, n, stream)
+      for path, lo, hi in flist:
+        t = pa.Table.from_arrays([writer._arrow(pa.string(), off, data, lo, hi)], schema=SCHEMA)
+        mine.append(pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=False))
+    files.extend(f[0] for f in flist)
+  if own:
+    for fu in mine:
+      fu.result()
+    pool.shutdown()
+  elif pending is not None:
+    pending.extend(mine)
+  return files
+
+
+def write_bart_txt(result, out_dir, part_base=0, batch_rows=1 << 20, max_parts=None, stream=None):
+  """The reference's txt sink (pretrain.py:148-150): one chunk per line in
+  ``{part_base + p}.txt``, lines joined by '\\n' with no final newline (dask's
+  to_textfiles, the convention writer.write_txt documents).  Every
+  partition's file is created.  Returns the files."""
+  os.makedirs(out_dir, exist_ok=True)
+  pco = result.part_chunk_off
+  files = []
+  for p0, p1 in _file_batches(pco, max_parts, batch_rows):
+    c0, n = int(pco[p0]), int(pco[p1] - pco[p0])
+    off, data = result.render(c0, n, stream)
+    raw = data.tobytes()
+    for p in range(p0, p1):
+      lo, hi = int(pco[p] - c0), int(pco[p + 1] - c0)
+      path = os.path.join(out_dir, '%d.txt' % (part_base + p))
+      with open(path, 'wb') as fh:
+        fh.write(b'\n'.join(raw[off[i]:off[i + 1]] for i in range(lo, hi)))
+      files.append(path)
+  return files

@@ -94,6 +94,8 @@ enum CtxWs {
                    // lddl_collate_rows_cu_seqlens / lddl_rows_from_strings_len: chunk sums of their scans
   CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len;
                    // lddl_collate_rows_cu_seqlens: total, max_len; lddl_rows_from_strings_len: its three totals
+                   // the lddl_bart_* calls use the three too: ROWS = chunks per document (plan_len) / bytes per chunk
+                   // (plan), BSUM = block sums of their scans, META = {bytes total, refused chunk, error word}
   CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded] / lddl_rows_from_strings[_len]:
                    // the error word
   CW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP]; written by lddl_tokenize (lddl_set_special_flags),
@@ -113,9 +115,13 @@ enum CtxWs {
 // on purpose: the eight fill one cache line.  A value narrower than 8 bytes fills the word's low bytes.
 enum HostWord {
   HW_NPAIRS,        // lddl_pack_bert / _codebert: the rows of the pack
+  HW_BART_LO = HW_NPAIRS,  // the same word; lddl_bart_plan_len: the chunks; lddl_bart_render: chunk_off[c0]
   HW_NTOK,          // lddl_pack_bert / _codebert: their tokens; lddl_rows_from_strings_len: the table's ids
+  HW_BART_HI = HW_NTOK,    // the same word; lddl_bart_plan_len: the chunks' bytes; lddl_bart_render: chunk_off[c0 + n],
+                           // then the lowest refused chunk
   HW_PACK_ERR,      // lddl_pack_bert / _codebert: the partitions' PACK_E* flags or-ed (int32);
                     // lddl_rows_from_strings_len: the table's row tokens (one 24-byte copy with its neighbours)
+  HW_BART_NSENT = HW_PACK_ERR,  // the same word; lddl_bart_plan_len: doc_sent_off's last entry, compared with n_sent
   HW_NMASK,         // lddl_pack_bert (masking): the masked entries; lddl_rows_from_strings_len: the same of the table
   HW_MARENA_USED,   // lddl_pack_bert (masking): the arena entries the bump allocator handed out
   HW_NDENSE,        // lddl_pack_bert / _codebert: the tokenizer's dense ids

@@ -155,9 +155,10 @@ def sample_shuffle(records, seed, sample_ratio):
   return [records[i] for i in sample_order(len(records), seed, sample_ratio)]
 
 
-def split_records(records, codebert=False, splitter=None):
+def split_records(records, codebert=False, splitter=None, whole_line=False):
   """Documents (in order) -> sentence-split synth.Corpus + doc ids; document
-  i of the corpus is record i.
+  i of the corpus is record i.  whole_line (BART, bart/pretrain.py:82-86):
+  the whole record is split, its leading id included (doc ids are empty).
 
   BERT: _to_document (pretrain.py:82-97): sentences = split(body), each
   stripped, empty ones dropped.  CodeBERT: _to_code_pair
@@ -174,7 +175,7 @@ def split_records(records, codebert=False, splitter=None):
       sents.extend(codes)
       nseg.append(len(docs))
     else:
-      doc_id, body = split_id_text(r)
+      doc_id, body = ('', r) if whole_line else split_id_text(r)
       sents.extend(s.strip() for s in splitter(body) if s.strip())
     ids.append(doc_id)
     doc_off.append(len(sents))
@@ -359,19 +360,20 @@ def _check(args):
 _FE = {}  # the split workers' fork-inherited state (record index, order, mode, splitter)
 
 
-def split_chunk(index, idx, codebert, split):
+def split_chunk(index, idx, codebert, split, whole_line=False):
   """records idx of the index -> (corpus, doc ids): BERT records under the
   rule-based splitter go through the C splitter (splitnative: the same
   result as split_records, ~13x faster; LDDL_SPLIT_NATIVE=0 turns it off),
-  everything else (CodeBERT, Punkt, a record that is not valid UTF-8, which
-  the decode then reports) through split_records"""
-  if not codebert and split is _rule_split and os.environ.get('LDDL_SPLIT_NATIVE', '1') != '0':
+  everything else (CodeBERT, Punkt, BART's whole lines -- the C splitter
+  cuts the id off --, a record that is not valid UTF-8, which the decode then
+  reports) through split_records"""
+  if not codebert and not whole_line and split is _rule_split and os.environ.get('LDDL_SPLIT_NATIVE', '1') != '0':
     from . import splitnative
     if splitnative.available():
       got = splitnative.split_raw(index.raws(idx))
       if got is not None:
         return got
-  return split_records(index.texts(idx), codebert, split)
+  return split_records(index.texts(idx), codebert, split, whole_line)
 
 
 def _nice_worker():
@@ -389,8 +391,10 @@ def _split_warm(_):
 
 def _split_worker(a, b):
   ts = time.perf_counter()
-  corpus, ids = split_chunk(_FE['index'], _FE['order'][a:b], _FE['codebert'], _FE['split'])
-  if _FE['codebert']:  # the writer's id column, built here in the worker, off the writer's path
+  corpus, ids = split_chunk(_FE['index'], _FE['order'][a:b], _FE['codebert'], _FE['split'], _FE.get('bart', False))
+  if _FE.get('bart', False):  # (BART keeps the id in the text: no id list travels back to the parent)
+    ids = None
+  elif _FE['codebert']:  # the writer's id column, built here in the worker, off the writer's path
     from .writer import str_array
     ids = str_array(ids)
   return corpus, ids, time.perf_counter() - ts
@@ -467,6 +471,15 @@ def plan_input(args, codebert=False, rank=0, world=1, gloo=None):
     if args.num_blocks is not None:
       bs = estimate_block_size(roots, args.num_blocks)  # readers.py:48-57 (the wikipedia ROOT, as the reference)
     n_part = count_partitions(files, bs)
+  idx = _record_index(files, delim, rank, world, gloo)
+  order = sample_order(len(idx), args.seed, args.sample_ratio)
+  pro = partition_by_size(idx.len[order], max(1, n_part))
+  return idx, order, pro
+
+
+def _record_index(files, delim, rank, world, gloo):
+  """the record index of the files; with several ranks each indexes every
+  world-th file and the shares are all-gathered (host, gloo)"""
   mine = set(range(rank, len(files), world))
   idx = RecordIndex.build(files, delim, file_ids=mine)
   if world > 1:
@@ -474,9 +487,7 @@ def plan_input(args, codebert=False, rank=0, world=1, gloo=None):
     parts = [None] * world
     dist.all_gather_object(parts, (idx.fid, idx.off, idx.len), group=gloo)
     idx = RecordIndex.merge(files, [RecordIndex(files, *p) for p in parts])
-  order = sample_order(len(idx), args.seed, args.sample_ratio)
-  pro = partition_by_size(idx.len[order], max(1, n_part))
-  return idx, order, pro
+  return idx
 
 
 def _dist_init(world):
@@ -770,6 +781,171 @@ def console_script(argv=None, codebert=False):
   print('Running the pipeline took {} s'.format(time.perf_counter() - tic))
 
 
+# ----------------------------------------------------------------- BART --
+def attach_bart_args(parser=None):
+  """The reference's BART flags (bart/pretrain.py:187-286) and
+  --sentence-splitter, which the other two sub-commands have too.
+  --short-seq-prob is accepted and unused, as in the reference;
+  --schedule / --local-* are accepted and ignored."""
+  p = parser or argparse.ArgumentParser('lddl_amd preprocessor for the BART pretraining task')
+  p.add_argument('--schedule', type=str, default='mpi', choices=['mpi', 'local'])
+  p.add_argument('--local-n-workers', type=int, default=os.cpu_count())
+  p.add_argument('--local-threads-per-worker', type=int, default=1)
+  p.add_argument('--wikipedia', type=str, default=None)
+  p.add_argument('--books', type=str, default=None)
+  p.add_argument('--common-crawl', type=str, default=None)
+  p.add_argument('--open-webtext', type=str, default=None)
+  p.add_argument('--sink', type=str, default=None, required=True)
+  p.add_argument('--output-format', type=str, default='parquet', choices=['parquet', 'txt'])
+  p.add_argument('--wikipedia-lang', type=str, default='en', choices=['en', 'zh'])
+  p.add_argument('--target-seq-length', type=int, default=128)
+  p.add_argument('--short-seq-prob', type=float, default=0.1, help='accepted and unused (bart/pretrain.py:47)')
+  p.add_argument('--block-size', type=lambda x: parse_str_of_num_bytes(x, return_str=False), default=None,
+                 metavar='n[KMG]')
+  p.add_argument('--num-blocks', type=int, default=None)
+  p.add_argument('--sentence-splitter', type=str, default='auto', choices=['auto', 'punkt', 'rules'])
+  return p
+
+
+def plan_bart_input(args, rank=0, world=1, gloo=None):
+  """(record index, record order, partition offsets) of the BART input: the
+  bags in the reference's order (bart/pretrain.py:57-80), every record kept
+  in input order (no sampling, no shuffle), partitions as for BERT."""
+  if args.num_blocks is not None and args.block_size is not None:
+    raise ValueError('Only one of num_blocks or blocksize needs to be set!')
+  roots = [args.wikipedia, args.books, args.common_crawl, args.open_webtext]
+  if not any(roots):
+    raise ValueError('at least one of --wikipedia, --books, --common-crawl and --open-webtext needs to be set')
+  srcs = [os.path.join(args.wikipedia, args.wikipedia_lang) if args.wikipedia else None] + roots[1:]
+  files = [f for s in srcs if s for f in find_files_under(s)]
+  bs = args.block_size
+  if args.num_blocks is not None:
+    bs = estimate_block_size(roots, args.num_blocks)  # bart/pretrain.py:50-56
+  n_part = count_partitions(files, bs)
+  idx = _record_index(files, None, rank, world, gloo)
+  order = np.arange(len(idx), dtype=np.int64)
+  return idx, order, partition_by_size(idx.len[order], max(1, n_part))
+
+
+BART_CHUNK_BYTES = 32 << 20  # raw bytes of partitions per trip to the GPU
+
+
+def bart_main(args):
+  """preprocess_bart_pretrain (bart/pretrain.py:155-184): returns (files
+  written by this rank, timings dict).  Host: the record index, the
+  partitions and the sentence split of this rank's records (whole lines: the
+  BART path keeps the id in the text), on forked workers ahead of the GPU;
+  GPU: word counts, chunk plan and the `sentences` column (lddl_amd/bart.py).
+  Rank r of a torch.distributed.run launch takes the contiguous partition
+  range r of world."""
+  import concurrent.futures
+  import multiprocessing
+  import torch
+  from . import bart, pipeline, writer
+  from .hostinfo import cpu_share
+  from .tokenizer import Tokenizer
+  rank = int(os.environ.get('RANK', 0))
+  world = int(os.environ.get('WORLD_SIZE', 1))
+  local = int(os.environ.get('LOCAL_RANK', 0))
+  t = {}
+  wall0 = t0 = time.perf_counter()
+  gloo = _dist_init(world)
+  split, how = sentence_splitter(args.sentence_splitter)
+  index, order, pro = plan_bart_input(args, rank, world, gloo)
+  n_part = len(pro) - 1
+  lo, hi = rank * n_part // world, (rank + 1) * n_part // world
+  t['host_read_s'] = time.perf_counter() - t0
+  sizes = index.len[order[pro[lo]:pro[hi]]]
+  cum = np.concatenate([[0], np.cumsum(sizes)])
+  part_end = cum[pro[lo + 1:hi + 1] - pro[lo]]
+  bounds, acc0 = [lo], 0
+  for p in range(lo, hi):
+    if part_end[p - lo] - acc0 >= BART_CHUNK_BYTES and p + 1 < hi:
+      bounds.append(p + 1)
+      acc0 = part_end[p - lo]
+  bounds.append(hi)
+  chunks = [(a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+  sink = os.path.abspath(os.path.expanduser(args.sink))
+  os.makedirs(sink, exist_ok=True)
+  # the encoder and the split workers fork before the GPU is touched, as in main()
+  enc = writer.ProcessEncoder() if args.output_format != 'txt' and os.environ.get('LDDL_ENCODE_PROCS', '1') != '0' \
+      else None
+  nw = min(cpu_share(), hi - lo) if hi - lo > 1 else 0
+  pool = None
+  try:
+    if nw > 0:
+      _FE.update(index=index, order=order, codebert=False, split=split, bart=True)
+      try:
+        pool = concurrent.futures.ProcessPoolExecutor(nw, mp_context=multiprocessing.get_context('fork'),
+                                                      initializer=_nice_worker)
+        list(pool.map(_split_warm, range(nw)))
+      finally:
+        _FE.clear()
+
+    def submit(c):
+      a, b = chunks[c]
+      if pool is not None:
+        return [pool.submit(_split_worker, int(pro[x]), int(pro[y]))
+                for x, y in chunk_pieces(part_end, lo, a, b, 2 * nw)]
+      ts = time.perf_counter()
+      corpus, ids = split_chunk(index, order[int(pro[a]):int(pro[b])], False, split, True)
+
+      class Done:
+        def result(self):
+          return corpus, ids, time.perf_counter() - ts
+      return [Done()]
+
+    futs = {c: submit(c) for c in range(min(2, len(chunks)))} if pool is not None else {}
+    t0 = time.perf_counter()
+    device = torch.device('cuda', local)
+    torch.cuda.set_device(device)
+    tok = Tokenizer(device=local)  # (the ctx of the C calls; the vocabulary is not read)
+    t['gpu_init_s'] = time.perf_counter() - t0
+    t.update(host_split_s=0.0, split_wait_s=0.0, gpu_s=0.0, write_s=0.0, chunks_out=0, split_workers=nw)
+    out, pending = [], []
+    for c, (a, b) in enumerate(chunks):
+      tw = time.perf_counter()
+      got = [f_.result() for f_ in (futs.pop(c) if c in futs else submit(c))]
+      t['split_wait_s'] += time.perf_counter() - tw
+      t['host_split_s'] += sum(g[2] for g in got)
+      if pool is not None and c + 2 < len(chunks):
+        futs[c + 2] = submit(c + 2)
+      t0 = time.perf_counter()
+      sh = pipeline.upload_pieces([g[0] for g in got], pro[a:b + 1] - pro[a], device)
+      res = bart.aggregate(sh, None, args.target_seq_length, tok)
+      torch.cuda.synchronize()
+      t['gpu_s'] += time.perf_counter() - t0
+      t0 = time.perf_counter()
+      if args.output_format == 'txt':
+        out += bart.write_bart_txt(res, sink, part_base=a)
+      else:
+        out += bart.write_bart_shards(res, sink, part_base=a, executor=enc, pending=pending)
+      t['write_s'] += time.perf_counter() - t0
+      t['chunks_out'] += res.n_chunks
+    t0 = time.perf_counter()
+    for f_ in pending:
+      f_.result()
+    t['drain_s'] = time.perf_counter() - t0
+  finally:
+    if pool is not None:
+      pool.shutdown(wait=True, cancel_futures=True)
+    if enc is not None:
+      enc.close()
+    index.close()
+  t['wall_s'] = time.perf_counter() - wall0
+  t.update(rank=rank, world=world, partitions=[lo, hi], documents=int(pro[hi] - pro[lo]), sentence_splitter=how,
+           n_partitions=n_part)
+  return out, t
+
+
+def bart_console_script(argv=None):
+  args = attach_bart_args().parse_args(argv)
+  tic = time.perf_counter()
+  files, t = bart_main(args)
+  print('rank %d: %d files, %s' % (t['rank'], len(files), {k: v for k, v in t.items() if k != 'rank'}))
+  print('Running the pipeline took {} s'.format(time.perf_counter() - tic))
+
+
 def codebert_console_script(argv=None):
   console_script(argv, codebert=True)
 
@@ -777,5 +953,7 @@ def codebert_console_script(argv=None):
 if __name__ == '__main__':
   if len(sys.argv) > 1 and sys.argv[1] == 'codebert':
     codebert_console_script(sys.argv[2:])
+  elif len(sys.argv) > 1 and sys.argv[1] == 'bart':
+    bart_console_script(sys.argv[2:])
   else:
     console_script()

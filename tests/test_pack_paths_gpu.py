@@ -4,7 +4,8 @@ register-resident and global-fill documents, the document table past its
 static LDS copy, >= 65536 kept sentences, dropped sentences / documents
 (slot != sentence index; spans and materialised rows), partitions of one and
 two documents, truncation across MT19937 twists, the seed edge values, and
-the masked instantiation on the dropped-sentence corpus."""
+the masked instantiation on every one of those corpora (the truncation draws
+and the masking draws share one MT19937 stream there)."""
 import functools
 import random
 
@@ -100,14 +101,15 @@ def corpus(name):
   return c, np.asarray(pdo, dtype=np.int64), oids, ontok
 
 
-def check(name, seq, dup, seed, bin_size=32, masking=False, spans=False):
+def check(name, seq, dup, seed, bin_size=32, masking=False, spans=False, ratio=MASK[0]):
   from lddl_amd import pipeline
   c, pdo, oids, ontok = corpus(name)
   res = pipeline.run_bert(c, target_seq_length=seq, bin_size=bin_size, seed=seed, duplicate_factor=dup,
-                          part_doc_off=pdo, check_host=True, masking=masking, spans=spans)
+                          part_doc_off=pdo, check_host=True, masking=masking, masked_lm_ratio=ratio, spans=spans)
   assert res.spans == spans
   assert np.array_equal(res.ntok_host, ontok)
-  exp = po.run_bert_shards(c, oids, ontok, pdo, seq, 0.1, dup, seed, bin_size, masking=MASK if masking else None)
+  exp = po.run_bert_shards(c, oids, ontok, pdo, seq, 0.1, dup, seed, bin_size,
+                           masking=(ratio,) + MASK[1:] if masking else None)
   pipeline.assert_same_pairs(res, exp)  # A, B, is_random_next, num_tokens, in the binned shuffled order
   nb = res.nbins
   bc = res.bin_count.cpu().numpy()
@@ -172,3 +174,25 @@ def test_seed_edges(gpu, seed):
 
 def test_masked_on_dropped_corpus(gpu):
   check('dropped', 128, 5, 4242, masking=True)
+
+
+@pytest.mark.parametrize('spans', [False, True])
+@pytest.mark.parametrize('name,seq,dup,ratio', [('mixed', 128, 5, 0.15), ('doctable', 128, 5, 0.15),
+                                                ('few', 128, 5, 0.15), ('long', 128, 5, 0.15),
+                                                ('mixed', 512, 5, 0.15), ('long', 512, 5, 0.15),
+                                                ('few', 128, 5, 1.0), ('long', 128, 5, 1.0)])
+def test_masked_on_branch_corpora(gpu, name, seq, dup, ratio, spans):
+  """the masked kernel on the corpora above: a slip in the draw accounting of
+  the truncation ('long': hundreds of steps per pair) or of the random-next
+  retries ('few') moves every later masking draw of the partition"""
+  _, exp = check(name, seq, dup, 4242, bin_size=seq // 4, masking=True, spans=spans, ratio=ratio)
+  assert all(r[4] for part in exp for r in part)  # words only: every row has a masked position
+  if ratio == 1.0:
+    assert all(len(r[4]) == r[3] - 3 for part in exp for r in part)
+
+
+@pytest.mark.parametrize('spans', [False, True])
+def test_masked_65536_kept_sentences(gpu, spans):
+  """'many' masked: 66 200 sentences in one partition, so one wave packs them
+  all (0.5 s on an MI355X, the oracle included)"""
+  check('many', 128, 1, 4242, masking=True, spans=spans)

@@ -38,6 +38,9 @@ static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
   return 0;
 }
 
+// the longest row m rounded up to a multiple of sequence_length_alignment (bert.py:94-97)
+static int64_t aligned_seq_len(int64_t m, int32_t seq_align) { return ((m - 1) / seq_align + 1) * seq_align; }
+
 extern "C" int lddl_collate_seq_len(lddl_ctx* c, const uint8_t* d_a, const int64_t* d_a_off, const uint8_t* d_b,
                                     const int64_t* d_b_off, int64_t n_rows, int32_t seq_align, int64_t* out_seq_len,
                                     void* stream) {
@@ -50,18 +53,14 @@ extern "C" int lddl_collate_seq_len(lddl_ctx* c, const uint8_t* d_a, const int64
   CollateParams P{};
   int rc;
   if ((rc = collate_vocab(c, &P.V))) return rc;
-  P.a = d_a;
-  P.a_off = d_a_off;
-  P.b = d_b;
-  P.b_off = d_b_off;
+  P.C = StringColumns{d_a, d_a_off, d_b, d_b_off, nullptr, nullptr, nullptr, nullptr};
   P.n_rows = n_rows;
   if ((rc = ws_get(c, CW_SHARED_META, 1, &P.max_len))) return rc;
   HIP_TRY(hipMemsetAsync(P.max_len, 0, 4, st));
   HIP_TRY(launch_collate_len(P, c->n_cu, st));
   HIP_TRY(fetch_word(c, HW_MAX_LEN, P.max_len, 4, st));
   HIP_TRY(hipStreamSynchronize(st));
-  const int64_t m = *(const int32_t*)&c->h_tot[HW_MAX_LEN];
-  *out_seq_len = ((m - 1) / seq_align + 1) * seq_align;
+  *out_seq_len = aligned_seq_len(*(const int32_t*)&c->h_tot[HW_MAX_LEN], seq_align);
   return 0;
 }
 
@@ -90,15 +89,8 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
   CollateParams P{};
   int rc;
   if ((rc = collate_vocab(c, &P.V))) return rc;
-  P.a = d_a;
-  P.a_off = d_a_off;
-  P.b = d_b;
-  P.b_off = d_b_off;
+  P.C = StringColumns{d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off};
   P.is_random_next = d_is_random_next;
-  P.pos = d_pos;
-  P.pos_off = d_pos_off;
-  P.lab = d_lab;
-  P.lab_off = d_lab_off;
   P.n_rows = n_rows;
   P.seq_len = (int32_t)seq_len;
   P.mode = mode;
@@ -214,8 +206,7 @@ extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, co
   HIP_TRY(fetch_word(c, HW_MAX_LEN, P.max_len, 4, st));
   if ((rc = read_err(c, P.err, st, &e))) return rc;
   if (e) return collate_rows_error(e, 0);
-  const int64_t m = *(const int32_t*)&c->h_tot[HW_MAX_LEN];
-  *out_seq_len = ((m - 1) / seq_align + 1) * seq_align;
+  *out_seq_len = aligned_seq_len(*(const int32_t*)&c->h_tot[HW_MAX_LEN], seq_align);
   return 0;
 }
 
@@ -317,7 +308,7 @@ extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0,
   CollateUnpaddedParams P{};
   collate_rows_index(&P.R, d_len0, d_len1, d_rows, row0, n_rows, n_total);
   P.cu_seqlens = d_cu_seqlens;
-  P.n_chunks = collate_cu_chunks(n_rows);
+  P.n_chunks = collate_chunks(n_rows);
   int rc;
   uint32_t e;
   int64_t* meta;  // total, then max_len in the low half of meta[1]: the layout of HW_CU_TOTAL, HW_MAX_LEN
@@ -400,14 +391,7 @@ static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, c
   RowsFromStringsParams P{};
   int rc;
   if (fill && (rc = collate_vocab(c, &P.V))) return rc;
-  P.a = d_a;
-  P.a_off = d_a_off;
-  P.b = d_b;
-  P.b_off = d_b_off;
-  P.pos = d_pos;
-  P.pos_off = d_pos_off;
-  P.lab = d_lab;
-  P.lab_off = d_lab_off;
+  P.C = StringColumns{d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off};
   P.is_random_next = d_is_random_next;
   P.n_rows = n_rows;
   P.len0 = d_len0;
@@ -431,7 +415,7 @@ static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, c
     if ((rc = read_err(c, P.err, st, &e))) return rc;
     return e ? rows_from_strings_error(e) : 0;
   }
-  P.n_chunks = rows_from_strings_chunks(n_rows);
+  P.n_chunks = collate_chunks(n_rows);
   if ((rc = ws_get(c, CW_SHARED_META, 3, &P.totals)) || (rc = ws_get(c, CW_SHARED_BSUM, (size_t)P.n_chunks, &P.chunk_sum)))
     return rc;
   HIP_TRY(hipMemsetAsync(P.chunk_sum, 0, (size_t)P.n_chunks * sizeof(*P.chunk_sum), st));

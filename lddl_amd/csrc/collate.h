@@ -20,17 +20,23 @@ struct CollateVocab {
   int32_t n_random;  // len(tokenizer): randint bound of the 10 % random words
 };
 
-struct CollateParams {
-  CollateVocab V;
+// The string columns of parquet rows as (bytes, offsets [n_rows + 1]) each.
+// pos .. lab_off are NULL without static masking.
+struct StringColumns {
   const uint8_t* a;
-  const int64_t* a_off;  // [n_rows + 1]
+  const int64_t* a_off;
   const uint8_t* b;
   const int64_t* b_off;
-  const uint8_t* is_random_next;  // [n_rows] (bool bytes)
-  const uint8_t* pos;             // static masking: np.save bytes per row
+  const uint8_t* pos;  // masked_lm_positions: np.save bytes per row
   const int64_t* pos_off;
-  const uint8_t* lab;             // static masking: space-joined label tokens
+  const uint8_t* lab;  // masked_lm_labels: space-joined label tokens
   const int64_t* lab_off;
+};
+
+struct CollateParams {
+  CollateVocab V;
+  StringColumns C;
+  const uint8_t* is_random_next;  // [n_rows] (bool bytes)
   int64_t n_rows;
   int32_t seq_len;   // output columns (aligned)
   int32_t mode;      // COLLATE_*
@@ -97,23 +103,16 @@ struct CollateUnpaddedParams {
   int64_t total;           // fill pass: the capacity of the token outputs
   uint32_t* chunk_sum;     // offsets pass: [n_chunks] tokens of each chunk of rows
   int64_t* total_out;      // offsets pass: [1] tokens of the batch
-  int64_t n_chunks;        // collate_cu_chunks(n_rows)
+  int64_t n_chunks;        // collate_chunks(n_rows)
 };
 
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
-// lddl_masked_lm_spans leave behind.  pos .. lab_off are NULL without static
-// masking, and so are mlm_off .. mlm_token then.
+// lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
+// static masking.
 struct RowsFromStringsParams {
   CollateVocab V;         // fill pass only
-  const uint8_t* a;
-  const int64_t* a_off;   // [n_rows + 1]
-  const uint8_t* b;
-  const int64_t* b_off;
-  const uint8_t* pos;     // np.save bytes per row
-  const int64_t* pos_off;
-  const uint8_t* lab;     // space-joined label tokens
-  const int64_t* lab_off;
+  StringColumns C;
   const uint8_t* is_random_next;  // [n_rows] (bool bytes; fill pass)
   int64_t n_rows;
   uint16_t* len0;         // [n_rows] written by the length pass, checked by the fill pass
@@ -131,7 +130,7 @@ struct RowsFromStringsParams {
   int64_t mlm_cap;
   unsigned long long* chunk_sum;  // length pass: [n_chunks] ids (low half) | masked entries (high half) of each chunk of rows
   int64_t* totals;        // length pass: [3] ids, row tokens and masked entries of the table
-  int64_t n_chunks;       // rows_from_strings_chunks(n_rows)
+  int64_t n_chunks;       // collate_chunks(n_rows)
   uint32_t* err;          // [1] as CollateParams::err
 };
 
@@ -151,15 +150,17 @@ enum : uint32_t {
 
 constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
 
+// rows per block of the offsets scans (collate_row.h), 8 per thread, and the blocks that n_rows take
+constexpr int kChunk = 2048;
+inline int64_t collate_chunks(int64_t n_rows) { return (n_rows + kChunk - 1) / kChunk; }
+
 uint32_t collate_hash_host(const uint8_t* p, int n);
 hipError_t launch_collate_rows_len(const CollateRowsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_rows(const CollateRowsParams& P, int32_t mode, int n_cu, hipStream_t s);
-int64_t collate_cu_chunks(int64_t n_rows);
 hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, hipStream_t s);
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
-int64_t rows_from_strings_chunks(int64_t n_rows);
 hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_rows_from_strings(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);

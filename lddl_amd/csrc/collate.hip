@@ -24,11 +24,13 @@
 // and probes the L2-resident vocab table.  Ids land in a per-wave LDS row;
 // pass 2 writes the five int64 columns coalesced (lane = column).  The bound
 // is the int64 output stream (40 B per column) against a few bytes of input.
+// What column j of a row holds is RowLayout's (collate_row.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "collate.h"
 #include "collate_dev.h"
+#include "collate_row.h"
 #include "wave.h"
 
 namespace lddl {
@@ -45,8 +47,8 @@ __global__ __launch_bounds__(256) void collate_len_kernel(CollateParams P) {
   const int64_t nw = (int64_t)gridDim.x * 4;
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < P.n_rows; r += nw) {
     auto none = [](int32_t, int64_t) {};
-    const int32_t na = scan_tokens(P.a, P.a_off[r], P.a_off[r + 1], none);
-    const int32_t nb = scan_tokens(P.b, P.b_off[r], P.b_off[r + 1], none);
+    const int32_t na = scan_tokens(P.C.a, P.C.a_off[r], P.C.a_off[r + 1], none);
+    const int32_t nb = scan_tokens(P.C.b, P.C.b_off[r], P.C.b_off[r + 1], none);
     if (lane == 0) atomicMax(P.max_len, na + nb + 3);
   }
 }
@@ -62,19 +64,20 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
   const int64_t nw = (int64_t)gridDim.x * 4;
   for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < P.n_rows; r += nw) {
     const CollateVocab& V = P.V;
+    const StringColumns& C = P.C;
     // pass 1: token ids into the LDS row (positions >= L are dropped and flagged)
-    int32_t na = scan_tokens(P.a, P.a_off[r], P.a_off[r + 1], [&](int32_t k, int64_t i) {
+    int32_t na = scan_tokens(C.a, C.a_off[r], C.a_off[r + 1], [&](int32_t k, int64_t i) {
       int64_t end;
-      const int32_t id = vocab_lookup(V, P.a, i, P.a_off[r + 1], end);
+      const int32_t id = vocab_lookup(V, C.a, i, C.a_off[r + 1], end);
       if (1 + k < L) ids[1 + k] = id;
     });
-    int32_t nb = scan_tokens(P.b, P.b_off[r], P.b_off[r + 1], [&](int32_t k, int64_t i) {
+    int32_t nb = scan_tokens(C.b, C.b_off[r], C.b_off[r + 1], [&](int32_t k, int64_t i) {
       int64_t end;
-      const int32_t id = vocab_lookup(V, P.b, i, P.b_off[r + 1], end);
+      const int32_t id = vocab_lookup(V, C.b, i, C.b_off[r + 1], end);
       if (na + 2 + k < L) ids[na + 2 + k] = id;
     });
-    const int32_t n = na + nb + 3;
-    if (n > L) {
+    const RowLayout S{na, na + nb + 3};
+    if (S.n > L) {
       if (lane == 0) set_err(P.err, CERR_LONG, r);
       continue;
     }
@@ -83,18 +86,18 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
       // positions: np.save v1.x bytes of a 1-D '<u2' array
       const uint8_t* d;
       int64_t np64;
-      if (!npy_u16_payload(P.pos + P.pos_off[r], P.pos_off[r + 1] - P.pos_off[r], d, np64)) {
+      if (!npy_u16_payload(C.pos + C.pos_off[r], C.pos_off[r + 1] - C.pos_off[r], d, np64)) {
         if (lane == 0) set_err(P.err, CERR_NPY, r);
         continue;
       }
       const int32_t np = (int32_t)np64;
       __builtin_amdgcn_wave_barrier();
       // labels[positions[k]] = id(masked_lm_labels.split()[k])
-      const int64_t l0 = P.lab_off[r], l1 = P.lab_off[r + 1];
+      const int64_t l0 = C.lab_off[r], l1 = C.lab_off[r + 1];
       bool bad = false;
-      const int32_t nl = scan_tokens(P.lab, l0, l1, [&](int32_t k, int64_t i) {
+      const int32_t nl = scan_tokens(C.lab, l0, l1, [&](int32_t k, int64_t i) {
         int64_t end;
-        const int32_t id = vocab_lookup(V, P.lab, i, l1, end);
+        const int32_t id = vocab_lookup(V, C.lab, i, l1, end);
         if (k < np) {
           const int32_t pos = (int32_t)d[2 * k] | ((int32_t)d[2 * k + 1] << 8);
           if (pos >= L) bad = true;
@@ -117,20 +120,18 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
     int64_t* o_am = P.attention_mask + r * (int64_t)L;
     int64_t* o_lab = P.labels + r * (int64_t)L;
     for (int32_t j = lane; j < L; j += 64) {
-      int64_t id;
-      if (j == 0) id = V.cls;
-      else if (j == na + 1 || j == n - 1) id = V.sep;
-      else if (j < n) id = ids[j];
-      else id = 0;
-      const bool special = j == 0 || j == na + 1 || j >= n - 1;
+      const bool pad = S.pad(j);
+      const bool special = pad || S.special(j);
+      int64_t id = 0;
+      if (!pad) id = S.base_id(j, V.cls, V.sep, [&](int32_t c) { return ids[c]; });
       int64_t l;
       if (P.mode == COLLATE_SPECIAL_MASK) l = special ? 1 : 0;
       else if (P.mode == COLLATE_STATIC) l = lab[j] < 0 ? P.ignore_index : (int64_t)lab[j];
       else id = mask_one(id, special, r, j, P.seed, P.counter, P.mlm_probability, V.mask_id, V.n_random,
                          P.ignore_index, l);
       o_ids[j] = id;
-      o_tt[j] = (j >= na + 2 && j < n) ? 1 : 0;
-      o_am[j] = j < n ? 1 : 0;
+      o_tt[j] = S.token_type(j);
+      o_am[j] = pad ? 0 : 1;
       o_lab[j] = l;
     }
     if (lane == 0) P.next_sentence_labels[r] = P.is_random_next[r] ? 1 : 0;
@@ -147,13 +148,6 @@ __global__ __launch_bounds__(256) void mask_tokens_kernel(MaskParams M) {
                            M.n_random, M.ignore_index, l);
     M.labels[e] = l;
   }
-}
-
-static int grid_rows(int64_t n_rows, int n_cu) {
-  int64_t g = (n_rows + 3) / 4;
-  const int64_t cap = (int64_t)n_cu * 8;
-  if (g > cap) g = cap;
-  return (int)(g < 1 ? 1 : g);
 }
 
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s) {

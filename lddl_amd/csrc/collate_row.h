@@ -1,0 +1,218 @@
+// What the collate kernels share about a `[CLS] A [SEP] B [SEP]` row, written
+// once: the row layout (collate.hip, collate_rows.hip, collate_unpadded.hip,
+// rows_from_strings.hip), opening a batch row of a row table and labelling its
+// columns by mode (collate_rows.hip, collate_unpadded.hip), the second level
+// of the chunked offsets scans (collate_unpadded.hip, rows_from_strings.hip)
+// and the launch helpers.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <type_traits>
+
+#include "collate.h"
+#include "collate_dev.h"
+#include "wave.h"
+
+namespace lddl {
+
+// ------------------------------------------------------------ the row layout --
+// A row of a = len(A) and b = len(B) tokens holds n = a + b + 3 columns:
+//   0 [CLS] | [1, a] A | a + 1 [SEP] | [a + 2, n - 2] B | n - 1 [SEP] | [n, ..) padding
+// (lddl/torch/bert.py:69-153).  token_type_ids is 1 on B and its [SEP]; the
+// special_tokens_mask is 1 on the three special tokens and, in a padded batch,
+// on the padding.
+struct RowLayout {
+  int32_t a, n;
+  __device__ __forceinline__ bool is_cls(int32_t j) const { return j == 0; }
+  __device__ __forceinline__ bool is_sep(int32_t j) const { return j == a + 1 || j == n - 1; }
+  __device__ __forceinline__ bool special(int32_t j) const { return is_cls(j) || is_sep(j); }
+  __device__ __forceinline__ bool seg0(int32_t j) const { return j >= 1 && j <= a; }
+  __device__ __forceinline__ bool seg1(int32_t j) const { return j >= a + 2 && j < n - 1; }
+  __device__ __forceinline__ bool pad(int32_t j) const { return j >= n; }
+  __device__ __forceinline__ int32_t token_type(int32_t j) const { return (j >= a + 2 && j < n) ? 1 : 0; }
+  // the id the row shows at column j < n, before any masking: at(j) is asked
+  // for the columns of the two segments only
+  template <class At>
+  __device__ __forceinline__ int32_t base_id(int32_t j, int32_t cls, int32_t sep, At at) const {
+    if (is_cls(j)) return cls;
+    if (is_sep(j)) return sep;
+    return at(j);
+  }
+};
+
+// ------------------------------------------------- a batch row of a row table --
+// the pack row of batch row r (rows NULL: row0 + r), or -1 when out of range
+__device__ __forceinline__ int64_t pack_row(const CollateRowsParams& P, int64_t r) {
+  const int64_t g = P.rows ? P.rows[r] : P.row0 + r;
+  return (g < 0 || g >= P.n_total) ? -1 : g;
+}
+
+// n of pack row g
+__device__ __forceinline__ uint32_t row_tokens(const CollateRowsParams& P, int64_t g) {
+  return (uint32_t)P.len0[g] + (uint32_t)P.len1[g] + 3u;
+}
+
+struct OpenRow {
+  int64_t g;           // the pack row
+  uint32_t flags;
+  RowLayout L;
+  const uint16_t* s0;  // ids + src0 - 1: column j of segment 0 is s0[j]
+  const uint16_t* s1;  // ids + src1 - (a + 2)
+};
+
+// Opens batch row r whose n may be `bound` at most: 0 and the row, or the error
+// code to set.  Nothing is loaded through a row index before it is
+// range-checked; the order of the checks decides which code a row with several
+// faults reports.
+__device__ __forceinline__ uint32_t open_row(const CollateRowsParams& P, int64_t r, int32_t bound, OpenRow& o) {
+  o.g = pack_row(P, r);
+  if (o.g < 0) return CERR_ROW_INDEX;
+  o.flags = P.flags[o.g];
+  if (!(o.flags & 2u)) return CERR_NO_SEP;  // a CodeBERT row without docstring: no [SEP] after segment 0
+  o.L.a = P.len0[o.g];
+  o.L.n = o.L.a + (int32_t)P.len1[o.g] + 3;
+  if (o.L.n > bound) return CERR_LONG;
+  o.s0 = P.ids + P.src0[o.g] - 1;
+  o.s1 = P.ids + P.src1[o.g] - (o.L.a + 2);
+  return 0;
+}
+
+constexpr uint32_t kNoMask = 0xFFFFFFFFu;
+
+// COLLATE_STATIC: label | token << 16 of pack row g's masked positions into the
+// first `bound` words of the wave's LDS row, kNoMask elsewhere.  False when a
+// position is >= bound (nothing is stored for it).
+__device__ __forceinline__ bool stage_static_masks(const CollateRowsParams& P, int64_t g, int32_t bound,
+                                                   uint32_t* mlm) {
+  const int lane = threadIdx.x & 63;
+  __builtin_amdgcn_wave_barrier();  // the previous row's reads are done
+  for (int32_t j = lane; j < bound; j += 64) mlm[j] = kNoMask;
+  __builtin_amdgcn_wave_barrier();
+  bool bad = false;
+  const int64_t k1 = P.mlm_off[g + 1];
+  for (int64_t k = P.mlm_off[g] + lane; k < k1; k += 64) {
+    const int32_t pos = P.mlm_pos[k];
+    if (pos >= bound) bad = true;
+    else mlm[pos] = (uint32_t)P.mlm_label[k] | ((uint32_t)P.mlm_token[k] << 16);
+  }
+  const bool ok = !__ballot(bad);
+  __builtin_amdgcn_wave_barrier();
+  return ok;
+}
+
+struct RowColumn {
+  int64_t id, tt, lab;
+};
+
+// Column j of batch row r, labelled by MODE: 0 the special_tokens_mask; 1 the
+// staged static masks (input_ids[pos] = mlm_token, labels[pos] = mlm_label,
+// ignore_index elsewhere); 2 mask_one with row = r.  pad: j is a pad column of
+// a padded batch (id 0, special); without padding j < n and pad is false.
+template <int MODE>
+__device__ __forceinline__ RowColumn row_column(const CollateRowsParams& P, const OpenRow& R, const uint32_t* mlm,
+                                                int64_t r, int32_t j, bool pad) {
+  RowColumn o;
+  const bool special = pad || R.L.special(j);
+  int64_t id = 0;
+  if (!pad) id = R.L.base_id(j, P.cls, P.sep, [&](int32_t c) { return (int32_t)(c <= R.L.a ? R.s0[c] : R.s1[c]); });
+  if (MODE == COLLATE_SPECIAL_MASK) {
+    o.lab = special ? 1 : 0;
+  } else if (MODE == COLLATE_STATIC) {
+    const uint32_t m = mlm[j];
+    o.lab = m == kNoMask ? P.ignore_index : (int64_t)(m & 0xFFFFu);
+    if (m != kNoMask) id = (int64_t)(m >> 16);
+  } else {
+    id = mask_one(id, special, r, j, P.seed, P.counter, P.mlm_probability, P.mask_id, P.n_random, P.ignore_index,
+                  o.lab);
+  }
+  o.id = id;
+  o.tt = R.L.token_type(j);
+  return o;
+}
+
+// ------------------------------------------------ the chunked offsets scan --
+// An exclusive scan of N per-row quantities over any number of rows, in two
+// levels.  Level one is each caller's own: chunk c's sums of its kChunk rows
+// (a chunk's sum fits 32 bits: kChunk * (2 * 65535 + 3) < 2^29).  Level two is
+// one block of 256 threads per chunk: chunk_scan_bases adds the chunk sums in
+// front of the block (base) and all of them (total), in 64 bits; then the
+// block walks its chunk 256 rows at a time and chunk_scan_step gives every
+// thread the sum up to and including its row.  One __syncthreads per step:
+// the steps alternate between the two halves of `wave`.
+template <int N>
+struct ChunkScanLds {
+  unsigned long long base[N], total[N];
+  uint32_t wave[2][N][4];
+};
+
+// sums(c, q): q[0 .. N) = the sums of chunk c.  Ends with a __syncthreads:
+// S.base and S.total are final for every thread.
+template <int N, class Sums>
+__device__ __forceinline__ void chunk_scan_bases(ChunkScanLds<N>& S, int64_t n_chunks, Sums sums) {
+  const int tid = threadIdx.x;
+  if (tid < N) S.base[tid] = S.total[tid] = 0;
+  __syncthreads();
+  unsigned long long below[N] = {}, all[N] = {};
+  for (int64_t c = tid; c < n_chunks; c += 256) {
+    unsigned long long q[N];
+    sums(c, q);
+#pragma unroll
+    for (int t = 0; t < N; ++t) {
+      all[t] += q[t];
+      if (c < (int64_t)blockIdx.x) below[t] += q[t];
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    if (below[t]) atomicAdd(&S.base[t], below[t]);
+    if (all[t]) atomicAdd(&S.total[t], all[t]);
+  }
+  __syncthreads();
+}
+
+// step `it` of the block's chunk: v = this thread's row (0 behind the last
+// row); end[t] = the sum of quantity t over rows [0, this row]; carry starts
+// at S.base and moves on by the step's 256 rows
+template <int N>
+__device__ __forceinline__ void chunk_scan_step(ChunkScanLds<N>& S, int it, const uint32_t (&v)[N], int64_t (&carry)[N],
+                                                int64_t (&end)[N]) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  uint32_t incl[N];
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    incl[t] = wave_incl_add(v[t]);
+    if (lane == 63) S.wave[it & 1][t][w] = incl[t];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < N; ++t) {
+    uint32_t before = 0, step = 0;
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t x = S.wave[it & 1][t][k];
+      step += x;
+      if (k < w) before += x;
+    }
+    end[t] = carry[t] + before + incl[t];
+    carry[t] += step;
+  }
+}
+
+// ------------------------------------------------------------------- launches --
+// one wave per row, four rows per block, at most eight blocks per CU
+inline int grid_rows(int64_t n_rows, int n_cu) {
+  int64_t g = (n_rows + 3) / 4;
+  const int64_t cap = (int64_t)n_cu * 8;
+  if (g > cap) g = cap;
+  return (int)(g < 1 ? 1 : g);
+}
+
+// f(std::integral_constant<int, MODE>) for the kernels that take the mode as a template constant
+template <class F>
+inline void dispatch_mode(int32_t mode, F f) {
+  if (mode == COLLATE_SPECIAL_MASK) f(std::integral_constant<int, COLLATE_SPECIAL_MASK>{});
+  else if (mode == COLLATE_STATIC) f(std::integral_constant<int, COLLATE_STATIC>{});
+  else f(std::integral_constant<int, COLLATE_DYNAMIC>{});
+}
+
+}  // namespace lddl

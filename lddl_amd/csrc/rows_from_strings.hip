@@ -27,10 +27,10 @@
 // (np.save header, label count = position count, every position < n) and adds
 // the row to its chunk's sums (one 64-bit atomic per row: ids in the low
 // half, positions in the high half; the row tokens of a chunk are its ids + 3
-// per row).  rows_scan_kernel is collate_unpadded.hip's second level: a block
-// adds the chunk sums in front of it and scans its chunk of kChunk rows, in
-// 64 bits across chunks.  k_r travels from the first kernel to the second in
-// mlm_off[r + 1], which the scan then overwrites with the sum.
+// per row).  rows_scan_kernel is the second level of collate_row.h's chunked
+// scan over two quantities, ids and positions.  k_r travels from the first
+// kernel to the second in mlm_off[r + 1], which the scan then overwrites with
+// the sum.
 //
 // Fill pass: rows_fill_kernel does not take len / src / mlm_off on trust: a wave
 // counts its row's tokens again first and refuses (CERR_ROW_COUNTS) a row whose
@@ -42,18 +42,19 @@
 // there: an altered src0 that lies inside the capacity is taken, also on top of
 // another row's span (the running sum is the scan's, not a row's, to know).
 // Then it scans again with the lookups.  mlm_token reads the ids the wave has
-// just stored (after a fence and a wave barrier).
+// just stored (after a fence and a wave barrier), at the column RowLayout
+// (collate_row.h) gives the position.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "collate.h"
 #include "collate_dev.h"
+#include "collate_row.h"
 #include "wave.h"
 
 namespace lddl {
 namespace {
 
-constexpr int kChunk = 2048;         // rows per block of the scan: 8 per thread
 constexpr int64_t kMaxSeg = 65535;   // len0 / len1 are u16
 constexpr int64_t kMaxMask = 2 * kMaxSeg + 3;  // positions of a row: at most its tokens
 // a chunk's sums fit 32 bits each: kChunk * 2 * kMaxSeg and kChunk * kMaxMask < 2^29
@@ -67,9 +68,10 @@ __device__ __forceinline__ int32_t count_tokens(const uint8_t* p, int64_t s, int
 __device__ __forceinline__ uint32_t static_columns(const RowsFromStringsParams& P, int64_t r, int32_t n,
                                                    const uint8_t*& d, int64_t& np) {
   const int lane = threadIdx.x & 63;
-  if (!npy_u16_payload(P.pos + P.pos_off[r], P.pos_off[r + 1] - P.pos_off[r], d, np)) return CERR_NPY;
+  const StringColumns& C = P.C;
+  if (!npy_u16_payload(C.pos + C.pos_off[r], C.pos_off[r + 1] - C.pos_off[r], d, np)) return CERR_NPY;
   if (np > kMaxMask) return CERR_NMASK;
-  if ((int64_t)count_tokens(P.lab, P.lab_off[r], P.lab_off[r + 1]) != np) return CERR_NLAB;
+  if ((int64_t)count_tokens(C.lab, C.lab_off[r], C.lab_off[r + 1]) != np) return CERR_NLAB;
   bool bad = false;
   for (int32_t j = lane; j < (int32_t)np; j += 64) {
     const int32_t pos = (int32_t)d[2 * j] | ((int32_t)d[2 * j + 1] << 8);
@@ -84,11 +86,11 @@ __global__ __launch_bounds__(256) void rows_len_kernel(RowsFromStringsParams P) 
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * 4;
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < P.n_rows; r += nw) {
-    int32_t na = count_tokens(P.a, P.a_off[r], P.a_off[r + 1]);
-    int32_t nb = count_tokens(P.b, P.b_off[r], P.b_off[r + 1]);
+    int32_t na = count_tokens(P.C.a, P.C.a_off[r], P.C.a_off[r + 1]);
+    int32_t nb = count_tokens(P.C.b, P.C.b_off[r], P.C.b_off[r + 1]);
     uint32_t code = (na > kMaxSeg || nb > kMaxSeg) ? (uint32_t)CERR_LONG : 0u;
     int64_t np = 0;
-    if (P.pos && !code) {
+    if (P.C.pos && !code) {
       const uint8_t* d;
       code = static_columns(P, r, na + nb + 3, d, np);
     }
@@ -104,73 +106,46 @@ __global__ __launch_bounds__(256) void rows_len_kernel(RowsFromStringsParams P) 
 }
 
 __global__ __launch_bounds__(256) void rows_scan_kernel(RowsFromStringsParams P) {
-  __shared__ unsigned long long s_base[2], s_total[2];
-  __shared__ uint32_t s_wave[2][2][4];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  if (tid < 2) s_base[tid] = s_total[tid] = 0;
-  __syncthreads();
-  unsigned long long below[2] = {0, 0}, all[2] = {0, 0};
-  for (int64_t c = tid; c < P.n_chunks; c += 256) {
+  __shared__ ChunkScanLds<2> S;
+  chunk_scan_bases(S, P.n_chunks, [&](int64_t c, unsigned long long (&q)[2]) {
     const unsigned long long v = P.chunk_sum[c];
-    const unsigned long long q[2] = {v & 0xFFFFFFFFull, v >> 32};
-    for (int t = 0; t < 2; ++t) {
-      all[t] += q[t];
-      if (c < (int64_t)blockIdx.x) below[t] += q[t];
-    }
-  }
-  for (int t = 0; t < 2; ++t) {
-    if (below[t]) atomicAdd(&s_base[t], below[t]);
-    if (all[t]) atomicAdd(&s_total[t], all[t]);
-  }
-  __syncthreads();
-  if (blockIdx.x == 0 && tid == 0) {
-    P.totals[0] = (int64_t)s_total[0];
-    P.totals[1] = (int64_t)s_total[0] + 3 * P.n_rows;
-    P.totals[2] = (int64_t)s_total[1];
+    q[0] = v & 0xFFFFFFFFull;
+    q[1] = v >> 32;
+  });
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    P.totals[0] = (int64_t)S.total[0];
+    P.totals[1] = (int64_t)S.total[0] + 3 * P.n_rows;
+    P.totals[2] = (int64_t)S.total[1];
     if (P.tok_off) P.tok_off[0] = 0;
     if (P.mlm_off) P.mlm_off[0] = 0;
   }
   const int64_t lo = (int64_t)blockIdx.x * kChunk;
-  int64_t carry_ids = (int64_t)s_base[0], carry_k = (int64_t)s_base[1];
+  int64_t carry[2] = {(int64_t)S.base[0], (int64_t)S.base[1]}, end[2];  // ids, positions
   for (int it = 0; it < kChunk / 256; ++it) {
-    const int64_t r = lo + it * 256 + tid;
+    const int64_t r = lo + it * 256 + threadIdx.x;
     uint32_t a = 0, b = 0, k = 0;
     if (r < P.n_rows) {
       a = P.len0[r];
       b = P.len1[r];
       if (P.mlm_off) k = (uint32_t)P.mlm_off[r + 1];  // rows_len_kernel's k_r <= kMaxMask
     }
-    const uint32_t incl_ids = wave_incl_add(a + b);
-    const uint32_t incl_k = wave_incl_add(k);
-    if (lane == 63) {
-      s_wave[it & 1][0][w] = incl_ids;
-      s_wave[it & 1][1][w] = incl_k;
-    }
-    __syncthreads();  // one per step: the steps alternate between the two halves of s_wave
-    uint32_t before[2] = {0, 0}, step[2] = {0, 0};
-    for (int t = 0; t < 2; ++t)
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t v = s_wave[it & 1][t][q];
-        step[t] += v;
-        if (q < w) before[t] += v;
-      }
+    const uint32_t v[2] = {a + b, k};
+    chunk_scan_step(S, it, v, carry, end);
     if (r < P.n_rows) {
-      const int64_t end = carry_ids + before[0] + incl_ids;  // the ids of rows [0, r]
-      P.src0[r] = end - (a + b);
-      P.src1[r] = end - b;
-      if (P.tok_off) P.tok_off[r + 1] = end + 3 * (r + 1);
-      if (P.mlm_off) P.mlm_off[r + 1] = carry_k + before[1] + incl_k;
+      P.src0[r] = end[0] - (a + b);  // end[0]: the ids of rows [0, r]
+      P.src1[r] = end[0] - b;
+      if (P.tok_off) P.tok_off[r + 1] = end[0] + 3 * (r + 1);
+      if (P.mlm_off) P.mlm_off[r + 1] = end[1];
     }
-    carry_ids += step[0];
-    carry_k += step[1];
   }
 }
 
 __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * 4;
-  const bool stat = P.pos != nullptr;
+  const bool stat = P.C.pos != nullptr;
   const CollateVocab& V = P.V;
+  const StringColumns& C = P.C;
   {
     // a table that ends beyond a capacity: every wave leaves, nothing is written
     const int64_t last = P.n_rows - 1;
@@ -182,20 +157,20 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
     }
   }
   for (int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); r < P.n_rows; r += nw) {
-    const int64_t a0 = P.a_off[r], a1 = P.a_off[r + 1], b0 = P.b_off[r], b1 = P.b_off[r + 1];
+    const int64_t a0 = C.a_off[r], a1 = C.a_off[r + 1], b0 = C.b_off[r], b1 = C.b_off[r + 1];
     // the row's counts again, and its spans against them and the capacities
-    const int32_t na = count_tokens(P.a, a0, a1);
-    const int32_t nb = count_tokens(P.b, b0, b1);
+    const int32_t na = count_tokens(C.a, a0, a1);
+    const int32_t nb = count_tokens(C.b, b0, b1);
     const int64_t s0 = P.src0[r], s1 = P.src1[r];
     uint32_t code = 0;
     // s0 is bounded before anything is added to it
     if (na != (int32_t)P.len0[r] || nb != (int32_t)P.len1[r] || s0 < 0 || s0 > P.ids_cap - na - nb || s1 != s0 + na)
       code = CERR_ROW_COUNTS;
-    const int32_t n = na + nb + 3;
+    const RowLayout S{na, na + nb + 3};
     const uint8_t* d = nullptr;
     int64_t np = 0, m0 = 0;
     if (stat && !code) {
-      code = static_columns(P, r, n, d, np);
+      code = static_columns(P, r, S.n, d, np);
       m0 = P.mlm_off[r];
       if (!code && (m0 < 0 || m0 > P.mlm_cap - np || P.mlm_off[r + 1] != m0 + np)) code = CERR_ROW_COUNTS;
     }
@@ -205,14 +180,14 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
     }
     uint16_t* oa = P.ids + s0;
     uint16_t* ob = P.ids + s1;
-    scan_tokens(P.a, a0, a1, [&](int32_t k, int64_t i) {
+    scan_tokens(C.a, a0, a1, [&](int32_t k, int64_t i) {
       int64_t end;
-      const int32_t id = vocab_lookup(V, P.a, i, a1, end);
+      const int32_t id = vocab_lookup(V, C.a, i, a1, end);
       if (k < na) oa[k] = (uint16_t)id;
     });
-    scan_tokens(P.b, b0, b1, [&](int32_t k, int64_t i) {
+    scan_tokens(C.b, b0, b1, [&](int32_t k, int64_t i) {
       int64_t end;
-      const int32_t id = vocab_lookup(V, P.b, i, b1, end);
+      const int32_t id = vocab_lookup(V, C.b, i, b1, end);
       if (k < nb) ob[k] = (uint16_t)id;
     });
     if (lane == 0) P.flags[r] = (uint8_t)((P.is_random_next[r] ? 1u : 0u) | 2u);
@@ -221,17 +196,15 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
       // is scheduled in front of the point all lanes have reached
       __threadfence();
       __builtin_amdgcn_wave_barrier();
-      const int64_t l1 = P.lab_off[r + 1];
-      scan_tokens(P.lab, P.lab_off[r], l1, [&](int32_t k, int64_t i) {
+      const int64_t l1 = C.lab_off[r + 1];
+      scan_tokens(C.lab, C.lab_off[r], l1, [&](int32_t k, int64_t i) {
         int64_t end;
-        const int32_t id = vocab_lookup(V, P.lab, i, l1, end);
+        const int32_t id = vocab_lookup(V, C.lab, i, l1, end);
         if (k >= (int32_t)np) return;
         const int32_t pos = (int32_t)d[2 * k] | ((int32_t)d[2 * k + 1] << 8);  // < n: static_columns
-        int32_t shown;
-        if (pos == 0) shown = V.cls;
-        else if (pos == na + 1 || pos == n - 1) shown = V.sep;
-        else if (pos <= na) shown = oa[pos - 1];
-        else shown = ob[pos - na - 2];
+        const int32_t shown = S.base_id(pos, V.cls, V.sep, [&](int32_t c) {
+          return (int32_t)(c <= na ? oa[c - 1] : ob[c - na - 2]);
+        });
         P.mlm_pos[m0 + k] = (uint16_t)pos;
         P.mlm_label[m0 + k] = (uint16_t)id;
         P.mlm_token[m0 + k] = (uint16_t)shown;
@@ -239,15 +212,6 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
     }
   }
 }
-
-static int grid_rows(int64_t n_rows, int n_cu) {
-  int64_t g = (n_rows + 3) / 4;
-  const int64_t cap = (int64_t)n_cu * 8;
-  if (g > cap) g = cap;
-  return (int)(g < 1 ? 1 : g);
-}
-
-int64_t rows_from_strings_chunks(int64_t n_rows) { return (n_rows + kChunk - 1) / kChunk; }
 
 hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;

@@ -74,6 +74,21 @@ def _merge_columns(parts):
   return data, np.concatenate(off)
 
 
+def _sample_columns(batch, static):
+  """the reference's samples -> ([A, B(, positions, labels)] as (bytes, offsets), is_random_next bytes)"""
+  cols = [_column([s[0] for s in batch], True), _column([s[1] for s in batch], True)]
+  if static:
+    cols += [_column([s[3] for s in batch], False), _column([s[4] for s in batch], True)]
+  return cols, np.fromiter((bool(s[2]) for s in batch), dtype=np.uint8, count=len(batch))
+
+
+def _table_columns(table, static):
+  """_sample_columns for a pyarrow RecordBatch / Table of the shard schema"""
+  names = ['A', 'B'] + (['masked_lm_positions', 'masked_lm_labels'] if static else [])
+  return ([_arrow_column(table.column(k)) for k in names],
+          np.asarray(table.column('is_random_next').to_numpy(zero_copy_only=False), dtype=np.uint8))
+
+
 def _shard_columns(table):
   """load_rows' input -> ([A, B(, positions, labels)] as (bytes, offsets), is_random_next bytes, static)"""
   if hasattr(table, 'schema'):
@@ -85,24 +100,29 @@ def _shard_columns(table):
     static = len(table[0]) > 3
     if any(len(s) != (5 if static else 3) for s in table):
       raise ValueError('samples of 3 fields, or of 5 with static masks')
-    cols = [_column([s[0] for s in table], True), _column([s[1] for s in table], True)]
-    if static:
-      cols += [_column([s[3] for s in table], False), _column([s[4] for s in table], True)]
-    return cols, np.fromiter((bool(s[2]) for s in table), dtype=np.uint8, count=len(table)), static
-  names = ['A', 'B']
+    return _sample_columns(table, static) + (static,)
   for t in table:
     if 'A' not in t.schema.names or 'B' not in t.schema.names:
       raise ValueError('not a BERT shard (columns %s): CodeBERT shards have no loader' % (t.schema.names,))
   static = 'masked_lm_positions' in table[0].schema.names
-  if static:
-    names += ['masked_lm_positions', 'masked_lm_labels']
   for t in table:
     if ('masked_lm_positions' in t.schema.names) != static or (static and 'masked_lm_labels' not in t.schema.names):
       raise ValueError('shards with and without static masks')
-  cols = [_merge_columns([_arrow_column(t.column(k)) for t in table]) for k in names]
-  rn = np.concatenate([np.asarray(t.column('is_random_next').to_numpy(zero_copy_only=False), dtype=np.uint8)
-                       for t in table])
-  return cols, rn, static
+  parts = [_table_columns(t, static) for t in table]
+  cols = [_merge_columns([c[k] for c, _ in parts]) for k in range(4 if static else 2)]
+  return cols, np.concatenate([rn for _, rn in parts]), static
+
+
+def _check(rc):
+  """_lib.check with LDDL_EINDEX (-7) as the IndexError the reference raises for a position out of range"""
+  if rc == -7:
+    raise IndexError(_lib.lib().lddl_last_error().decode())
+  _lib.check(rc)
+
+
+def _ptr(t):
+  """a tensor's (None: NULL) or a device address's void pointer"""
+  return ctypes.c_void_p(0 if t is None else t if isinstance(t, int) else t.data_ptr())
 
 
 _SHARD_NAME = re.compile(r'^(?:(?:part\.|shard-)(\d+)(?=\.parquet)|[^/]*?)\.parquet(?:_(\d+))?$')
@@ -216,36 +236,35 @@ class BertCollate:
     base = dev.data_ptr()
     return dev, host, [base + s for s in starts]
 
-  def _run(self, cols, is_random_next, static):
+  def _run(self, cols, is_random_next, static, mode=None):
+    """lddl_collate_seq_len + lddl_collate_bert over staged columns.  mode None:
+    static or dynamic masking, and the batch counter advances; mode 0 (the
+    special_tokens_mask in place of labels) leaves it."""
     L = _lib.lib()
     n = len(is_random_next)
     if n == 0:
       raise ValueError('empty batch')  # max() of an empty sequence in bert.py:94-95
     dev, host, ptrs = self._upload(cols, is_random_next)
     st = _stream()
-    P = ctypes.c_void_p
+    ab = [_ptr(x) for x in ptrs[:4]]
     seq = ctypes.c_int64()
-    _lib.check(L.lddl_collate_seq_len(self.tok.handle, P(ptrs[0]), P(ptrs[1]), P(ptrs[2]), P(ptrs[3]), n,
-                                      self.sequence_length_alignment, ctypes.byref(seq), st))
+    _check(L.lddl_collate_seq_len(self.tok.handle, *ab, n, self.sequence_length_alignment, ctypes.byref(seq), st))
     S = int(seq.value)
-    out = torch.empty((5, n, S), dtype=torch.int64, device=self.device)
+    out = torch.empty((4, n, S), dtype=torch.int64, device=self.device)
     nsl = torch.empty(n, dtype=torch.int64, device=self.device)
-    if static:
-      pos_d, pos_o, lab_d, lab_o = ptrs[4:8]
-    else:
-      pos_d = pos_o = lab_d = lab_o = 0
-    mode = MODE_STATIC if static else MODE_DYNAMIC
-    rc = L.lddl_collate_bert(self.tok.handle, P(ptrs[0]), P(ptrs[1]), P(ptrs[2]), P(ptrs[3]), P(ptrs[-1]),
-                             P(pos_d), P(pos_o), P(lab_d), P(lab_o), n, S, mode, self.ignore_index,
-                             self.mlm_probability, self.seed, self.counter, P(out[0].data_ptr()),
-                             P(out[1].data_ptr()), P(out[2].data_ptr()), P(out[3].data_ptr()), P(nsl.data_ptr()), st)
-    self.counter += 1
-    if rc == -7:
-      raise IndexError(L.lddl_last_error().decode())
-    _lib.check(rc)
+    advance = mode is None
+    if advance:
+      mode = MODE_STATIC if static else MODE_DYNAMIC
+    masks = [_ptr(x) for x in ptrs[4:8]] if mode == MODE_STATIC else [_ptr(None)] * 4
+    rc = L.lddl_collate_bert(self.tok.handle, *ab, _ptr(ptrs[-1]), *masks, n, S, mode, self.ignore_index,
+                             self.mlm_probability, self.seed, self.counter, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
+                             _ptr(out[3]), _ptr(nsl), st)
+    if advance:
+      self.counter += 1
+    _check(rc)
     del dev, host  # the stream was synchronised by the call
-    return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2],
-            'next_sentence_labels': nsl, 'labels': out[3]}
+    return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2], 'next_sentence_labels': nsl,
+            'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
 
   # ---- entry points ---------------------------------------------------------
   def __call__(self, batch):
@@ -254,40 +273,19 @@ class BertCollate:
     static = len(batch[0]) > 3
     if static:
       assert len(batch[0]) == 5
-    cols = [_column([s[0] for s in batch], True), _column([s[1] for s in batch], True)]
-    if static:
-      cols.append(_column([s[3] for s in batch], False))
-      cols.append(_column([s[4] for s in batch], True))
-    rn = np.fromiter((bool(s[2]) for s in batch), dtype=np.uint8, count=len(batch))
-    return self._run(cols, rn, static)
+    return self._run(*_sample_columns(batch, static), static)
 
   def collate_arrow(self, table):
     """A pyarrow RecordBatch/Table with the shard schema (pretrain.py:457-471)."""
-    names = table.schema.names
-    static = 'masked_lm_positions' in names
+    static = 'masked_lm_positions' in table.schema.names
     if static:
-      assert 'masked_lm_labels' in names
-    cols = [_arrow_column(table.column('A')), _arrow_column(table.column('B'))]
-    if static:
-      cols.append(_arrow_column(table.column('masked_lm_positions')))
-      cols.append(_arrow_column(table.column('masked_lm_labels')))
-    rn = np.asarray(table.column('is_random_next').to_numpy(zero_copy_only=False), dtype=np.uint8)
-    return self._run(cols, rn, static)
+      assert 'masked_lm_labels' in table.schema.names
+    return self._run(*_table_columns(table, static), static)
 
-  def collate_rows(self, res, rows=None, row0=0, n_rows=None, mode=None):
-    """A batch straight from a pack result on the GPU (lddl_collate_rows):
-    the rows ``rows`` (an int64 CUDA tensor, or anything torch.as_tensor
-    takes; any order, repeats allowed) of ``res``, a PackResult with spans
-    (``Packer.pack(..., spans=True)``) -- or rows [row0, row0 + n_rows)
-    (default: all from row0 on).  Returns the dict of ``__call__`` (mode 0:
-    'special_tokens_mask' in place of 'labels', as ``to_encoded_inputs``) and
-    advances the batch counter as ``__call__`` does.  mode defaults to static
-    when the result carries static masks, else dynamic.  Nothing is staged on
-    the host: the kernel reads the packer's own buffers.  ``res`` must have
-    been packed with this collate's vocab, on its device; a CodeBERT result
-    (rows without the [SEP] after segment 0) is refused by the C call."""
+  def _row_batch(self, who, res, rows, row0, n_rows, mode):
+    """what collate_rows / collate_rows_unpadded (who) take -> (mode, rows, row0, n)"""
     if not res.spans:
-      raise ValueError('collate_rows needs a PackResult with spans (Packer.pack(..., spans=True))')
+      raise ValueError('%s needs a PackResult with spans (Packer.pack(..., spans=True))' % who)
     if mode is None:
       mode = MODE_STATIC if res.mlm_token is not None else MODE_DYNAMIC
     if mode not in (MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC):
@@ -302,16 +300,25 @@ class BertCollate:
       n = res.n_pairs - row0 if n_rows is None else int(n_rows)
     if n <= 0:
       raise ValueError('empty batch')  # max() of an empty sequence in bert.py:94-95
-    L = _lib.lib()
-    st = _stream()
-    P = ctypes.c_void_p
-    p = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+    return mode, rows, row0, n
+
+  def collate_rows(self, res, rows=None, row0=0, n_rows=None, mode=None):
+    """A batch straight from a pack result on the GPU (lddl_collate_rows):
+    the rows ``rows`` (an int64 CUDA tensor, or anything torch.as_tensor
+    takes; any order, repeats allowed) of ``res``, a PackResult with spans
+    (``Packer.pack(..., spans=True)``) -- or rows [row0, row0 + n_rows)
+    (default: all from row0 on).  Returns the dict of ``__call__`` (mode 0:
+    'special_tokens_mask' in place of 'labels', as ``to_encoded_inputs``) and
+    advances the batch counter as ``__call__`` does.  mode defaults to static
+    when the result carries static masks, else dynamic.  Nothing is staged on
+    the host: the kernel reads the packer's own buffers.  ``res`` must have
+    been packed with this collate's vocab, on its device; a CodeBERT result
+    (rows without the [SEP] after segment 0) is refused by the C call."""
+    mode, rows, row0, n = self._row_batch('collate_rows', res, rows, row0, n_rows, mode)
+    L, st, p = _lib.lib(), _stream(), _ptr
     seq = ctypes.c_int64()
-    rc = L.lddl_collate_rows_seq_len(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
-                                     self.sequence_length_alignment, ctypes.byref(seq), st)
-    if rc == -7:
-      raise IndexError(L.lddl_last_error().decode())
-    _lib.check(rc)
+    _check(L.lddl_collate_rows_seq_len(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
+                                       self.sequence_length_alignment, ctypes.byref(seq), st))
     S = int(seq.value)
     out = torch.empty((4, n, S), dtype=torch.int64, device=self.device)
     nsl = torch.empty(n, dtype=torch.int64, device=self.device)
@@ -322,9 +329,7 @@ class BertCollate:
                              p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nsl), st)
     if mode != MODE_SPECIAL_MASK:
       self.counter += 1
-    if rc == -7:
-      raise IndexError(L.lddl_last_error().decode())
-    _lib.check(rc)
+    _check(rc)
     return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2], 'next_sentence_labels': nsl,
             'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
 
@@ -341,33 +346,12 @@ class BertCollate:
     with the pad columns dropped, bit for bit.  The batch counter advances as
     in ``collate_rows``.  ``sequence_length_alignment`` has no effect here:
     nothing is padded."""
-    if not res.spans:
-      raise ValueError('collate_rows_unpadded needs a PackResult with spans (Packer.pack(..., spans=True))')
-    if mode is None:
-      mode = MODE_STATIC if res.mlm_token is not None else MODE_DYNAMIC
-    if mode not in (MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC):
-      raise ValueError('mode %r not in 0..2' % (mode,))
-    if mode == MODE_STATIC and res.mlm_token is None:
-      raise ValueError('static mode needs a result packed with masking=True')
-    if rows is not None:
-      rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device).contiguous().view(-1)
-      n, row0 = rows.numel(), 0
-    else:
-      row0 = int(row0)
-      n = res.n_pairs - row0 if n_rows is None else int(n_rows)
-    if n <= 0:
-      raise ValueError('empty batch')
-    L = _lib.lib()
-    st = _stream()
-    P = ctypes.c_void_p
-    p = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+    mode, rows, row0, n = self._row_batch('collate_rows_unpadded', res, rows, row0, n_rows, mode)
+    L, st, p = _lib.lib(), _stream(), _ptr
     cu = torch.empty(n + 1, dtype=torch.int32, device=self.device)
     total, longest = ctypes.c_int64(), ctypes.c_int64()
-    rc = L.lddl_collate_rows_cu_seqlens(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
-                                        p(cu), ctypes.byref(total), ctypes.byref(longest), st)
-    if rc == -7:
-      raise IndexError(L.lddl_last_error().decode())
-    _lib.check(rc)
+    _check(L.lddl_collate_rows_cu_seqlens(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
+                                          p(cu), ctypes.byref(total), ctypes.byref(longest), st))
     T = int(total.value)
     out = torch.empty((4, T), dtype=torch.int64, device=self.device)
     nsl = torch.empty(n, dtype=torch.int64, device=self.device)
@@ -378,9 +362,7 @@ class BertCollate:
                                       self.seed, self.counter, p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nsl), st)
     if mode != MODE_SPECIAL_MASK:
       self.counter += 1
-    if rc == -7:
-      raise IndexError(L.lddl_last_error().decode())
-    _lib.check(rc)
+    _check(rc)
     return {'input_ids': out[0], 'token_type_ids': out[1], 'position_ids': out[2], 'next_sentence_labels': nsl,
             'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3], 'cu_seqlens': cu,
             'max_seqlen': int(longest.value)}
@@ -406,12 +388,9 @@ class BertCollate:
     n = len(rn)
     if n == 0:
       raise ValueError('no rows')
-    L = _lib.lib()
-    st = _stream()
-    P = ctypes.c_void_p
-    p = lambda t: P(t.data_ptr() if t is not None else 0)  # noqa: E731
+    L, st, p = _lib.lib(), _stream(), _ptr
     dev, host, ptrs = self._upload(cols, rn)
-    inp = [P(x) for x in ptrs[:8]] if static else [P(x) for x in ptrs[:4]] + [P(0)] * 4
+    inp = [p(x) for x in ptrs[:8]] if static else [p(x) for x in ptrs[:4]] + [p(None)] * 4
 
     def buf(m, dtype):
       return torch.empty(max(m, 1), dtype=dtype, device=self.device)
@@ -420,14 +399,9 @@ class BertCollate:
     tok_off = buf(n + 1, torch.int64)
     mlm_off = buf(n + 1, torch.int64) if static else None
     tot = (ctypes.c_int64 * 3)()
-
-    def check(rc):
-      if rc == -7:
-        raise IndexError(L.lddl_last_error().decode())
-      _lib.check(rc)
     try:
-      check(L.lddl_rows_from_strings_len(self.tok.handle, *inp, n, p(len0), p(len1), p(src0), p(src1), p(tok_off),
-                                         p(mlm_off), tot, st))
+      _check(L.lddl_rows_from_strings_len(self.tok.handle, *inp, n, p(len0), p(len1), p(src0), p(src1), p(tok_off),
+                                          p(mlm_off), tot, st))
     except Exception:
       torch.cuda.current_stream().synchronize()  # a call refused before its launch leaves the staging copy queued
       raise
@@ -436,8 +410,9 @@ class BertCollate:
     ids[n_ids:].zero_()
     flags = buf(n, torch.uint8)
     mlm = [buf(n_masked, torch.int16) for _ in range(3)] if static else [None] * 3
-    check(L.lddl_rows_from_strings(self.tok.handle, *inp, P(ptrs[-1]), n, p(len0), p(len1), p(src0), p(src1),
-                                   p(mlm_off), p(ids), n_ids, p(flags), p(mlm[0]), p(mlm[1]), p(mlm[2]), n_masked, st))
+    _check(L.lddl_rows_from_strings(self.tok.handle, *inp, p(ptrs[-1]), n, p(len0), p(len1), p(src0), p(src1),
+                                    p(mlm_off), p(ids), n_ids, p(flags), p(mlm[0]), p(mlm[1]), p(mlm[2]), n_masked,
+                                    st))
     del dev, host  # the length call synchronised the stream behind the staging copy
     part_h = np.zeros(n, np.int64) if part is None else np.ascontiguousarray(part, dtype=np.int64).reshape(-1)
     bins_h = np.zeros(n, np.uint8) if bins is None else np.ascontiguousarray(bins, dtype=np.uint8).reshape(-1)
@@ -465,30 +440,9 @@ class BertCollate:
   def to_encoded_inputs(self, batch):
     """bert.py:69-153 as is: with static masks 'labels', else
     'special_tokens_mask' (dynamic masking left to mask_tokens)."""
-    static = len(batch[0]) > 3
-    if static:
+    if len(batch[0]) > 3:
       return self(batch)
-    L = _lib.lib()
-    n = len(batch)
-    cols = [_column([s[0] for s in batch], True), _column([s[1] for s in batch], True)]
-    rn = np.fromiter((bool(s[2]) for s in batch), dtype=np.uint8, count=n)
-    dev, host, ptrs = self._upload(cols, rn)
-    st = _stream()
-    P = ctypes.c_void_p
-    seq = ctypes.c_int64()
-    _lib.check(L.lddl_collate_seq_len(self.tok.handle, P(ptrs[0]), P(ptrs[1]), P(ptrs[2]), P(ptrs[3]), n,
-                                      self.sequence_length_alignment, ctypes.byref(seq), st))
-    S = int(seq.value)
-    out = torch.empty((4, n, S), dtype=torch.int64, device=self.device)
-    nsl = torch.empty(n, dtype=torch.int64, device=self.device)
-    _lib.check(L.lddl_collate_bert(self.tok.handle, P(ptrs[0]), P(ptrs[1]), P(ptrs[2]), P(ptrs[3]), P(ptrs[-1]),
-                                   P(0), P(0), P(0), P(0), n, S, MODE_SPECIAL_MASK, self.ignore_index,
-                                   self.mlm_probability, self.seed, self.counter, P(out[0].data_ptr()),
-                                   P(out[1].data_ptr()), P(out[2].data_ptr()), P(out[3].data_ptr()),
-                                   P(nsl.data_ptr()), st))
-    del dev, host
-    return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2],
-            'next_sentence_labels': nsl, 'special_tokens_mask': out[3]}
+    return self._run(*_sample_columns(batch, False), False, mode=MODE_SPECIAL_MASK)
 
   def mask_tokens(self, inputs, special_tokens_mask, counter=None):
     """bert.py:156-196 on device tensors: masks ``inputs`` in place and

@@ -417,6 +417,58 @@ def test_batch_sizes(gpu, n):
   assert_raw(tokenizer(_lib.VOCAB_BERT), short_rows(n, n), 0)
 
 
+def short_masked_rows(n, seed):
+  """two or three tokens per segment, one or two masked positions, every seventh row none"""
+  words = ['the', 'of', 'and', 'hello', 'world', 'qqzz', 'in', '[MASK]']
+  rng = np.random.default_rng(seed)
+  pick = lambda k: ' '.join(words[j] for j in rng.integers(0, len(words), k))  # noqa: E731
+  rows = []
+  for r in range(n):
+    la, lb = int(rng.integers(2, 4)), int(rng.integers(2, 4))
+    k = 0 if r % 7 == 3 else int(rng.integers(1, 3))
+    rows.append((pick(la), pick(lb), r & 1, npy(sorted(rng.permutation(la + lb + 3)[:k].tolist())), pick(k)))
+  return rows
+
+
+def table_arrays(res):
+  """a load_rows result as the arrays of model()"""
+  n = res.n_pairs
+  o = {k: u16(getattr(res, k)[:n]) for k in ('len0', 'len1')}
+  o['flags'] = res.flags[:n].cpu().numpy().astype(np.int64)
+  o['ids'] = u16(res.ids)[:int((o['len0'] + o['len1']).sum())]
+  for k in ('src0', 'src1'):
+    o[k] = getattr(res, k)[:n].cpu().numpy()
+  for k in ('tok_off', 'mlm_off'):
+    o[k] = getattr(res, k)[:n + 1].cpu().numpy()
+  for k in ('mlm_pos', 'mlm_label', 'mlm_token'):
+    o[k] = u16(getattr(res, k)[:res.n_masked])
+  return o
+
+
+@pytest.mark.parametrize('n', [2047, 2048, 2049])
+def test_static_rows_across_a_scan_chunk(gpu, n):
+  """both scanned quantities, ids and masked entries, up to and across the base of the scan's second chunk of
+  2048 rows: the table of n rows against the host model and against the same rows loaded in two halves"""
+  tok = tokenizer(_lib.VOCAB_BERT)
+  rows = short_masked_rows(n, 5)
+  col = collate_for(tok)
+  exp = model(tok, rows)
+  assert exp['mlm_off'][2047] > 0 and (exp['mlm_k'] == 0).sum() > 100
+  whole = col.load_rows(rows)
+  assert (whole.n_pairs, whole.n_tokens, whole.n_masked) == (n, int(exp['tok_off'][-1]), exp['mlm_pos'].size)
+  got = table_arrays(whole)
+  for k, v in got.items():
+    assert np.array_equal(v, exp[k]), k
+  h = n // 2
+  lo, hi = table_arrays(col.load_rows(rows[:h])), table_arrays(col.load_rows(rows[h:]))
+  for k in ('len0', 'len1', 'flags', 'ids', 'mlm_pos', 'mlm_label', 'mlm_token'):
+    assert np.array_equal(got[k], np.concatenate([lo[k], hi[k]])), k
+  for k, base in (('src0', lo['ids'].size), ('src1', lo['ids'].size), ('tok_off', lo['tok_off'][-1]),
+                  ('mlm_off', lo['mlm_off'][-1])):
+    first = lo[k] if k in ('src0', 'src1') else lo[k][:-1]
+    assert np.array_equal(got[k], np.concatenate([first, hi[k] + base])), k
+
+
 def test_segment_of_65535_tokens(gpu):
   tok = tokenizer(_lib.VOCAB_BERT)
   assert_raw(tok, [('the', 'of', 0), ('a ' * 65535, 'b\n' * 65535, 1), ('and', '', 0)])

@@ -146,7 +146,6 @@ struct lddl_pack {
   WsBuf ws[PW_COUNT];
   PackParams pp{};
   int64_t last_npairs = -1, last_ntok = -1, last_nmask = -1, last_ndense = 0;
-  int pack_codebert = 0;
   uint64_t mlm_cap = 0;  // masking arena capacity that last sufficed
   uint16_t* last_tokens = nullptr;  // rows of the last lddl_materialize of this result
   const int64_t* last_tok_off = nullptr;

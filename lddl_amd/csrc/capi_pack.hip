@@ -246,7 +246,6 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
     break;
   }
   const int32_t e = (int32_t)(c->h_tot[HW_PACK_ERR] & 0xFFFFFFFF);
-  k->pack_codebert = codebert;
   k->last_nmask = masking ? c->h_tot[HW_NMASK] : -1;
   if (e & PACK_EINDEX) { k->last_npairs = -1; return set_err(LDDL_EINDEX, "IndexError in _truncate_seq (reference quirk)"); }
   if (e & PACK_EASSERT) { k->last_npairs = -1; return set_err(LDDL_EASSERT, "AssertionError: empty segment after truncation"); }
@@ -281,29 +280,38 @@ extern "C" int lddl_pack_codebert(lddl_ctx* c, lddl_pack* pk, const int32_t* d_n
                      n_part, target_seq_length, short_seq_prob, duplicate_factor, seed, bin_size, out_totals, stream);
 }
 
-// MatParams of the last pack call (lddl_materialize / lddl_row_spans)
-static MatParams mat_params(const lddl_ctx* c, const lddl_pack* k) {
+// The view of the last pack call's result that every call reading it works through
+static PackView pack_view(const lddl_pack* k) {
   const PackParams& P = k->pp;
+  PackView V{};
+  V.pairs = P.pairs;
+  V.binned = P.binned;
+  V.tok_local = P.tok_local;
+  V.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
+  V.tok_base = (const int64_t*)k->ws[PW_TOK_BASE].p;
+  V.doc_sent_off = P.doc_sent_off;
+  V.part_doc_off = P.part_doc_off;
+  V.fs_dense = P.fs_dense;
+  V.n_part = P.n_part;
+  V.dup = P.dup;
+  V.bin_size = P.bin_size;
+  V.nbins = P.nbins;
+  return V;
+}
+
+// MatParams of the last pack call with the per-row outputs both of its calls take (lddl_materialize / lddl_row_spans)
+static MatParams mat_params(const lddl_ctx* c, const lddl_pack* k, int64_t* tok_off, uint16_t* len0, uint16_t* len1,
+                            uint8_t* flags, uint8_t* bin, int64_t* part) {
   MatParams M{};
-  M.fs_dense = P.fs_dense;
-  M.sent_off = P.sent_off;
-  M.doc_sent_off = P.doc_sent_off;
-  M.part_doc_off = P.part_doc_off;
-  M.fs_base = P.fs_base;
-  M.fs_ntok = P.fs_ntok;
-  M.pairs = P.pairs;
-  M.binned = P.binned;
-  M.tok_local = P.tok_local;
-  M.part_npairs = P.part_npairs;
-  M.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
-  M.tok_base = (const int64_t*)k->ws[PW_TOK_BASE].p;
-  M.n_part = P.n_part;
-  M.dup = P.dup;
-  M.bin_size = P.bin_size;
-  M.nbins = P.nbins;
+  M.V = pack_view(k);
   M.cls_id = c->special[2];
   M.sep_id = c->special[3];
-  M.codebert = k->pack_codebert;
+  M.out_tok_off = tok_off;
+  M.out_len0 = len0;
+  M.out_len1 = len1;
+  M.out_flags = flags;
+  M.out_bin = bin;
+  M.out_part = part;
   return M;
 }
 
@@ -311,16 +319,11 @@ static MatParams mat_params(const lddl_ctx* c, const lddl_pack* k) {
 static MlmParams mlm_params(const lddl_pack* k) {
   const PackParams& P = k->pp;
   MlmParams M{};
-  M.doc_sent_off = P.doc_sent_off;
-  M.part_doc_off = P.part_doc_off;
-  M.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
-  M.binned = P.binned;
+  M.V = pack_view(k);
   M.mref = P.mref;
   M.mloc = P.mloc;
   M.mask_base = (const int64_t*)k->ws[PW_MASK_BASE].p;
   M.marena = P.marena;
-  M.n_part = P.n_part;
-  M.dup = P.dup;
   return M;
 }
 
@@ -339,15 +342,9 @@ extern "C" int lddl_materialize(lddl_ctx* c, lddl_pack* pk, const uint16_t* d_id
   // LDDL_MAT_ALGO=1: the wave-per-partition materialize kernel (also taken
   // for unaligned buffers); otherwise the chunked v2 kernel
   const int mat_algo = getenv("LDDL_MAT_ALGO") ? atoi(getenv("LDDL_MAT_ALGO")) : 2;
-  MatParams M = mat_params(c, k);
+  MatParams M = mat_params(c, k, d_out_tok_off, d_out_len0, d_out_len1, d_out_flags, d_out_bin, d_out_part);
   M.dense = d_ids;
   M.out_tokens = d_out_tokens;
-  M.out_tok_off = d_out_tok_off;
-  M.out_len0 = d_out_len0;
-  M.out_len1 = d_out_len1;
-  M.out_flags = d_out_flags;
-  M.out_bin = d_out_bin;
-  M.out_part = d_out_part;
   if (k->last_npairs == 0) {
     HIP_TRY(hipMemsetAsync(d_out_tok_off, 0, 8, st));
   } else {
@@ -372,15 +369,9 @@ extern "C" int lddl_row_spans(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_src0, i
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   const PackParams& P = k->pp;
-  MatParams M = mat_params(c, k);
+  MatParams M = mat_params(c, k, d_out_tok_off, d_out_len0, d_out_len1, d_out_flags, d_out_bin, d_out_part);
   M.out_src0 = d_out_src0;
   M.out_src1 = d_out_src1;
-  M.out_tok_off = d_out_tok_off;
-  M.out_len0 = d_out_len0;
-  M.out_len1 = d_out_len1;
-  M.out_flags = d_out_flags;
-  M.out_bin = d_out_bin;
-  M.out_part = d_out_part;
   if (k->last_npairs == 0) {
     if (d_out_tok_off) HIP_TRY(hipMemsetAsync(d_out_tok_off, 0, 8, st));
   } else {
@@ -390,7 +381,7 @@ extern "C" int lddl_row_spans(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_src0, i
     if ((rc =ws_get(c, CW_CHUNK_PART, (size_t)((k->last_npairs + 63) >> 6), &chunk_part)) ||
         (rc = ws_get(c, CW_PART_PB, (size_t)P.n_part, &part_pb)))
       return rc;
-    HIP_TRY(launch_chunk_parts(M.pair_base, P.doc_sent_off, P.part_doc_off, P.dup, P.n_part, chunk_part, part_pb, st));
+    HIP_TRY(launch_chunk_parts(M.V.pair_base, P.doc_sent_off, P.part_doc_off, P.dup, P.n_part, chunk_part, part_pb, st));
     M.chunk_part = chunk_part;
     M.part_pb = part_pb;
     HIP_TRY(launch_row_spans(M, k->last_npairs, st));
@@ -465,16 +456,10 @@ extern "C" int lddl_row_docs(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_doc, voi
   HIP_TRY(hipSetDevice(c->device));
   const PackParams& P = k->pp;
   RowDocParams D{};
-  D.pairs = P.pairs;
-  D.binned = P.binned;
-  D.pair_base = (const int64_t*)k->ws[PW_PAIR_BASE].p;
+  D.V = pack_view(k);
   D.fs_base = P.fs_base;
   D.sent_off = P.sent_off;
-  D.doc_sent_off = P.doc_sent_off;
-  D.part_doc_off = P.part_doc_off;
-  D.n_part = P.n_part;
   D.n_rows = k->last_npairs;
-  D.dup = P.dup;
   D.out_doc = d_out_doc;
   HIP_TRY(launch_row_docs(D, c->n_cu, (hipStream_t)stream));
   return 0;

@@ -77,17 +77,31 @@ constexpr int MLM_CHUNK = 1024;     // arena entries grabbed per allocation
 constexpr int MLM_MAX_SEQ = 1024;   // masking: target_seq_length limit (LDS lists)
 constexpr uint32_t MLM_KEEP = 0xFFFFu;
 
-struct MlmParams {
+// What a finished pack leaves for the calls that read it (materialize, row
+// spans, masked LM, row docs): row g of the output lies in partition p, at
+// binned position pb + (g - pair_base[p]) with pb = dup *
+// doc_sent_off[part_doc_off[p]], and its record is pairs[pb + binned[that]].
+// pack_row.h resolves rows through it; capi_pack.hip's pack_view fills it.
+struct PackView {
+  const PairRec* pairs;
+  const int32_t* binned;
+  const int64_t* tok_local;     // [dup * n_sent] per binned position: tokens before it in its partition
+  const int64_t* pair_base;     // [n_part+1] exclusive scan of part_npairs
+  const int64_t* tok_base;      // [n_part+1] exclusive scan of part_ntok
   const int64_t* doc_sent_off;
   const int64_t* part_doc_off;
-  const int64_t* pair_base;
-  const int32_t* binned;
+  const int64_t* fs_dense;      // dense id offset per filtered slot
+  int64_t n_part;
+  int32_t dup;
+  int32_t bin_size, nbins;
+};
+
+struct MlmParams {
+  PackView V;
   const int64_t* mref;
   const int64_t* mloc;
   const int64_t* mask_base;     // [n_part+1] exclusive scan of part_nmask
   const uint32_t* marena;
-  int64_t n_part;
-  int32_t dup;
   uint16_t* tokens;             // rows written by lddl_materialize (masked in place)
   const int64_t* tok_off;
   const int64_t* row_part;      // [n_pairs] partition of each row (materialize's out_part)
@@ -103,26 +117,11 @@ struct MlmParams {
 };
 
 struct MatParams {
+  PackView V;
   const uint16_t* dense;        // the tokenizer's dense ids (sentence s at tokoff[s])
-  const int64_t* fs_dense;      // dense offset per filtered slot
-  const int64_t* sent_off;
-  const int64_t* doc_sent_off;
-  const int64_t* part_doc_off;
-  const int64_t* fs_base;
-  const uint16_t* fs_ntok;
-  const PairRec* pairs;
-  const int32_t* binned;
-  const int64_t* tok_local;
-  const int64_t* part_npairs;
-  const int64_t* pair_base;     // [n_part+1] exclusive scan of part_npairs
-  const int64_t* tok_base;      // [n_part+1] exclusive scan of part_ntok
   const int32_t* chunk_part;    // row spans: partition of row 64c, per 64-row chunk c (chunk_parts_kernel)
   const int64_t* part_pb;       // row spans: dup * first sentence of partition p (its pair arrays' base)
-  int64_t n_part;
-  int32_t dup;
-  int32_t bin_size, nbins;
   uint32_t cls_id, sep_id;
-  int32_t codebert;
   // outputs, global final order (partition-major, bin-major, shuffled)
   uint16_t* out_tokens;         // [total tokens]  [CLS] A [SEP] B [SEP]
   int64_t* out_tok_off;         // [n_pairs + 1]

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "pack.h"
+#include "pack_row.h"
 #include "wave.h"
 
 namespace lddl {
@@ -53,63 +54,37 @@ __global__ __launch_bounds__(1024) void scan_parts_kernel(const int64_t* a, cons
 }
 
 // ----------------------------------------------------- materialise ----
-// A segment is n consecutive filtered sentences cut to [lo, hi); in the dense
-// id array (sentences' ids back to back) that is ONE run starting at
-// fs_dense[fs] + lo.  One wave per partition (no row -> partition search):
-// chunks of 64 rows are staged in LDS (record, offsets, runs), then copied by
-// half-waves, one row each, 16 tokens per lane in flight.
-struct RowStage {
-  int64_t off;        // first output token of the row
-  int64_t src0, src1; // dense offsets of segment 0 / 1
-  int32_t l0, l1;     // segment lengths
-  int32_t nt;         // num_tokens
-  int32_t seg0;       // [SEP] after segment 0
-};
-
+// One wave per partition (no row -> partition search): chunks of 64 rows are
+// staged in LDS (descriptor and output offset), then copied by half-waves,
+// one row each, 16 tokens per lane in flight.
 __global__ __launch_bounds__(256) void materialize_kernel(MatParams M) {
-  __shared__ RowStage st[4][64];
+  __shared__ RowDesc st[4][64];
+  __shared__ int64_t st_off[4][64];  // first output token of the row
+  const PackView& V = M.V;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t total = M.pair_base[M.n_part];
+  const int64_t total = V.pair_base[V.n_part];
   const int64_t nw = (int64_t)gridDim.x * 4;
-  for (int64_t p = (int64_t)blockIdx.x * 4 + wv; p < M.n_part; p += nw) {
-    const int64_t s0 = M.doc_sent_off[M.part_doc_off[p]];
-    const int64_t pb = (int64_t)M.dup * s0;
-    const int64_t g0 = M.pair_base[p], np = M.pair_base[p + 1] - g0, tb = M.tok_base[p];
+  for (int64_t p = (int64_t)blockIdx.x * 4 + wv; p < V.n_part; p += nw) {
+    const int64_t g0 = V.pair_base[p], np = V.pair_base[p + 1] - g0;
     for (int64_t c = 0; c < np; c += 64) {
-      const int64_t i = c + lane;
-      if (i < np) {
-        const PairRec r = M.pairs[pb + M.binned[pb + i]];
-        const int64_t off = tb + M.tok_local[pb + i];
-        const int32_t l0 = r.hi0 - r.lo0, l1 = r.hi1 - r.lo1;
-        const int64_t g = g0 + i;
-        RowStage& x = st[wv][lane];
-        x.off = off;
-        x.src0 = l0 > 0 ? M.fs_dense[r.fs0] + r.lo0 : 0;
-        x.src1 = l1 > 0 ? M.fs_dense[r.fs1] + r.lo1 : 0;
-        x.l0 = l0;
-        x.l1 = l1;
-        x.nt = r.num_tokens;
-        x.seg0 = (r.flags & 2) != 0;
-        M.out_tok_off[g] = off;
-        M.out_len0[g] = (uint16_t)l0;
-        M.out_len1[g] = (uint16_t)l1;
-        M.out_flags[g] = (uint8_t)r.flags;
-        const int32_t b = ((int32_t)r.num_tokens - 1) / M.bin_size;
-        M.out_bin[g] = (uint8_t)(b > M.nbins - 1 ? M.nbins - 1 : b);
-        M.out_part[g] = p;
-        if (g == total - 1) M.out_tok_off[total] = off + r.num_tokens;
+      if (c + lane < np) {
+        const int64_t g = g0 + c + lane;
+        PairRec r;
+        const RowRef w = pair_of_row(V, p, g, r);
+        const int64_t off = row_tok_off(V, p, w);
+        const RowDesc x = row_desc(V, r);
+        st[wv][lane] = x;
+        st_off[wv][lane] = off;
+        store_row_meta(M, g, p, r, x, total, [&] { return off; });
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
       const int nr = (int)min((int64_t)64, np - c);
       const int hl = lane & 31;
       for (int r0 = 0; r0 < nr; r0 += 2) {
         const int rr = r0 + (lane >> 5);
         if (rr >= nr) continue;
-        const RowStage x = st[wv][rr];
-        uint16_t* out = M.out_tokens + x.off;
-        const int b1 = 1 + x.l0 + x.seg0;  // first token of segment 1
+        const RowDesc x = st[wv][rr];
+        uint16_t* out = M.out_tokens + st_off[wv][rr];
         for (int t0 = 0; t0 < x.nt; t0 += 512) {
           uint16_t v[16];
 #pragma unroll
@@ -118,7 +93,7 @@ __global__ __launch_bounds__(256) void materialize_kernel(MatParams M) {
             uint16_t y = (uint16_t)M.sep_id;
             if (t == 0) y = (uint16_t)M.cls_id;
             else if (t <= x.l0) y = M.dense[x.src0 + (t - 1)];
-            else if (t >= b1 && t < b1 + x.l1) y = M.dense[x.src1 + (t - b1)];
+            else if (t >= x.b1 && t < x.b1 + x.l1) y = M.dense[x.src1 + (t - x.b1)];
             v[k] = y;
           }
 #pragma unroll
@@ -128,9 +103,7 @@ __global__ __launch_bounds__(256) void materialize_kernel(MatParams M) {
           }
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_sync();
     }
   }
 }
@@ -150,10 +123,6 @@ __global__ __launch_bounds__(256) void materialize_kernel(MatParams M) {
 constexpr int MAT_U = 2;         // chunks per lane per phase-1 iteration (1 / 3 within noise, 8 slower)
 constexpr int MAT_SLOW = 512;    // slow-chunk list capacity per wave
 constexpr int MAT_PBITS = 26;    // slow entry: chunk start + 8 (26 bits) | row << 26
-struct RowDesc {
-  int64_t src0, src1;       // source start of segment A / B
-  int32_t l0, b1, l1, nt;   // |A|, first position of B, |B|, row length
-};
 struct MatWave {
   int32_t roff[64];         // row start relative to G0 (INT_MAX past the last row)
   RowDesc row[64];
@@ -171,12 +140,6 @@ __device__ __forceinline__ uint4 funnel8(const uint4 A, const uint4 B, uint32_t 
   const uint32_t e4 = h0 ? B.x : h1 ? B.y : h2 ? B.z : B.w;
   return make_uint4(__builtin_amdgcn_alignbit(e1, e0, sh), __builtin_amdgcn_alignbit(e2, e1, sh),
                     __builtin_amdgcn_alignbit(e3, e2, sh), __builtin_amdgcn_alignbit(e4, e3, sh));
-}
-
-__device__ __forceinline__ void mat_wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // last row starting at or before p (rows may be empty: the last of equals)
@@ -201,7 +164,7 @@ __device__ __forceinline__ bool mat_tok(const RowDesc& x, int32_t t, uint32_t cl
 __device__ __forceinline__ void mat_drain(const MatWave& W, int ntok, bool listed, int64_t G0, int32_t G1r,
                                           const uint16_t* src, uint16_t* out, uint32_t cls, uint32_t sep,
                                           int lane) {
-  mat_wsync();
+  wave_sync();
   for (int j0 = 0; j0 < ntok; j0 += 4 * 64) {
     uint32_t y[4];
     int32_t pos[4];
@@ -226,7 +189,7 @@ __device__ __forceinline__ void mat_drain(const MatWave& W, int ntok, bool liste
     for (int m = 0; m < 4; ++m)
       if (pos[m] >= 0) out[G0 + pos[m]] = (uint16_t)y[m];
   }
-  mat_wsync();
+  wave_sync();
 }
 
 // rows published in W (roff, row) for nr rows spanning [G0, G1) of out;
@@ -320,51 +283,28 @@ __global__ __launch_bounds__(256) void materialize2_kernel(MatParams M, int64_t 
   if (gbase >= total) return;
   const int nr = (int)min((int64_t)64, total - gbase);
   MatWave& W = mw[wv];
-  // partition of the item's first pair (uniform binary search over pair_base)
-  int64_t plo = 0, phi = M.n_part - 1;
-  while (plo < phi) {
-    const int64_t mid = (plo + phi + 1) >> 1;
-    if (M.pair_base[mid] <= gbase) plo = mid;
-    else phi = mid - 1;
-  }
+  const PackView& V = M.V;
+  const int64_t plo = part_of_row(V, gbase);  // partition of the item's first pair
   // ---- row metadata + per-pair outputs ----
   int64_t off = 0, rend = 0;
   RowDesc x{};
   if (lane < nr) {
     const int64_t g = gbase + lane;
-    int64_t p = plo;
-    while (M.pair_base[p + 1] <= g) ++p;  // partitions of < 64 pairs
-    const int64_t i = g - M.pair_base[p];
-    const int64_t pb = (int64_t)M.dup * M.doc_sent_off[M.part_doc_off[p]];
-    const PairRec r = M.pairs[pb + M.binned[pb + i]];
-    off = M.tok_base[p] + M.tok_local[pb + i];
-    const int32_t l0 = r.hi0 - r.lo0, l1 = r.hi1 - r.lo1;
-    x.src0 = l0 > 0 ? M.fs_dense[r.fs0] + r.lo0 : 0;
-    x.src1 = l1 > 0 ? M.fs_dense[r.fs1] + r.lo1 : 0;
-    x.l0 = l0;
-    x.l1 = l1;
-    x.b1 = 1 + l0 + ((r.flags & 2) != 0);
-    x.nt = r.num_tokens;
-    rend = off + r.num_tokens;
-    M.out_tok_off[g] = off;
-    M.out_len0[g] = (uint16_t)l0;
-    M.out_len1[g] = (uint16_t)l1;
-    M.out_flags[g] = (uint8_t)r.flags;
-    const int32_t b = ((int32_t)r.num_tokens - 1) / M.bin_size;
-    M.out_bin[g] = (uint8_t)(b > M.nbins - 1 ? M.nbins - 1 : b);
-    M.out_part[g] = p;
-    if (g == total - 1) M.out_tok_off[total] = rend;
+    const int64_t p = part_walk(V, plo, g);
+    PairRec r;
+    const RowRef w = pair_of_row(V, p, g, r);
+    off = row_tok_off(V, p, w);
+    x = row_desc(V, r);
+    rend = off + x.nt;
+    store_row_meta(M, g, p, r, x, total, [&] { return off; });
   }
   const int64_t G0 = __shfl(off, 0), G1 = __shfl(rend, nr - 1);
   W.roff[lane] = lane < nr ? (int32_t)(off - G0) : 0x7FFFFFFF;
   W.row[lane] = x;
-  mat_wsync();
+  wave_sync();
   mat_copy(W, G0, G1, M.dense, n_src, M.out_tokens, M.cls_id, M.sep_id, lane);
 }
 
-#ifndef LDDL_ROWSPAN_XCD
-#define LDDL_ROWSPAN_XCD 1
-#endif
 // Row spans (lddl_row_spans): the rows of materialize2 without the token
 // copy.  Each segment of a row is ONE contiguous run of the tokenizer's dense
 // ids (a document's sentences are contiguous there and a segment is a window
@@ -396,19 +336,19 @@ hipError_t launch_chunk_parts(const int64_t* pair_base, const int64_t* doc_sent_
 }
 
 // (XCD-aware blocks, as materialize2: a partition's rows run on one XCD, so
-// its pair records and binned order are fetched into one L2, not all eight)
+// its pair records and binned order are fetched into one L2, not all eight;
+// against blocks in plain order 3.35 vs 3.53 ms per launch,
+// profiles/r5_rowspan_xcd.txt)
 // RS_U consecutive 64-row chunks per wave, each metadata level loaded for all
 // of them before the next: a row's chain (partition -> bases -> binned
 // index -> pair record -> segment offsets) is ~6 dependent loads, and
-// RS_U chains in flight per wave instead of one
-#ifndef LDDL_ROWSPAN_U
-#define LDDL_ROWSPAN_U 2
-#endif
-constexpr int RS_U = LDDL_ROWSPAN_U;
+// RS_U chains in flight per wave instead of one (1 / 2 / 4 chunks: 3.32 /
+// 2.99 / 2.99 ms per launch, profiles/r6/rowspan_u/)
+constexpr int RS_U = 2;
 __global__ __launch_bounds__(256) void rowspan_kernel(MatParams M, int64_t total) {
+  const PackView& V = M.V;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t gbase =
-      (LDDL_ROWSPAN_XCD ? xcd_block(blockIdx.x, gridDim.x) * 4 + wv : (int64_t)blockIdx.x * 4 + wv) * 64 * RS_U;
+  const int64_t gbase = (xcd_block(blockIdx.x, gridDim.x) * 4 + wv) * 64 * RS_U;
   if (gbase >= total) return;
   int64_t g[RS_U], p[RS_U];
   bool in[RS_U];
@@ -418,44 +358,31 @@ __global__ __launch_bounds__(256) void rowspan_kernel(MatParams M, int64_t total
     in[u] = g[u] < total;
     p[u] = in[u] ? M.chunk_part[(gbase >> 6) + u] : 0;
   }
-  int64_t i[RS_U], pb[RS_U];
+  RowRef w[RS_U];  // (pb from chunk_parts_kernel's table: one load, not part_first_pair's two)
 #pragma unroll
   for (int u = 0; u < RS_U; ++u) {
-    if (in[u]) {
-      while (M.pair_base[p[u] + 1] <= g[u]) ++p[u];  // partitions of < 64 pairs
-    }
-    i[u] = in[u] ? g[u] - M.pair_base[p[u]] : 0;
-    pb[u] = in[u] ? M.part_pb[p[u]] : 0;
+    if (in[u]) p[u] = part_walk(V, p[u], g[u]);
+    w[u].i = in[u] ? g[u] - V.pair_base[p[u]] : 0;
+    w[u].pb = in[u] ? M.part_pb[p[u]] : 0;
   }
-  int32_t bi[RS_U];
 #pragma unroll
-  for (int u = 0; u < RS_U; ++u) bi[u] = in[u] ? M.binned[pb[u] + i[u]] : 0;
+  for (int u = 0; u < RS_U; ++u) w[u].rec = in[u] ? row_rec(V, w[u].pb, w[u].i) : 0;
   PairRec r[RS_U];
 #pragma unroll
-  for (int u = 0; u < RS_U; ++u) r[u] = M.pairs[in[u] ? pb[u] + bi[u] : 0];
+  for (int u = 0; u < RS_U; ++u) r[u] = V.pairs[w[u].rec];
 #pragma unroll
   for (int u = 0; u < RS_U; ++u) {
     if (!in[u]) continue;
-    const int32_t l0 = r[u].hi0 - r[u].lo0, l1 = r[u].hi1 - r[u].lo1;
-    M.out_src0[g[u]] = l0 > 0 ? M.fs_dense[r[u].fs0] + r[u].lo0 : 0;
-    M.out_src1[g[u]] = l1 > 0 ? M.fs_dense[r[u].fs1] + r[u].lo1 : 0;
-    if (M.out_tok_off) {
-      const int64_t off = M.tok_base[p[u]] + M.tok_local[pb[u] + i[u]];
-      M.out_tok_off[g[u]] = off;
-      if (g[u] == total - 1) M.out_tok_off[total] = off + r[u].num_tokens;
-    }
-    M.out_len0[g[u]] = (uint16_t)l0;
-    M.out_len1[g[u]] = (uint16_t)l1;
-    M.out_flags[g[u]] = (uint8_t)r[u].flags;
-    const int32_t bb = ((int32_t)r[u].num_tokens - 1) / M.bin_size;
-    M.out_bin[g[u]] = (uint8_t)(bb > M.nbins - 1 ? M.nbins - 1 : bb);
-    M.out_part[g[u]] = p[u];
+    const RowDesc x = row_desc(V, r[u]);
+    M.out_src0[g[u]] = x.src0;
+    M.out_src1[g[u]] = x.src1;
+    store_row_meta(M, g[u], p[u], r[u], x, total, [&] { return row_tok_off(V, p[u], w[u]); });
   }
 }
 
 hipError_t launch_row_spans(const MatParams& M, int64_t total_pairs, hipStream_t s) {
   int64_t nblk = (total_pairs + 256 * RS_U - 1) / (256 * RS_U);
-  if (LDDL_ROWSPAN_XCD && nblk >= 64) nblk = (nblk + 7) & ~(int64_t)7;  // xcd_block: 8 equal ranges (extra blocks exit)
+  if (nblk >= 64) nblk = (nblk + 7) & ~(int64_t)7;  // xcd_block: 8 equal ranges (extra blocks exit)
   hipLaunchKernelGGL(rowspan_kernel, dim3((unsigned)nblk), dim3(256), 0, s, M, total_pairs);
   return hipGetLastError();
 }
@@ -620,27 +547,19 @@ __global__ __launch_bounds__(256) void sent_special_kernel(const uint16_t* ids, 
 // so the wave keeps four chains in flight.
 __global__ __launch_bounds__(256) void masked_lm_kernel(MlmParams M) {
   const int sl = threadIdx.x & 15;
-  const int64_t total = M.pair_base[M.n_part];
+  const int64_t total = M.V.pair_base[M.V.n_part];
   const int64_t ng = (int64_t)gridDim.x * 16;  // row groups of 16 lanes
   for (int64_t g = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4); g < total; g += ng) {
     const int64_t p = M.row_part[g];  // (materialize wrote every row's partition)
-    const int64_t i = g - M.pair_base[p];
-    const int64_t pb = (int64_t)M.dup * M.doc_sent_off[M.part_doc_off[p]];
-    const int64_t ref = M.mref[pb + M.binned[pb + i]];
-    const int nm = (int)((uint64_t)ref >> 48);
-    const int64_t aoff = ref & ((int64_t(1) << 48) - 1);
-    const int64_t ooff = M.mask_base[p] + M.mloc[pb + i];
+    const MaskRef m = mask_ref(M, p, row_ref(M.V, p, g));
     uint16_t* row = M.tokens + M.tok_off[g];
-    if (sl == 0) {
-      M.out_off[g] = ooff;
-      if (g == total - 1) M.out_off[total] = ooff + nm;
-    }
-    for (int k = sl; k < nm; k += 16) {
-      const uint32_t e = M.marena[aoff + k];
+    if (sl == 0) store_mask_off(M, g, total, m);
+    for (int k = sl; k < m.nm; k += 16) {
+      const uint32_t e = M.marena[m.aoff + k];
       const uint32_t pos = e & 0xFFFFu, nid = e >> 16;
       const uint16_t label = row[pos];
-      M.out_pos[ooff + k] = (uint16_t)pos;
-      M.out_label[ooff + k] = label;
+      M.out_pos[m.ooff + k] = (uint16_t)pos;
+      M.out_label[m.ooff + k] = label;
       if (nid != MLM_KEEP) row[pos] = (uint16_t)nid;
     }
   }
@@ -670,33 +589,27 @@ __global__ __launch_bounds__(256) void masked_lm_spans_kernel(MlmParams M) {
   __shared__ RowLds R[4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   RowLds& L = R[wv];
-  const int64_t total = M.pair_base[M.n_part];
+  const int64_t total = M.V.pair_base[M.V.n_part];
   const int64_t nw = (int64_t)gridDim.x * 4;
   for (int64_t g0 = ((int64_t)blockIdx.x * 4 + wv) * 64; g0 < total; g0 += nw * 64) {
     const int64_t g = g0 + lane;
     int nm = 0;
     if (g < total) {
       const int64_t p = M.row_part[g];
-      const int64_t i = g - M.pair_base[p];
-      const int64_t pb = (int64_t)M.dup * M.doc_sent_off[M.part_doc_off[p]];
-      const int64_t ref = M.mref[pb + M.binned[pb + i]];
-      nm = (int)((uint64_t)ref >> 48);
-      const int64_t ooff = M.mask_base[p] + M.mloc[pb + i];
-      L.aoff[lane] = ref & ((int64_t(1) << 48) - 1);
-      L.ooff[lane] = ooff;
+      const MaskRef m = mask_ref(M, p, row_ref(M.V, p, g));
+      nm = m.nm;
+      L.aoff[lane] = m.aoff;
+      L.ooff[lane] = m.ooff;
       L.a[lane] = M.src0[g];
       L.b[lane] = M.src1[g];
       L.l0[lane] = M.len0[g];
-      M.out_off[g] = ooff;
-      if (g == total - 1) M.out_off[total] = ooff + nm;
+      store_mask_off(M, g, total, m);
     }
     const int incl = wave_incl_add(nm);
     L.pre[lane] = incl - nm;
     if (lane == 63) L.pre[64] = incl;
     const int T = lane_get(incl, 63);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
     int r = 0;  // this lane's row cursor (positions rise with t)
     constexpr int U = MLM_SPAN_UNROLL;
     for (int t0 = 0; t0 < T; t0 += 64 * U) {
@@ -734,9 +647,7 @@ __global__ __launch_bounds__(256) void masked_lm_spans_kernel(MlmParams M) {
         }
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync();
   }
 }
 
@@ -747,17 +658,15 @@ hipError_t launch_sent_special(const uint16_t* ids, const int64_t* tok_off, cons
 }
 
 // masked_lm_spans_kernel's grid: up to one 64-row group per wave (blocks of 4
-// waves), capped at LDDL_MLM_GRID blocks -- the hardware then balances the
+// waves), capped at MLM_GRID blocks -- the hardware then balances the
 // launch instead of a fixed grid-stride share per wave (4096 blocks: 424.5,
 // 65 536: 420.8 ms per masked step, profiles/r6/v/)
-#ifndef LDDL_MLM_GRID
-#define LDDL_MLM_GRID (1 << 20)
-#endif
+constexpr int64_t MLM_GRID = 1 << 20;
 hipError_t launch_masked_lm(const MlmParams& M, int64_t n_rows, hipStream_t s) {
   if (M.tokens) {
     hipLaunchKernelGGL(masked_lm_kernel, dim3(2048), dim3(256), 0, s, M);
   } else {
-    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, LDDL_MLM_GRID));
+    const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n_rows + 255) / 256, MLM_GRID));
     hipLaunchKernelGGL(masked_lm_spans_kernel, dim3((unsigned)grid), dim3(256), 0, s, M);
   }
   return hipGetLastError();
@@ -771,7 +680,7 @@ hipError_t launch_materialize(const MatParams& M, int64_t total_pairs, int64_t n
     if (nblk >= 64) nblk = (nblk + 7) & ~(int64_t)7;  // xcd_block: 8 equal ranges (extra blocks exit)
     hipLaunchKernelGGL(materialize2_kernel, dim3((unsigned)nblk), dim3(256), 0, s, M, total_pairs, n_dense);
   } else {
-    const int64_t grid = (M.n_part + 3) / 4;  // one wave per partition
+    const int64_t grid = (M.V.n_part + 3) / 4;  // one wave per partition
     hipLaunchKernelGGL(materialize_kernel, dim3((unsigned)grid), dim3(256), 0, s, M);
   }
   return hipGetLastError();

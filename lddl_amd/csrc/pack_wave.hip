@@ -20,6 +20,7 @@
 // arrays in global memory (wave-uniform branch).
 #include "common.h"
 #include "pack.h"
+#include "pack_row.h"
 #include "wave.h"
 
 #include <cmath>
@@ -73,24 +74,6 @@ size_t pack_dyn_bytes(int cap_lens, int cap_docs, int cap_pairs, bool mask) {
   return 2 * (size_t)cap_lens + 4 * (size_t)cap_docs + 4 * (size_t)cap_pairs + (mask ? 4 * (size_t)(cap_lens / 32 + 2) : 0);
 }
 
-__device__ __forceinline__ void wsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// global writes of this wave visible to its later reads (other lanes)
-__device__ __forceinline__ void gsync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-__device__ __forceinline__ int wscan_incl(int v, int lane) {
-  (void)lane;
-  return wave_incl_add(v);
-}
-
 __device__ __forceinline__ int wsum(int v) { return lane_get(wave_incl_add(v), 63); }
 
 // a wave-uniform value copied into a VGPR (v_mov): arithmetic on it runs on
@@ -127,9 +110,9 @@ __device__ __attribute__((noinline)) void pack_mt_refill(lds_u32* mt, int lane) 
       const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
       v = m ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
     }
-    wsync();
+    wave_sync();
     if (i < MT_N) mt[i] = v;
-    wsync();
+    wave_sync();
   }
 }
 
@@ -202,7 +185,7 @@ struct WaveRng {
   // partition (624 words, coalesced), the next draw twists
   __device__ __forceinline__ void load(const uint32_t* __restrict__ st) {
     for (int c = lane; c < MT_N; c += 64) L.mt[c] = st[c];
-    wsync();
+    wave_sync();
     idx = MT_N;
   }
 
@@ -348,7 +331,7 @@ struct WaveRng {
       idx += end + 1;
       q -= s;
     }
-    wsync();
+    wave_sync();
   }
 
   // create_masked_lm_predictions' replacement choices for nm picks
@@ -425,7 +408,7 @@ struct WaveRng {
         idx += pos;
       }
     }
-    wsync();
+    wave_sync();
   }
 };
 
@@ -441,7 +424,7 @@ struct WaveRng {
 // dependent global round trip per swap.
 __device__ __forceinline__ void shuffle_global(WaveRng& rng, int np, int32_t* order, int32_t* jq, int lane) {
   rng.shuffle_draws_inl(np, jq);  // (inline: a call's clobbers cost the caller's SGPRs as spills)
-  gsync();
+  group_sync();
   for (int qb = np - 1; qb >= 1; qb -= 64) {
     const int qmin = max(qb - 63, 1);
     const int q = qb - lane;
@@ -472,7 +455,7 @@ __device__ __forceinline__ void shuffle_global(WaveRng& rng, int np, int32_t* or
     }
     if (vq) order[q] = va;
     if (own) order[j] = vb;
-    gsync();
+    group_sync();
   }
 }
 
@@ -488,7 +471,7 @@ __device__ __forceinline__ void pack_order_nt(int32_t* order, const PairRec* out
     const int rec = order[k];
     order[k] = rec | ((int)out[rec].num_tokens << PACKED_REC_BITS);
   }
-  gsync();
+  group_sync();
 }
 
 // smallest k in [k0, n) with (k == n-1) or (sum lens[k0..k] >= target);
@@ -502,7 +485,7 @@ __device__ __forceinline__ int find_fill(const GET& len_at, int k0, int n, int t
   for (int k = k0; k < n; k += 64) {
     const int kk = k + lane;
     const int l = kk < n ? len_at(kk) : (1 << 20);
-    const int ps = base + wscan_incl(l, lane);
+    const int ps = base + wave_incl_add(l);
     const uint64_t m = __ballot(ps >= target);
     if (m) {
       const int j = min((int)__builtin_ctzll(m), n - 1 - k);
@@ -540,6 +523,103 @@ __device__ __forceinline__ int find_fill_reg(int dps, int dex, int tot, int k0, 
   return j;
 }
 
+// ---- what the two packers share around their generate loops --------------
+// the partition a packer wave works on: ndoc documents from d0, nsent
+// sentences from s0, its pair arrays from pb
+struct PartOpen {
+  int64_t d0, s0, pb;
+  int nsent, ndoc;
+};
+__device__ __forceinline__ PartOpen open_part(const PackParams& P, int64_t p) {
+  PartOpen O;
+  const int64_t d1 = P.part_doc_off[p + 1];
+  O.d0 = P.part_doc_off[p];
+  O.s0 = P.doc_sent_off[O.d0];
+  O.pb = (int64_t)P.dup * O.s0;
+  O.nsent = (int)(P.doc_sent_off[d1] - O.s0);
+  O.ndoc = (int)(d1 - O.d0);
+  return O;
+}
+
+// random.shuffle(partition_pairs) over the identity order of np records: in
+// LDS (D.order) when LDSOK and they fit, else in P.order
+template <bool LDSOK>
+__device__ __forceinline__ void shuffle_pairs(const PackParams& P, const PartOpen& O, const PackDyn& D, WaveRng& rng,
+                                              int np, int lane) {
+  const bool ores = LDSOK && np <= P.cap_pairs;
+  int32_t* gorder = P.order + O.pb;
+  if (ores) for (int k = lane; k < np; k += 64) D.order[k] = (uint16_t)k;
+  else for (int k = lane; k < np; k += 64) gorder[k] = k;
+  group_sync();
+  if (ores) {
+    // lane 0 alone touches the order array here (program order suffices)
+    for (int k = np - 1; k >= 1; --k) {
+      const int j = (int)rng.randbelow((uint32_t)(k + 1));
+      if (lane == 0) { const uint16_t t = D.order[k]; D.order[k] = D.order[j]; D.order[j] = t; }
+    }
+  } else {
+    shuffle_global(rng, np, gorder, P.binned + O.pb, lane);  // (binned: draw scratch until binning)
+  }
+  group_sync();
+}
+
+// stable bin partition of the shuffled order + token offsets (MASK: and the
+// masked-entry offsets), then the partition's totals
+template <int MASK, bool LDSOK>
+__device__ __forceinline__ void bin_pairs(const PackParams& P, const PartOpen& O, const PackDyn& D, int64_t p, int np,
+                                          int lane) {
+  const int64_t pb = O.pb;
+  const PairRec* out = P.pairs + pb;
+  int32_t* gorder = P.order + pb;
+  const bool ores = LDSOK && np <= P.cap_pairs;
+  const bool packed = !ores && order_packable(np, P.max_seq);
+  if (packed) pack_order_nt(gorder, out, np, lane);
+  auto ord_at = [&](int k) -> int { return ores ? (int)D.order[k] : packed ? gorder[k] & ((1 << PACKED_REC_BITS) - 1) : gorder[k]; };
+  auto ntk_at = [&](int k, int rec) -> int {
+    return ores ? (int)D.ntk[rec] : packed ? (int)((uint32_t)gorder[k] >> PACKED_REC_BITS) : (int)out[rec].num_tokens;
+  };
+  const int nb = P.nbins;
+  int32_t* binned = P.binned + pb;
+  int64_t* tl = P.tok_local + pb;
+  int pos = 0;
+  int64_t acc = 0, macc = 0;
+  for (int b = 0; b < nb; ++b) {
+    int cnt = 0;
+    for (int k = 0; k < np; k += 64) {
+      const int kk = k + lane;
+      int rec = 0, nt = 0;
+      bool in = false;
+      if (kk < np) {
+        rec = ord_at(kk);
+        nt = ntk_at(kk, rec);
+        in = bin_of(nt, P.bin_size, nb) == b;
+      }
+      const uint64_t m = __ballot(in);
+      const int before = __popcll(m & ((1ull << lane) - 1ull));
+      const int tinc = wave_incl_add(in ? nt : 0);
+      if (in) {
+        binned[pos + before] = rec;
+        tl[pos + before] = acc + tinc - nt;
+      }
+      if constexpr (MASK) {
+        const int nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
+        const int minc = wave_incl_add(nmk);
+        if (in) P.mloc[pb + pos + before] = macc + minc - nmk;
+        macc += lane_get(minc, 63);
+      }
+      pos += __popcll(m);
+      cnt += __popcll(m);
+      acc += lane_get(tinc, 63);
+    }
+    if (lane == 0) P.bin_count[p * nb + b] = cnt;
+  }
+  if (lane == 0) {
+    P.part_npairs[p] = np;
+    P.part_ntok[p] = acc;
+    if (MASK) P.part_nmask[p] = macc;
+  }
+}
+
 // LDSOK = false: every LDS capacity is 0 (the default), the arrays are in
 // global memory and the LDS/global branches compile away
 // DBG: the phase stamps (LDDL_PACK_DEBUG=1) compiled in; the production
@@ -559,11 +639,10 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
   const int lane = threadIdx.x;
   const int64_t p = blockIdx.x;
   if (p >= P.n_part) return;
-  const int64_t d0 = P.part_doc_off[p], d1 = P.part_doc_off[p + 1];
-  const int64_t s0 = P.doc_sent_off[d0], s1 = P.doc_sent_off[d1];
-  const int64_t pb = (int64_t)P.dup * s0;
+  const PartOpen O = open_part(P, p);
+  const int64_t d0 = O.d0, s0 = O.s0, pb = O.pb;
   const int64_t base = P.sent_off[0];
-  const int nsent = (int)(s1 - s0), ndoc = (int)(d1 - d0);
+  const int nsent = O.nsent, ndoc = O.ndoc;
   // optional phase stamps (wave-uniform branch): filter, LDS fill, seed,
   // pair generation, shuffle, binning; masking: candidates, shuffle draws,
   // pick trace, 80/10/10 choices, sorted writes
@@ -599,7 +678,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
       int n = 0;
       if (kk < nsent) n = P.ntok[s0 + kk];
       const int keep = (kk < nsent && n > 0) ? 1 : 0;
-      const int incl = wscan_incl(keep, lane);
+      const int incl = wave_incl_add(keep);
       bool sp = false;
       if (kk < nsent) {
         const int slot = run + incl - keep;
@@ -620,9 +699,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
     }
     if (lane == 0) kept_before[nsent] = run;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  group_sync();
   // documents with >= 1 kept sentence, compacted
   int nd = 0;
   for (int k = 0; k < ndoc; k += 64) {
@@ -635,7 +712,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
       cnt = last - first;
     }
     const int keep = (kk < ndoc && cnt > 0) ? 1 : 0;
-    const int incl = wscan_incl(keep, lane);
+    const int incl = wave_incl_add(keep);
     if (keep) {
       const int di = nd + incl - 1;
       P.fd_first[d0 + di] = s0 + first;
@@ -644,9 +721,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
     nd += lane_get(incl, 63);
   }
   const int nfs = kept_before[nsent];
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  group_sync();
   PW_STAMP(0)
   const bool lres = LDSOK && nfs <= P.cap_lens && nd <= P.cap_docs;
   if (lres) {
@@ -662,7 +737,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
       }
     }
   }
-  wsync();
+  wave_sync();
   PW_STAMP(1)
   // slot-relative accessors
   // global-only variant: the documents (the random-next lookups) in static LDS
@@ -673,7 +748,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
         DL.dfirst[k] = (uint16_t)(P.fd_first[d0 + k] - s0);
         DL.dn[k] = (uint16_t)P.fd_n[d0 + k];
       }
-      wsync();
+      wave_sync();
     }
   }
   auto len_at = [&](int k) -> int { return lres ? (int)D.lens[k] : P.fs_ntok[s0 + k]; };
@@ -942,7 +1017,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
             };
             seg(fa, a_end, alo, ahi, 1);
             seg(fb, n1, blo, bhi, 2 + la2);
-            gsync();  // the list's global writes visible to the trace's reads (other lanes)
+            group_sync();  // the list's global writes visible to the trace's reads (other lanes)
           }
           // random.shuffle(cand_indexes): record the swaps, then undo them
           // per picked slot (lane per pick) instead of permuting the list
@@ -978,7 +1053,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
             static_assert(offsetof(MLT, mid) == offsetof(MLT, mpos) + sizeof(ML.mpos), "mid follows mpos");
             static_assert(sizeof(ML.mpos) + sizeof(ML.mid) >= 2 * MCAP, "F spans mpos + mid");
             for (int k = lane; k < m; k += 64) F[k] = 0xFFFFu;
-            wsync();
+            wave_sync();
             PW_STAMP(8)  // (trace sub-phases: the list reset above -> m_trace; F build -> 11, chains -> 12)
             for (int qb = nm + ((m - nm - 1) & ~63); qb >= nm; qb -= 64) {
               const int q = qb + lane;
@@ -990,9 +1065,9 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
               }
               while (__ballot(pend) != 0) {
                 if (pend) F[j] = (uint16_t)q;
-                wsync();
+                wave_sync();
                 if (pend) pend = (uint32_t)F[j] > (uint32_t)q;
-                wsync();
+                wave_sync();
               }
             }
             PW_STAMP(11)
@@ -1013,7 +1088,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
             const int end = split ? nm : m;
             if (lane == 0) ML.jb[0] = 0;
             if (end + lane < tr8) ML.jb[end + lane] = (uint16_t)((end + lane) & 7);
-            wsync();
+            wave_sync();
             const uint4* jb4 = reinterpret_cast<const uint4*>(ML.jb);
             auto elem = [&](int q) { return split ? (int)ML.jb[nm8 + q] : q; };
             // one pick per lane, 64 picks per pass: swaps below a pass's first
@@ -1035,7 +1110,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
               }
               const int qa = d + tr8;
               const int ea = pk < nm ? elem(qa) : 0;
-              wsync();  // (mpos overlaps F: every lane has read its chains)
+              wave_sync();  // (mpos overlaps F: every lane has read its chains)
               if (pk < nm) ML.mpos[pk] = pick_pos(ea);
             }
           }
@@ -1060,12 +1135,12 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
             uint32_t* bm = reinterpret_cast<uint32_t*>(ML.jb);
             uint32_t* pre = bm + NW;
             for (int w = lane; w < NW; w += 64) bm[w] = 0;
-            wsync();
+            wave_sync();
             for (int pk = lane; pk < nm; pk += 64) {
               const uint32_t pos = ML.mpos[pk];
               atomicOr(&bm[pos >> 5], 1u << (pos & 31));
             }
-            wsync();
+            wave_sync();
             uint32_t carry = 0;
             for (int w0 = 0; w0 < NW; w0 += 64) {
               const uint32_t c = w0 + lane < NW ? (uint32_t)__popc(bm[w0 + lane]) : 0u;
@@ -1073,7 +1148,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
               if (w0 + lane < NW) pre[w0 + lane] = carry + x - c;
               carry += lane_get(x, 63);
             }
-            wsync();
+            wave_sync();
             for (int pk = lane; pk < nm; pk += 64) {
               if (!fits) break;
               const uint32_t pos = ML.mpos[pk];
@@ -1083,7 +1158,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
           }
           mref = mcur | ((int64_t)nm << 48);
           mcur += nm;
-          wsync();
+          wave_sync();
           PW_STAMP(10)
         }
         {
@@ -1114,77 +1189,10 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
     if (lane == 0) { P.part_npairs[p] = 0; P.part_ntok[p] = 0; if (MASK) P.part_nmask[p] = 0; }
     return;
   }
-  wsync();
-  // ---- random.shuffle(partition_pairs) -----------------------------------
-  const bool ores = LDSOK && np <= pcap;
-  int32_t* gorder = P.order + pb;
-  if (ores) for (int k = lane; k < np; k += 64) D.order[k] = (uint16_t)k;
-  else for (int k = lane; k < np; k += 64) gorder[k] = k;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  if (ores) {
-    // lane 0 alone touches the order array here (program order suffices)
-    for (int k = np - 1; k >= 1; --k) {
-      const int j = (int)rng.randbelow((uint32_t)(k + 1));
-      if (lane == 0) { const uint16_t t = D.order[k]; D.order[k] = D.order[j]; D.order[j] = t; }
-    }
-  } else {
-    shuffle_global(rng, np, gorder, P.binned + pb, lane);  // (binned: draw scratch until binning)
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  wave_sync();
+  shuffle_pairs<LDSOK>(P, O, D, rng, np, lane);
   PW_STAMP(4)
-  const bool packed = !ores && order_packable(np, P.max_seq);
-  if (packed) pack_order_nt(gorder, out, np, lane);
-  auto ord_at = [&](int k) -> int { return ores ? (int)D.order[k] : packed ? gorder[k] & ((1 << PACKED_REC_BITS) - 1) : gorder[k]; };
-  auto ntk_at = [&](int k, int rec) -> int {
-    return ores ? (int)D.ntk[rec] : packed ? (int)((uint32_t)gorder[k] >> PACKED_REC_BITS) : (int)out[rec].num_tokens;
-  };
-  // ---- stable bin partition + token offsets -------------------------------
-  const int nb = P.nbins;
-  int32_t* binned = P.binned + pb;
-  int64_t* tl = P.tok_local + pb;
-  int pos = 0;
-  int64_t acc = 0, macc = 0;
-  for (int b = 0; b < nb; ++b) {
-    int cnt = 0;
-    for (int k = 0; k < np; k += 64) {
-      const int kk = k + lane;
-      int rec = 0, nt = 0;
-      bool in = false;
-      if (kk < np) {
-        rec = ord_at(kk);
-        nt = ntk_at(kk, rec);
-        int bb = (nt - 1) / P.bin_size;
-        bb = bb > nb - 1 ? nb - 1 : bb;
-        in = bb == b;
-      }
-      const uint64_t m = __ballot(in);
-      const int before = __popcll(m & ((1ull << lane) - 1ull));
-      const int tinc = wscan_incl(in ? nt : 0, lane);
-      if (in) {
-        binned[pos + before] = rec;
-        tl[pos + before] = acc + tinc - nt;
-      }
-      if constexpr (MASK) {
-        const int nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
-        const int minc = wscan_incl(nmk, lane);
-        if (in) P.mloc[pb + pos + before] = macc + minc - nmk;
-        macc += lane_get(minc, 63);
-      }
-      pos += __popcll(m);
-      cnt += __popcll(m);
-      acc += lane_get(tinc, 63);
-    }
-    if (lane == 0) P.bin_count[p * nb + b] = cnt;
-  }
-  if (lane == 0) {
-    P.part_npairs[p] = np;
-    P.part_ntok[p] = acc;
-    if (MASK) P.part_nmask[p] = macc;
-  }
+  bin_pairs<MASK, LDSOK>(P, O, D, p, np, lane);
   PW_STAMP(5)
   if (DBG && lane == 0) {
     for (int k = 0; k < 6; ++k) atomicAdd((unsigned long long*)&P.dbg[k], (unsigned long long)ph[k]);
@@ -1254,7 +1262,7 @@ __device__ __forceinline__ int find_over(const GET& len_at, int k0, int n, int s
   for (int k = k0; k < n; k += 64) {
     const int kk = k + lane;
     const int l = kk < n ? len_at(kk) : 0;
-    const int ps = base + wscan_incl(l, lane);
+    const int ps = base + wave_incl_add(l);
     const uint64_t m = __ballot(kk < n && (kk == stop || ps > limit));
     if (m) {
       const int j = __ffsll((unsigned long long)m) - 1;
@@ -1294,11 +1302,10 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
   const int lane = threadIdx.x;
   const int64_t p = blockIdx.x;
   if (p >= P.n_part) return;
-  const int64_t d0 = P.part_doc_off[p], d1 = P.part_doc_off[p + 1];
-  const int64_t s0 = P.doc_sent_off[d0], s1 = P.doc_sent_off[d1];
-  const int64_t pb = (int64_t)P.dup * s0;
+  const PartOpen O = open_part(P, p);
+  const int64_t d0 = O.d0, s0 = O.s0, pb = O.pb;
   const int64_t base = P.sent_off[0];
-  const int nsent = (int)(s1 - s0), ndoc = (int)(d1 - d0);
+  const int nsent = O.nsent, ndoc = O.ndoc;
   // ---- filter: kept segment slots (wave scan), kept documents ------------
   int32_t* kept_before = P.kept + s0 + p;
   {
@@ -1307,7 +1314,7 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
       const int kk = k + lane;
       const int n = kk < nsent ? P.ntok[s0 + kk] : 0;
       const int keep = (kk < nsent && n > 0) ? 1 : 0;
-      const int incl = wscan_incl(keep, lane);
+      const int incl = wave_incl_add(keep);
       if (kk < nsent) {
         const int slot = run + incl - keep;
         kept_before[kk] = slot;
@@ -1321,9 +1328,7 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
     }
     if (lane == 0) kept_before[nsent] = run;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  group_sync();
   // a document is kept when it has a kept code segment (len(CodePair) > 0,
   // pretrain_codebert.py:161); its first fd_nd kept slots are docstring
   int nd_docs = 0;
@@ -1338,7 +1343,7 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
       ndseg = kept_before[c] - first;
     }
     const int keep = (kk < ndoc && cnt - ndseg > 0) ? 1 : 0;
-    const int incl = wscan_incl(keep, lane);
+    const int incl = wave_incl_add(keep);
     if (keep) {
       const int di = nd_docs + incl - 1;
       P.fd_first[d0 + di] = s0 + first;
@@ -1347,9 +1352,7 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
     }
     nd_docs += lane_get(incl, 63);
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  group_sync();
   auto len_abs = [&](int64_t slot) -> int { return P.fs_ntok[slot]; };
 
   WaveRng rng{L, lane, MT_N};
@@ -1421,55 +1424,10 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
     if (lane == 0) { P.part_npairs[p] = 0; P.part_ntok[p] = 0; }
     return;
   }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  // ---- random.shuffle(partition_pairs) (:476) ------------------------------
-  int32_t* gorder = P.order + pb;
-  for (int k = lane; k < np; k += 64) gorder[k] = k;
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_s_waitcnt(0);
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-  shuffle_global(rng, np, gorder, P.binned + pb, lane);  // (binned: draw scratch until binning)
-  const bool packed = order_packable(np, P.max_seq);
-  if (packed) pack_order_nt(gorder, out, np, lane);
-  // ---- stable bin partition + token offsets ---------------------------------
-  const int nb = P.nbins;
-  int32_t* binned = P.binned + pb;
-  int64_t* tl = P.tok_local + pb;
-  int pos = 0;
-  int64_t acc = 0;
-  for (int b = 0; b < nb; ++b) {
-    int cnt = 0;
-    for (int k = 0; k < np; k += 64) {
-      const int kk = k + lane;
-      int rec = 0, nt = 0;
-      bool in = false;
-      if (kk < np) {
-        const int v = gorder[kk];
-        rec = packed ? v & ((1 << PACKED_REC_BITS) - 1) : v;
-        nt = packed ? (int)((uint32_t)v >> PACKED_REC_BITS) : (int)out[rec].num_tokens;
-        int bb = (nt - 1) / P.bin_size;
-        bb = bb > nb - 1 ? nb - 1 : bb;
-        in = bb == b;
-      }
-      const uint64_t m = __ballot(in);
-      const int before = __popcll(m & ((1ull << lane) - 1ull));
-      const int tinc = wscan_incl(in ? nt : 0, lane);
-      if (in) {
-        binned[pos + before] = rec;
-        tl[pos + before] = acc + tinc - nt;
-      }
-      pos += __popcll(m);
-      cnt += __popcll(m);
-      acc += lane_get(tinc, 63);
-    }
-    if (lane == 0) P.bin_count[p * nb + b] = cnt;
-  }
-  if (lane == 0) {
-    P.part_npairs[p] = np;
-    P.part_ntok[p] = acc;
-  }
+  group_sync();
+  // random.shuffle(partition_pairs) (:476) and the binning: the BERT packer's, arrays in global memory
+  shuffle_pairs<false>(P, O, PackDyn{}, rng, np, lane);
+  bin_pairs<0, false>(P, O, PackDyn{}, p, np, lane);
 }
 
 hipError_t launch_pack_codebert_wave(const PackParams& P, hipStream_t s) {

@@ -34,15 +34,10 @@ struct RenderParams {
 };
 
 struct RowDocParams {
-  const PairRec* pairs;
-  const int32_t* binned;
-  const int64_t* pair_base;
+  PackView V;
   const int64_t* fs_base;
   const int64_t* sent_off;
-  const int64_t* doc_sent_off;
-  const int64_t* part_doc_off;
-  int64_t n_part, n_rows;
-  int32_t dup;
+  int64_t n_rows;
   int64_t* out_doc;
 };
 

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pack_row.h"
 #include "render.h"
 #include "wave.h"
 
@@ -140,29 +141,24 @@ __global__ __launch_bounds__(256) void render_bytes_kernel(RenderParams R) {
 __global__ __launch_bounds__(256) void row_docs_kernel(RowDocParams D) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < D.n_rows; g += stride) {
-    int64_t plo = 0, phi = D.n_part - 1;
-    while (plo < phi) {
-      const int64_t mid = (plo + phi + 1) >> 1;
-      if (D.pair_base[mid] <= g) plo = mid;
-      else phi = mid - 1;
-    }
-    const int64_t p = plo;
-    const int64_t pb = (int64_t)D.dup * D.doc_sent_off[D.part_doc_off[p]];
-    const PairRec r = D.pairs[pb + D.binned[pb + (g - D.pair_base[p])]];
+    const PackView& V = D.V;
+    const int64_t p = part_of_row(V, g);
+    PairRec r;
+    pair_of_row(V, p, g, r);
     // seg0 (A / doc) is the row's own document; a CodeBERT row without a doc
     // segment has only seg1 (BERT's B may come from a random document)
     const int64_t x = D.fs_base[r.hi0 > r.lo0 ? r.fs0 : r.fs1] + D.sent_off[0];
     // sentences of partition p
-    int64_t lo = D.doc_sent_off[D.part_doc_off[p]], hi = D.doc_sent_off[D.part_doc_off[p + 1]] - 1;
+    int64_t lo = V.doc_sent_off[V.part_doc_off[p]], hi = V.doc_sent_off[V.part_doc_off[p + 1]] - 1;
     while (lo < hi) {
       const int64_t mid = (lo + hi + 1) >> 1;
       if (D.sent_off[mid] <= x) lo = mid;
       else hi = mid - 1;
     }
-    int64_t dlo = D.part_doc_off[p], dhi = D.part_doc_off[p + 1] - 1;
+    int64_t dlo = V.part_doc_off[p], dhi = V.part_doc_off[p + 1] - 1;
     while (dlo < dhi) {
       const int64_t mid = (dlo + dhi + 1) >> 1;
-      if (D.doc_sent_off[mid] <= lo) dlo = mid;
+      if (V.doc_sent_off[mid] <= lo) dlo = mid;
       else dhi = mid - 1;
     }
     D.out_doc[g] = dlo;

@@ -58,6 +58,21 @@ __device__ __forceinline__ int wave_shr1(int x) { return (int)dpp0<DPP_WAVE_SHR1
 // lane l receives lane l+1's value, lane 63 receives 0
 __device__ __forceinline__ uint32_t wave_shl1(uint32_t x) { return dpp0<DPP_WAVE_SHL1>(x); }
 
+// this wave's LDS / global writes visible to its other lanes' later reads
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the same at workgroup scope, waiting for the outstanding memory operations:
+// global writes of a one-wave block visible to its later reads (other lanes)
+__device__ __forceinline__ void group_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_s_waitcnt(0);
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
 // value of a (wave-uniform) lane
 __device__ __forceinline__ uint32_t lane_get(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
 __device__ __forceinline__ int lane_get(int x, int l) { return __builtin_amdgcn_readlane(x, l); }

@@ -186,25 +186,71 @@ def test_codebert_end_to_end_vs_oracle(gpu, monkeypatch, mat):
   assert g == len(rows)
 
 
+# partitions with zero docs and docs with empty sentences; partitions of fewer
+# than 64 rows share a wave of the readers that take 64 rows per wave
+MANY_DOCS = [[[5, 6, 7], [], [8, 9]], [[]], [[10] * 40, [11] * 30, [12] * 50], [[13] * 3]] * 20
+MANY_PDO = [0, 0, 5, 5, 17, 40, 80, 80]
+_many = {}
+
+
+def many_expected(masking):
+  """the oracle's rows of the corpus above (seq 64, dup 2, bin 16, seed 7) in
+  output order: (partition, A, B, is_random_next, document[, A', B', positions,
+  labels]); document = the global index of the document of A's first sentence
+  (A is never empty in a BERT row).  Computed once per masking mode."""
+  if masking not in _many:
+    exp = []
+    for p in range(len(MANY_PDO) - 1):
+      kept = [d for d in range(MANY_PDO[p], MANY_PDO[p + 1]) if any(MANY_DOCS[d])]
+      D = [[s for s in MANY_DOCS[d] if s] for d in kept]
+      prs = po.partition_pairs(D, 7 + p, lambda X, di, r: po.bert_pairs(X, di, 64, 0.1, r, MASK if masking else None), 2)
+      rr = [(p,) + po.pair_tokens(D, pr) + (kept[pr[0][0][0]],) + (tuple(pr[5]) if masking else ()) for pr in prs]
+      order, _ = po.binned_order([len(r[1]) + len(r[2]) + 3 for r in rr], 16, 4)
+      exp += [rr[i] for i in order]
+    _many[masking] = exp
+  return _many[masking]
+
+
+def test_many_partitions_oracle_shape():
+  """what makes the corpus sharp for a row -> partition resolver, from the
+  oracle alone: empty partitions, a partition of 1..63 rows, and a group of 64
+  consecutive rows that spans two partitions"""
+  part = [e[0] for e in many_expected(False)]
+  counts = np.bincount(part, minlength=len(MANY_PDO) - 1)
+  assert (counts == 0).sum() >= 3 and ((counts >= 1) & (counts <= 63)).any()
+  assert any(part[g] != part[min(g + 63, len(part) - 1)] for g in range(0, len(part), 64))
+
+
 @pytest.mark.parametrize('spans', [False, True])
 def test_many_partitions_and_empty_partitions(packer, spans):
-  # partitions with zero docs and docs with empty sentences; as span rows,
-  # partitions of fewer than 64 rows share a row-spans wave
-  docs = [[[5, 6, 7], [], [8, 9]], [[]], [[10] * 40, [11] * 30, [12] * 50], [[13] * 3]] * 20
-  pdo = [0, 0, 5, 5, 17, 40, 80, 80]
-  sh, ids, ntok = shards_from_docs(docs, part_doc_off=pdo)
+  sh, ids, ntok = shards_from_docs(MANY_DOCS, part_doc_off=MANY_PDO)
   res = packer.pack(sh, ids, ntok, target_seq_length=64, duplicate_factor=2, seed=7, bin_size=16, spans=spans)
   assert res.spans == spans
+  assert [(r[0], r[1], r[2], bool(r[3] & 1)) for r in res.rows()] == [e[:4] for e in many_expected(False)]
+
+
+@pytest.mark.parametrize('route', ['mat_algo1', 'row_docs', 'masked_lm', 'masked_lm_spans'])
+def test_many_partitions_every_reader(packer, monkeypatch, route):
+  """the same pack shape through the other readers of a pack result: the
+  wave-per-partition materialize, lddl_row_docs, and with masking lddl_masked_lm
+  over materialised rows and lddl_masked_lm_spans"""
+  from lddl_amd import writer
+  masking = route.startswith('masked')
+  if route == 'mat_algo1':
+    monkeypatch.setenv('LDDL_MAT_ALGO', '1')
+  exp = many_expected(masking)
+  sh, ids, ntok = shards_from_docs(MANY_DOCS, part_doc_off=MANY_PDO)
+  res = packer.pack(sh, ids, ntok, target_seq_length=64, duplicate_factor=2, seed=7, bin_size=16,
+                    masking=masking, spans=route == 'masked_lm_spans')
   rows = res.rows()
-  fdocs = [[s for s in d if s] for d in docs]
-  exp = []
-  for p in range(len(pdo) - 1):
-    D = [d for d in fdocs[pdo[p]:pdo[p + 1]] if d]
-    prs = po.partition_pairs(D, 7 + p, lambda X, di, r: po.bert_pairs(X, di, 64, 0.1, r), 2)
-    rr = [po.pair_tokens(D, pr) for pr in prs]
-    order, _ = po.binned_order([len(a) + len(b) + 3 for a, b, _ in rr], 16, 4)
-    exp += [(p,) + rr[i] for i in order]
-  assert [(r[0], r[1], r[2], bool(r[3] & 1)) for r in rows] == [(p, a, b, rn) for p, a, b, rn in exp]
+  assert [(r[0], bool(r[3] & 1)) for r in rows] == [(e[0], e[3]) for e in exp]
+  if route == 'row_docs':
+    assert writer.row_docs(packer, res).tolist() == [e[4] for e in exp]
+  if masking:  # the masked segments, positions and labels
+    assert res.n_masked == sum(len(e[7]) for e in exp)
+    assert [(r[1], r[2], r[6], r[7]) for r in rows] == [(list(e[5]), list(e[6]), list(e[7]), list(e[8])) for e in exp]
+  else:
+    assert [(r[1], r[2]) for r in rows] == [(e[1], e[2]) for e in exp]
 
 
 # ---------------------------------------------------------------- masking --

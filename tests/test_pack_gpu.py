@@ -404,19 +404,24 @@ def test_codebert_long_documents_vs_oracle(cpacker, seq, ssp, dup):
     ndoc.append(nds)
   pdo = [0, 13, 13, 40, 60]
   sh, ids, ntok = shards_from_docs(docs, ndoc, part_doc_off=pdo)
-  try:
-    exp, counts = codebert_oracle_rows(docs, ndoc, pdo, seq, ssp, dup, 77, seq // 4, 4)
-  except IndexError:
-    with pytest.raises(IndexError):
-      cpacker.pack(sh, ids, ntok, target_seq_length=seq, short_seq_prob=ssp, duplicate_factor=dup, seed=77,
-                   codebert=True, bin_size=seq // 4)
-    return
+  # All four parametrisations compare rows: the longest docstring line has 90
+  # tokens, below the seq - 3 = 125 at which a line taken whole leaves the code
+  # nothing (AssertionError) or less (IndexError), so the oracle raises in
+  # none -- decided here on the host, by calling it outside any try.  The
+  # error exits have their own corpora in test_pack_codebert_regimes_gpu.py.
+  assert max(len(s) for d, n in zip(docs, ndoc) for s in d[:n]) == 90 < seq - 3
+  exp, counts = codebert_oracle_rows(docs, ndoc, pdo, seq, ssp, dup, 77, seq // 4, 4)
   res = cpacker.pack(sh, ids, ntok, target_seq_length=seq, short_seq_prob=ssp, duplicate_factor=dup, seed=77,
                      codebert=True, bin_size=seq // 4)
   rows = res.rows()
-  assert len(rows) == len(exp)
+  assert len(rows) == len(exp) > 300
+  cls_id, sep_id = cpacker.tok.cls_id, cpacker.tok.sep_id
   for (p, a, b, fl, bn, tok), e in zip(rows, exp):
     assert (p, a, b, len(tok)) == e
+    # the whole row: [CLS] doc [SEP] code [SEP] with a docstring (3 special tokens), else [CLS] code [SEP]
+    assert fl == (2 if e[3] - len(a) - len(b) == 3 else 0)
+    assert tok == [cls_id] + (a + [sep_id] if fl & 2 else []) + b + [sep_id]
+    assert bn == po.bin_of(e[3], seq // 4, 4)
   assert res.bin_count.cpu().numpy().tolist() == counts
 
 

@@ -73,6 +73,63 @@ def test_codebert_pairs_match_reference(k):
     assert (dt, ct, len(dt) + len(ct) + special) == (row['doc'], row['code'], row['num_tokens'])
 
 
+REGIMES = load('pack_codebert_regimes.json.gz')
+
+
+def regime_corpus(case, corpus):
+  """the corpus of tests/codebert_regimes.py the fixture was made from (the
+  fixture keeps its segment lengths, not its ids)"""
+  docs, ndoc, pdo = corpus
+  assert [[len(s) for s in d] for d in docs] == case['corpus'] and list(ndoc) == case['ndoc']
+  assert list(pdo) == case['part_doc_off']
+  return docs, ndoc, pdo
+
+
+@pytest.mark.parametrize('k', range(len(REGIMES['cases'])))
+def test_codebert_regimes_match_reference(k):
+  """The regime corpora (unflushed docstring, flush in the second window,
+  lost tail, the 16-token drop rule, ...): po.codebert_pairs against the
+  reference's rows, per partition in the shuffled order."""
+  import codebert_regimes as cr
+  case = REGIMES['cases'][k]
+  seq, ssp = case['seq'], case['ssp']
+  assert (seq, ssp) == cr.CONFIGS[k] and case['dup'] == cr.DUP
+  assert case['seed'] == cr.PACK_SEEDS.get((seq, ssp), cr.PACK_SEED)
+  docs, ndoc, pdo = regime_corpus(case, cr.corpus(seq))
+  for p, exp in enumerate(case['parts']):
+    D, nd = cr.partition_docs(docs, ndoc, pdo, p)
+    pairs = po.partition_pairs(D, case['seed'] + p, lambda X, di, r: po.codebert_pairs(X, nd, di, seq, ssp, r),
+                               case['dup'])
+    got = []
+    for (doc_s, code_s, dw, cw) in pairs:
+      dt = [t for (d, s) in doc_s for t in D[d][s]][dw[0]:dw[1]]
+      ct = [t for (d, s) in code_s for t in D[d][s]][cw[0]:cw[1]]
+      got.append([dt, ct, len(dt) + len(ct) + (3 if nd[code_s[0][0]] else 2)])
+    assert got == exp, p
+  # the same rows as the GPU tests take them: binned
+  assert cr.golden_rows(case) == cr.oracle_rows(seq, ssp)[1:]
+
+
+@pytest.mark.parametrize('k', range(len(REGIMES['errors'])))
+def test_codebert_regime_errors_match_reference(k):
+  """the reference raises exactly that exception, in partition 1 alone; so does the oracle"""
+  import codebert_regimes as cr
+  case = REGIMES['errors'][k]
+  seq, ssp, exc = case['seq'], case['ssp'], case['error']
+  assert (seq, ssp, exc) == cr.ERROR_CONFIGS[k] and case['errors'] == [None, exc, None]
+  docs, ndoc, pdo = regime_corpus(case, cr.error_corpus(seq, exc))
+  for p in range(3):
+    D, nd = cr.partition_docs(docs, ndoc, pdo, p)
+
+    def run():
+      po.partition_pairs(D, case['seed'] + p, lambda X, di, r: po.codebert_pairs(X, nd, di, seq, ssp, r), case['dup'])
+    if p == 1:
+      with pytest.raises(IndexError if exc == 'IndexError' else AssertionError):
+        run()
+    else:
+      run()
+
+
 BERT_MASK = (0.15, 30522, 101, 102, 103)  # ratio, |vocab|, [CLS], [SEP], [MASK]
 
 

@@ -9,7 +9,9 @@ directly and restate the 5-line _to_partition_pairs closure
 uses vocab_words in vocab-file order (the reference's tuple(vocab.keys()) is
 hash-ordered).  Binning restates binning.py:72-75.
 
-Writes tests/golden/pack_bert.json.gz, pack_codebert.json.gz (data only).
+Writes tests/golden/pack_bert.json.gz, pack_codebert.json.gz and
+pack_codebert_regimes.json.gz (data only).  Arguments name the fixtures to
+write (bert, codebert, regimes); none writes all three.
 """
 import gzip
 import json
@@ -74,7 +76,7 @@ def ref_bert_partition(docs_ids, V, seed, max_seq, ssp, dup, masking, ratio):
   return pairs
 
 
-def main():
+def main_bert():
   Vb = vocab(os.path.join(ROOT, 'lddl_amd', 'data', 'bert_vocab.txt'))
   idx = {t: i for i, t in enumerate(Vb)}
   wiki = synth.make_wiki(400_000, seed=21)
@@ -116,7 +118,38 @@ def main():
                'seed_rule': 'random.seed(seed) before each partition', 'cases': cases}, f)
   print('bert cases', len(cases), sum(len(c['rows']) for c in cases), 'rows')
 
-  # ---------------- CodeBERT ----------------
+
+
+def ref_codebert_partition(part, nd, Vc, cidx, seed, max_seq, ssp, dup):
+  """pretrain_codebert.py:460-477 _to_partition_pairs after random.seed(seed)
+  over (segments, docstring segment count) documents of token ids ->
+  (rows in the shuffled order, the exception's name or None)"""
+  cps = []
+  for k, (d, n) in enumerate(zip(part, nd)):
+    ds = tuple(refc.Sentence(tuple(Vc[t] for t in s)) for s in d[:n] if len(s) > 0)
+    cs = tuple(refc.Sentence(tuple(Vc[t] for t in s)) for s in d[n:] if len(s) > 0)
+    cp = refc.CodePair('py_%d' % k, refc.Document(cs), refc.Document(ds))
+    if len(cp) > 0:
+      cps.append(cp)
+  cps = tuple(cps)
+  random.seed(seed)
+  rows = []
+  try:
+    pairs = []
+    for _ in range(dup):
+      for di in range(len(cps)):
+        pairs.extend(refc.create_pairs_from_document(cps, di, max_seq_length=max_seq, short_seq_prob=ssp))
+    random.shuffle(pairs)
+  except (IndexError, AssertionError) as e:
+    return [], type(e).__name__
+  for p in pairs:
+    rows.append({'id': p['id'], 'doc': [cidx[t] for t in p['doc'].split(' ')] if p['doc'] else [],
+                 'code': [cidx[t] for t in p['code'].split(' ')] if p['code'] else [],
+                 'num_tokens': int(p['num_tokens'])})
+  return rows, None
+
+
+def main_codebert():
   Vc = vocab(os.path.join(ROOT, 'lddl_amd', 'data', 'codebert_52000_vocab.txt'))
   cidx = {t: i for i, t in enumerate(Vc)}
   code = synth.make_code(120, seed=22)
@@ -129,29 +162,7 @@ def main():
   for cfg in [dict(max_seq=512, ssp=0.1, dup=1), dict(max_seq=128, ssp=0.1, dup=2), dict(max_seq=128, ssp=0.9, dup=1)]:
     for pi, (part, nd) in enumerate(cparts):
       seed = 777 + pi
-      cps = []
-      for k, (d, n) in enumerate(zip(part, nd)):
-        ds = tuple(refc.Sentence(tuple(Vc[t] for t in s)) for s in d[:n] if len(s) > 0)
-        cs = tuple(refc.Sentence(tuple(Vc[t] for t in s)) for s in d[n:] if len(s) > 0)
-        cp = refc.CodePair('py_%d' % k, refc.Document(cs), refc.Document(ds))
-        if len(cp) > 0:
-          cps.append(cp)
-      cps = tuple(cps)
-      random.seed(seed)
-      rows, err = [], None
-      try:
-        pairs = []
-        for _ in range(cfg['dup']):
-          for di in range(len(cps)):
-            pairs.extend(refc.create_pairs_from_document(cps, di, max_seq_length=cfg['max_seq'],
-                                                         short_seq_prob=cfg['ssp']))
-        random.shuffle(pairs)
-        for p in pairs:
-          rows.append({'id': p['id'], 'doc': [cidx[t] for t in p['doc'].split(' ')] if p['doc'] else [],
-                       'code': [cidx[t] for t in p['code'].split(' ')] if p['code'] else [],
-                       'num_tokens': int(p['num_tokens'])})
-      except IndexError:
-        err = 'IndexError'
+      rows, err = ref_codebert_partition(part, nd, Vc, cidx, seed, cfg['max_seq'], cfg['ssp'], cfg['dup'])
       ccases.append({'cfg': cfg, 'seed': seed, 'docs': part, 'ndoc': nd, 'rows': rows, 'error': err})
   with gzip.open(os.path.join(ROOT, 'tests', 'golden', 'pack_codebert.json.gz'), 'wt') as f:
     json.dump({'generator': 'tools/gen_golden_pack.py',
@@ -160,5 +171,44 @@ def main():
         [c['error'] for c in ccases])
 
 
+def main_regimes():
+  """the regime corpora of tests/codebert_regimes.py: the main corpus at every
+  configuration (rows per partition in the shuffled order) and the error
+  corpora (the exception per partition).  The documents are not stored: the
+  test rebuilds them, and 'corpus' pins their lengths."""
+  sys.path.insert(0, os.path.join(ROOT, 'tests'))
+  import codebert_regimes as cr
+  Vc = vocab(os.path.join(ROOT, 'lddl_amd', 'data', 'codebert_52000_vocab.txt'))
+  cidx = {t: i for i, t in enumerate(Vc)}
+  assert len(cidx) == len(Vc)  # ids <-> tokens one to one
+  shape = lambda docs: [[len(s) for s in d] for d in docs]  # noqa: E731
+  cases, errors = [], []
+  for seq, ssp in cr.CONFIGS:
+    docs, ndoc, pdo = cr.corpus(seq)
+    seed = cr.PACK_SEEDS.get((seq, ssp), cr.PACK_SEED)
+    parts = []
+    for p in range(len(pdo) - 1):
+      rows, err = ref_codebert_partition(docs[pdo[p]:pdo[p + 1]], ndoc[pdo[p]:pdo[p + 1]], Vc, cidx, seed + p, seq, ssp,
+                                         cr.DUP)
+      assert err is None, (seq, ssp, p, err)
+      parts.append([[r['doc'], r['code'], r['num_tokens']] for r in rows])
+    cases.append({'seq': seq, 'ssp': ssp, 'dup': cr.DUP, 'seed': seed, 'corpus': shape(docs), 'ndoc': ndoc,
+                  'part_doc_off': pdo, 'parts': parts})
+  for seq, ssp, exc in cr.ERROR_CONFIGS:
+    docs, ndoc, pdo = cr.error_corpus(seq, exc)
+    errs = [ref_codebert_partition(docs[pdo[p]:pdo[p + 1]], ndoc[pdo[p]:pdo[p + 1]], Vc, cidx, cr.PACK_SEED + p, seq, ssp,
+                                   cr.DUP)[1] for p in range(len(pdo) - 1)]
+    errors.append({'seq': seq, 'ssp': ssp, 'dup': cr.DUP, 'seed': cr.PACK_SEED, 'corpus': shape(docs), 'ndoc': ndoc,
+                   'part_doc_off': pdo, 'error': exc, 'errors': errs})
+  with gzip.open(os.path.join(ROOT, 'tests', 'golden', 'pack_codebert_regimes.json.gz'), 'wt') as f:
+    json.dump({'generator': 'tools/gen_golden_pack.py', 'reference': 'lddl/dask/bert/pretrain_codebert.py:343-477',
+               'seed_rule': 'random.seed(seed + partition) before each partition', 'cases': cases, 'errors': errors}, f,
+              separators=(',', ':'))
+  print('codebert regime cases', len(cases), sum(len(p) for c in cases for p in c['parts']), 'rows',
+        [e['errors'] for e in errors])
+
+
 if __name__ == '__main__':
-  main()
+  which = sys.argv[1:] or ['bert', 'codebert', 'regimes']
+  for name in which:
+    {'bert': main_bert, 'codebert': main_codebert, 'regimes': main_regimes}[name]()

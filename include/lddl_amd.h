@@ -366,7 +366,7 @@ int lddl_collate_rows_seq_len(lddl_ctx *ctx, const uint16_t *d_len0, const uint1
  * seq_len), LDDL_ECAPACITY (a row longer than seq_len, seq_len > 2048),
  * LDDL_EINVAL (a row whose flags lack bit 1: a CodeBERT row without
  * docstring has no [SEP] after segment 0, and bert.py has no CodeBERT
- * loader). */
+ * loader; lddl_collate_code_rows takes such rows). */
 int lddl_collate_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
                       const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags, const int64_t *d_rows,
                       int64_t row0, int64_t n_rows, int64_t n_total, const int64_t *d_mlm_off,
@@ -425,6 +425,84 @@ int lddl_collate_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64
                                int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
                                int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
                                int64_t *d_labels, int64_t *d_next_sentence_labels, void *stream);
+
+/* ---- collate CodeBERT rows straight from a pack result ----------------------
+ * The four calls above for the rows of lddl_pack_codebert (or of
+ * lddl_code_rows_from_strings): the row pretrain_codebert.py:425-433 saves as
+ * doc / code / num_tokens.  The reference has no loader for it
+ * (lddl/torch/bert.py only knows A / B / is_random_next); the layout is what a
+ * BERT tokenizer gives for a pair and for a single sequence.  Row g has
+ * a = len0[g] doc tokens, b = len1[g] code tokens, s = (flags[g] >> 1) & 1
+ * (1 when the document has docstring segments, pretrain_codebert.py:356) and
+ * n = a + b + 2 + s columns:
+ *   s = 1:  0 [CLS] | [1, a] doc | a + 1 [SEP] | [a + 2, n - 2] code | n - 1 [SEP]
+ *   s = 0:  0 [CLS] | [1, n - 2] code | n - 1 [SEP]              (a must be 0)
+ * a = 0 with s = 1 is a regular row, [CLS] [SEP] code [SEP].  token_type_ids
+ * is 1 on [a + 2, n) when s = 1 and 0 on every column when s = 0;
+ * attention_mask 1 on [0, n); the special_tokens_mask 1 on [CLS], each [SEP]
+ * and the pad columns.  There is no next_sentence_labels (the rows carry no
+ * NSP label) and no static mode (the CodeBERT preprocessor ignores masking):
+ * mode 0 is the special_tokens_mask, mode 2 is mode 0 followed by
+ * lddl_mask_tokens' draw keyed by (seed, counter, row of the batch, column),
+ * with the vocabulary size of the ctx, bit for bit.  For s = 1 rows the
+ * outputs are those of lddl_collate_rows on the same rows.  Rows are picked as
+ * there: batch row r is row g = d_rows[r] (d_rows NULL: g = row0 + r),
+ * 0 <= g < n_total, any order, repeats allowed.  All four synchronise the
+ * stream, and an empty batch (n_rows <= 0) is LDDL_EINVAL in each.
+ *
+ * lddl_collate_code_rows_seq_len: the batch's padded length = max over its
+ * rows of a + b + 2 + s, rounded up to seq_align; d_flags is read as well.
+ * A row index outside [0, n_total) is LDDL_EINDEX (checked before any load
+ * through it). */
+int lddl_collate_code_rows_seq_len(lddl_ctx *ctx, const uint16_t *d_len0, const uint16_t *d_len1,
+                                   const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                   int64_t n_total, int32_t seq_align, int64_t *out_seq_len, void *stream);
+
+/* Fill the [n_rows, seq_len] int64 outputs of a padded batch of CodeBERT rows
+ * (pretrain_codebert.py:425-433; no loader in the reference), pad columns
+ * with id 0, attention 0 and special 1.  d_labels by mode 0 / 2 as above.
+ * Errors, first one wins, none faults, a refused row is left unwritten:
+ * LDDL_EINDEX (a row index outside [0, n_total), checked before any load
+ * through it), LDDL_EINVAL (n_rows <= 0; a mode other than 0 or 2: CodeBERT
+ * has no static masks; a row with s = 0 and a > 0, which the packer never
+ * makes), LDDL_ECAPACITY (a row longer than seq_len, seq_len > 2048). */
+int lddl_collate_code_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                           const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                           const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total, int64_t seq_len,
+                           int32_t mode, int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
+                           int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_attention_mask,
+                           int64_t *d_labels, void *stream);
+
+/* lddl_collate_rows_cu_seqlens for CodeBERT rows (pretrain_codebert.py:425-433;
+ * no loader in the reference): d_cu_seqlens is the exclusive scan of
+ * n_r = a + b + 2 + s as int32 [n_rows + 1], *out_total = T, *out_max_seqlen =
+ * max n_r; d_flags is read as well.  LDDL_EINDEX (a row index outside
+ * [0, n_total)), LDDL_EINVAL (n_rows <= 0), LDDL_ECAPACITY (T >= 2^31, summed
+ * in 64 bits; d_cu_seqlens is then left unwritten). */
+int lddl_collate_code_rows_cu_seqlens(lddl_ctx *ctx, const uint16_t *d_len0, const uint16_t *d_len1,
+                                      const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                      int64_t n_total, int32_t *d_cu_seqlens, int64_t *out_total,
+                                      int64_t *out_max_seqlen, void *stream);
+
+/* The padding-free batch of CodeBERT rows (pretrain_codebert.py:425-433; no
+ * loader in the reference): lddl_collate_code_rows at the same seed and
+ * counter with every column j >= n_r dropped, bit for bit in modes 0 and 2.
+ * For t = cu_seqlens[r] + j: input_ids[t], token_type_ids[t], d_labels[t] are
+ * column j of row r, position_ids[t] = j; the four outputs are [total].
+ * d_cu_seqlens is checked, not trusted.  Errors, first one wins, none faults,
+ * the row is left unwritten and no row stores outside its own tokens:
+ * LDDL_EINDEX (a row index outside [0, n_total)), LDDL_EINVAL (n_rows <= 0; a
+ * mode other than 0 or 2: CodeBERT has no static masks; a row with s = 0 and
+ * a > 0; a row with cu_seqlens[r] < 0, cu_seqlens[r + 1] - cu_seqlens[r] !=
+ * n_r or cu_seqlens[r] + n_r > total), LDDL_ECAPACITY (a row longer than 2048
+ * tokens, total >= 2^31). */
+int lddl_collate_code_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                    const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                    const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                    int64_t n_total, const int32_t *d_cu_seqlens, int64_t total, int32_t mode,
+                                    int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
+                                    int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
+                                    int64_t *d_labels, void *stream);
 
 /* ---- a row table from the shards on disk ----------------------------------
  * The bridge from parquet shards to lddl_collate_rows[_unpadded]: the string
@@ -489,6 +567,47 @@ int lddl_rows_from_strings(lddl_ctx *ctx, const uint8_t *d_a, const int64_t *d_a
                            const int64_t *d_mlm_off, uint16_t *d_out_ids, int64_t ids_cap, uint8_t *d_out_flags,
                            uint16_t *d_out_mlm_pos, uint16_t *d_out_mlm_label, uint16_t *d_out_mlm_token,
                            int64_t mlm_cap, void *stream);
+
+/* ---- a row table from CodeBERT shards ---------------------------------------
+ * The two calls above for the shards of the CodeBERT preprocessor: the row
+ * pretrain_codebert.py:425-433 saves as id / doc / code / num_tokens (the
+ * reference has no loader for it; the id column is not read).  d_doc /
+ * d_code: Arrow bytes + int64 offsets [n_rows + 1]; d_num_tokens: uint16
+ * [n_rows] on the device.  Per row a = tokens of doc.split(), b = tokens of
+ * code.split(), s = num_tokens - a - b - 2 (1 when a [SEP] follows the doc
+ * segment), flags = s << 1.
+ *
+ * lddl_code_rows_from_strings_len: d_out_len0[r] = a, d_out_len1[r] = b,
+ * d_out_src0[r] = the sum of a + b over the rows before r, d_out_src1[r] =
+ * d_out_src0[r] + a, d_out_tok_off (optional, [n_rows + 1]) the exclusive scan
+ * of a + b + 2 + s; out_totals = {ids = sum of a + b, row tokens}.
+ * Synchronises the stream once.  Errors, first one wins, none faults:
+ * LDDL_ECAPACITY (a segment of more than 65535 tokens), LDDL_EFORMAT (a
+ * num_tokens that is not a + b + 2 or a + b + 3, or is a + b + 2 with a > 0:
+ * doc tokens with no [SEP] to end them), LDDL_EINVAL (n_rows <= 0, a NULL
+ * pointer, a vocabulary of more than 65536 entries). */
+int lddl_code_rows_from_strings_len(lddl_ctx *ctx, const uint8_t *d_doc, const int64_t *d_doc_off,
+                                    const uint8_t *d_code, const int64_t *d_code_off, const uint16_t *d_num_tokens,
+                                    int64_t n_rows, uint16_t *d_out_len0, uint16_t *d_out_len1, int64_t *d_out_src0,
+                                    int64_t *d_out_src1, int64_t *d_out_tok_off, int64_t out_totals[2],
+                                    void *stream);
+
+/* Fill the table from a CodeBERT shard (pretrain_codebert.py:425-433; no
+ * loader in the reference): d_out_ids[src0[r] .. + a) = the ids of doc's
+ * tokens, d_out_ids[src1[r] .. + b) = of code's ([UNK] for a miss),
+ * d_out_flags[r] = s << 1.  d_len0 .. d_src1 are the length call's outputs and
+ * are checked, not trusted: every row is counted again, and its num_tokens
+ * checked again, before anything is stored.  ids_cap and the padding behind
+ * d_out_ids as in lddl_rows_from_strings.  Synchronises the stream.  Errors as
+ * the length call, and: LDDL_ECAPACITY (the table ends beyond ids_cap: nothing
+ * is written), LDDL_EINVAL (a row whose len0 / len1 / src0 / src1 are not what
+ * its strings give, or whose span leaves the capacity).  A refused row is
+ * left unwritten and a row stores only inside [src0[r], src0[r] + a + b). */
+int lddl_code_rows_from_strings(lddl_ctx *ctx, const uint8_t *d_doc, const int64_t *d_doc_off, const uint8_t *d_code,
+                                const int64_t *d_code_off, const uint16_t *d_num_tokens, int64_t n_rows,
+                                const uint16_t *d_len0, const uint16_t *d_len1, const int64_t *d_src0,
+                                const int64_t *d_src1, uint16_t *d_out_ids, int64_t ids_cap, uint8_t *d_out_flags,
+                                void *stream);
 
 /* ---- BART: sentence aggregation --------------------------------------------
  * The reference's third preprocessor (lddl/dask/bart/pretrain.py) cuts every

@@ -159,8 +159,12 @@ static int collate_rows_error(uint32_t e, int64_t seq_len) {
                      (long long)seq_len);
     case CERR_CU_SEQLENS:
       return set_err(LDDL_EINVAL, "batch row %llu: cu_seqlens do not hold the row's tokens within [0, total)", row);
+    case CERR_CODE_ROW:
+      return set_err(LDDL_EINVAL, "batch row %llu has doc tokens and no [SEP] after them (flags bit 1 clear, len0 > 0)", row);
     default:
-      return set_err(LDDL_EINVAL, "batch row %llu has no [SEP] after its first segment (a CodeBERT row)", row);
+      return set_err(LDDL_EINVAL,
+                     "batch row %llu has no [SEP] after its first segment (a CodeBERT row: lddl_collate_code_rows takes it)",
+                     row);
   }
 }
 
@@ -174,35 +178,39 @@ static int collate_unpadded_error(uint32_t e) {
   }
 }
 
-// the row selection that every lddl_collate_rows* call takes
-static void collate_rows_index(CollateRowsParams* P, const uint16_t* d_len0, const uint16_t* d_len1, const int64_t* d_rows,
-                               int64_t row0, int64_t n_rows, int64_t n_total) {
+// the row selection that every lddl_collate_rows* / lddl_collate_code_rows* call takes (d_flags: the CodeBERT
+// calls, whose row lengths depend on it, and the fill calls)
+static void collate_rows_index(CollateRowsParams* P, const uint16_t* d_len0, const uint16_t* d_len1,
+                               const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                               int64_t n_total) {
   P->len0 = d_len0;
   P->len1 = d_len1;
+  P->flags = d_flags;
   P->rows = d_rows;
   P->row0 = row0;
   P->n_rows = n_rows;
   P->n_total = n_total;
 }
 
-extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
-                                         const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
-                                         int32_t seq_align, int64_t* out_seq_len, void* stream) {
+// lddl_collate_rows_seq_len (code 0: d_flags NULL) and lddl_collate_code_rows_seq_len (code 1)
+static int collate_rows_seq_len_common(lddl_ctx* c, int code, const uint16_t* d_len0, const uint16_t* d_len1,
+                                       const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                       int64_t n_total, int32_t seq_align, int64_t* out_seq_len, void* stream) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   if (n_rows < 0 || n_total < 0 || seq_align < 1 || !out_seq_len)
     return set_err(LDDL_EINVAL, "bad n_rows / n_total / seq_align / out");
   if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
-  if (!d_len0 || !d_len1) return set_err(LDDL_EINVAL, "null pointer");
+  if (!d_len0 || !d_len1 || (code && !d_flags)) return set_err(LDDL_EINVAL, "null pointer");
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   CollateRowsParams P{};
-  collate_rows_index(&P, d_len0, d_len1, d_rows, row0, n_rows, n_total);
+  collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   int rc;
   uint32_t e;
   if ((rc = ws_get(c, CW_SHARED_META, 1, &P.max_len)) || (rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
   HIP_TRY(hipMemsetAsync(P.max_len, 0, 4, st));
   HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
-  HIP_TRY(launch_collate_rows_len(P, c->n_cu, st));
+  HIP_TRY(launch_collate_rows_len(P, code != 0, c->n_cu, st));
   HIP_TRY(fetch_word(c, HW_MAX_LEN, P.max_len, 4, st));
   if ((rc = read_err(c, P.err, st, &e))) return rc;
   if (e) return collate_rows_error(e, 0);
@@ -210,11 +218,20 @@ extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, co
   return 0;
 }
 
+extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                         const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                         int32_t seq_align, int64_t* out_seq_len, void* stream) {
+  return collate_rows_seq_len_common(c, 0, d_len0, d_len1, nullptr, d_rows, row0, n_rows, n_total, seq_align, out_seq_len,
+                                     stream);
+}
+
 // lddl_collate_rows (unpadded 0: seq_len, d_attention_mask) and lddl_collate_rows_unpadded (1: d_cu_seqlens,
 // total, d_position_ids) validate their arguments and fill CollateRowsParams here, once.  The range check
 // between the mode and the probability checks, the launch and the wording of the device's errors are each
-// call's own; the arguments of the other call arrive as 0 / NULL and are passed on as that.
-static int collate_rows_common(lddl_ctx* c, int unpadded, const uint16_t* d_ids, const int64_t* d_src0,
+// call's own; the arguments of the other call arrive as 0 / NULL and are passed on as that.  code 1: the
+// lddl_collate_code_rows[_unpadded] twins, CodeBERT rows: modes 0 and 2, no static arrays, no
+// d_next_sentence_labels, a row of two tokens at least, and an empty batch is refused.
+static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16_t* d_ids, const int64_t* d_src0,
                                const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
                                const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
                                int64_t n_total, const int64_t* d_mlm_off, const uint16_t* d_mlm_pos,
@@ -225,14 +242,19 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, const uint16_t* d_ids,
                                int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   if (n_rows < 0 || n_total < 0) return set_err(LDDL_EINVAL, "negative n_rows / n_total");
+  if (code && n_rows == 0) return set_err(LDDL_EINVAL, "empty batch");
+  if (code && mode != COLLATE_SPECIAL_MASK && mode != COLLATE_DYNAMIC)
+    return set_err(LDDL_EINVAL, "mode %d: CodeBERT rows have no static masks, the modes are 0 and 2", mode);
   if (mode < COLLATE_SPECIAL_MASK || mode > COLLATE_DYNAMIC) return set_err(LDDL_EINVAL, "mode %d not in 0..2", mode);
-  if (!unpadded && (seq_len < 3 || seq_len > COLLATE_MAX_LEN))
-    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [3, %d]", (long long)seq_len, COLLATE_MAX_LEN);
+  const int min_len = code ? 2 : 3;
+  if (!unpadded && (seq_len < min_len || seq_len > COLLATE_MAX_LEN))
+    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [%d, %d]", (long long)seq_len, min_len, COLLATE_MAX_LEN);
   if (unpadded && total < 0) return set_err(LDDL_EINVAL, "negative total");
   if (unpadded && total > INT32_MAX) return set_err(LDDL_ECAPACITY, "total %lld: cu_seqlens are int32", (long long)total);
   if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
   if (n_rows > 0 && (!d_ids || !d_src0 || !d_src1 || !d_len0 || !d_len1 || !d_flags || !d_input_ids || !d_token_type_ids ||
-                     (unpadded ? !d_cu_seqlens || !d_position_ids : !d_attention_mask) || !d_labels || !d_next_sentence_labels))
+                     (unpadded ? !d_cu_seqlens || !d_position_ids : !d_attention_mask) || !d_labels ||
+                     (!code && !d_next_sentence_labels)))
     return set_err(LDDL_EINVAL, "null pointer");
   if (mode == COLLATE_STATIC && n_rows > 0 && (!d_mlm_off || !d_mlm_pos || !d_mlm_label || !d_mlm_token))
     return set_err(LDDL_EINVAL, "static masking needs lddl_masked_lm_spans' arrays");
@@ -241,11 +263,10 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, const uint16_t* d_ids,
   hipStream_t st = (hipStream_t)stream;
   CollateUnpaddedParams U{};
   CollateRowsParams& P = U.R;
-  collate_rows_index(&P, d_len0, d_len1, d_rows, row0, n_rows, n_total);
+  collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   P.ids = d_ids;
   P.src0 = d_src0;
   P.src1 = d_src1;
-  P.flags = d_flags;
   P.mlm_off = d_mlm_off;
   P.mlm_pos = d_mlm_pos;
   P.mlm_label = d_mlm_label;
@@ -271,7 +292,8 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, const uint16_t* d_ids,
   uint32_t e;
   if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
   HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
-  HIP_TRY(unpadded ? launch_collate_unpadded(U, mode, c->n_cu, st) : launch_collate_rows(P, mode, c->n_cu, st));
+  HIP_TRY(unpadded ? launch_collate_unpadded(U, code != 0, mode, c->n_cu, st)
+                   : launch_collate_rows(P, code != 0, mode, c->n_cu, st));
   if ((rc = read_err(c, P.err, st, &e))) return rc;
   if (e) return unpadded ? collate_unpadded_error(e) : collate_rows_error(e, seq_len);
   return 0;
@@ -285,28 +307,30 @@ extern "C" int lddl_collate_rows(lddl_ctx* c, const uint16_t* d_ids, const int64
                                  double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
                                  int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_labels,
                                  int64_t* d_next_sentence_labels, void* stream) {
-  return collate_rows_common(c, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
+  return collate_rows_common(c, 0, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
                              d_mlm_pos, d_mlm_label, d_mlm_token, seq_len, nullptr, 0, mode, ignore_index, mlm_probability,
                              seed, counter, d_input_ids, d_token_type_ids, d_attention_mask, nullptr, d_labels,
                              d_next_sentence_labels, stream);
 }
 
 // ------------------------------------- padding-free collate from a pack result --
-extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
-                                            const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
-                                            int32_t* d_cu_seqlens, int64_t* out_total, int64_t* out_max_seqlen,
-                                            void* stream) {
+// lddl_collate_rows_cu_seqlens (code 0: d_flags NULL) and lddl_collate_code_rows_cu_seqlens (code 1)
+static int collate_cu_seqlens_common(lddl_ctx* c, int code, const uint16_t* d_len0, const uint16_t* d_len1,
+                                     const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                     int64_t n_total, int32_t* d_cu_seqlens, int64_t* out_total, int64_t* out_max_seqlen,
+                                     void* stream) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   if (n_rows < 0 || n_total < 0 || !out_total || !out_max_seqlen)
     return set_err(LDDL_EINVAL, "bad n_rows / n_total / out");
   if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch (max() of an empty sequence)");
-  if (!d_len0 || !d_len1 || !d_cu_seqlens) return set_err(LDDL_EINVAL, "null pointer");
-  // every row has its three special tokens at least
-  if (n_rows > INT32_MAX / 3) return set_err(LDDL_ECAPACITY, "%lld rows hold 2^31 tokens or more", (long long)n_rows);
+  if (!d_len0 || !d_len1 || !d_cu_seqlens || (code && !d_flags)) return set_err(LDDL_EINVAL, "null pointer");
+  // every row has its special tokens at least: three, or the two of a CodeBERT row without docstring
+  if (n_rows > INT32_MAX / (code ? 2 : 3))
+    return set_err(LDDL_ECAPACITY, "%lld rows hold 2^31 tokens or more", (long long)n_rows);
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
   CollateUnpaddedParams P{};
-  collate_rows_index(&P.R, d_len0, d_len1, d_rows, row0, n_rows, n_total);
+  collate_rows_index(&P.R, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   P.cu_seqlens = d_cu_seqlens;
   P.n_chunks = collate_chunks(n_rows);
   int rc;
@@ -319,7 +343,7 @@ extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0,
   P.R.max_len = (int32_t*)(meta + 1);
   HIP_TRY(hipMemsetAsync(meta, 0, 16, st));
   HIP_TRY(hipMemsetAsync(P.R.err, 0, 4, st));
-  HIP_TRY(launch_collate_cu_seqlens(P, st));
+  HIP_TRY(launch_collate_cu_seqlens(P, code != 0, st));
   HIP_TRY(fetch_word(c, HW_CU_TOTAL, meta, 16, st));
   if ((rc = read_err(c, P.R.err, st, &e))) return rc;
   if (e) return collate_unpadded_error(e);
@@ -331,6 +355,14 @@ extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0,
   return 0;
 }
 
+extern "C" int lddl_collate_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                            const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                            int32_t* d_cu_seqlens, int64_t* out_total, int64_t* out_max_seqlen,
+                                            void* stream) {
+  return collate_cu_seqlens_common(c, 0, d_len0, d_len1, nullptr, d_rows, row0, n_rows, n_total, d_cu_seqlens, out_total,
+                                   out_max_seqlen, stream);
+}
+
 extern "C" int lddl_collate_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
                                           const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
                                           const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
@@ -340,10 +372,50 @@ extern "C" int lddl_collate_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, co
                                           int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
                                           int64_t* d_input_ids, int64_t* d_token_type_ids, int64_t* d_position_ids,
                                           int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream) {
-  return collate_rows_common(c, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
+  return collate_rows_common(c, 1, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
                              d_mlm_pos, d_mlm_label, d_mlm_token, 0, d_cu_seqlens, total, mode, ignore_index,
                              mlm_probability, seed, counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids,
                              d_labels, d_next_sentence_labels, stream);
+}
+
+// ------------------------------------------------- the same for CodeBERT rows --
+extern "C" int lddl_collate_code_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                              const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                              int64_t n_total, int32_t seq_align, int64_t* out_seq_len, void* stream) {
+  return collate_rows_seq_len_common(c, 1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, seq_align, out_seq_len,
+                                     stream);
+}
+
+extern "C" int lddl_collate_code_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                      const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                      const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                      int64_t seq_len, int32_t mode, int64_t ignore_index, double mlm_probability,
+                                      uint64_t seed, uint64_t counter, int64_t* d_input_ids, int64_t* d_token_type_ids,
+                                      int64_t* d_attention_mask, int64_t* d_labels, void* stream) {
+  return collate_rows_common(c, 0, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, nullptr,
+                             nullptr, nullptr, nullptr, seq_len, nullptr, 0, mode, ignore_index, mlm_probability, seed,
+                             counter, d_input_ids, d_token_type_ids, d_attention_mask, nullptr, d_labels, nullptr, stream);
+}
+
+extern "C" int lddl_collate_code_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                 const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                 int64_t n_rows, int64_t n_total, int32_t* d_cu_seqlens,
+                                                 int64_t* out_total, int64_t* out_max_seqlen, void* stream) {
+  return collate_cu_seqlens_common(c, 1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_cu_seqlens, out_total,
+                                   out_max_seqlen, stream);
+}
+
+extern "C" int lddl_collate_code_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                               const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                               const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                               int64_t n_rows, int64_t n_total, const int32_t* d_cu_seqlens,
+                                               int64_t total, int32_t mode, int64_t ignore_index, double mlm_probability,
+                                               uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                               int64_t* d_token_type_ids, int64_t* d_position_ids, int64_t* d_labels,
+                                               void* stream) {
+  return collate_rows_common(c, 1, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, nullptr,
+                             nullptr, nullptr, nullptr, 0, d_cu_seqlens, total, mode, ignore_index, mlm_probability, seed,
+                             counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids, d_labels, nullptr, stream);
 }
 
 // ------------------------------------------- a row table from a shard's strings --
@@ -357,6 +429,9 @@ static int rows_from_strings_error(uint32_t e) {
     case CERR_NPY: return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions is not np.save bytes", row);
     case CERR_NLAB:
       return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions and masked_lm_labels differ in length", row);
+    case CERR_CODE_ROW:
+      return set_err(LDDL_EFORMAT,
+                     "row %llu: num_tokens is neither doc + code + 3 nor, with an empty doc, code + 2 (tokens by split())", row);
     default:
       return set_err(LDDL_EINVAL, "row %llu: len0 / len1 / src0 / src1 / mlm_off are not what its strings give", row);
   }
@@ -365,10 +440,12 @@ static int rows_from_strings_error(uint32_t e) {
 // lddl_rows_from_strings_len (fill 0: the outputs d_len0 .. d_mlm_off, d_tok_off, out_totals) and
 // lddl_rows_from_strings (fill 1: the same arrays as inputs, d_is_random_next and the table) validate their
 // arguments and fill RowsFromStringsParams here, once; the arguments of the other call arrive as 0 / NULL.
-static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, const int64_t* d_a_off,
+// code 1: the lddl_code_rows_from_strings[_len] twins over doc / code with d_num_tokens in place of
+// d_is_random_next and the static columns; out_totals is then {ids, row tokens}.
+static int rows_from_strings_common(lddl_ctx* c, int fill, int code, const uint8_t* d_a, const int64_t* d_a_off,
                                     const uint8_t* d_b, const int64_t* d_b_off, const uint8_t* d_pos,
                                     const int64_t* d_pos_off, const uint8_t* d_lab, const int64_t* d_lab_off,
-                                    const uint8_t* d_is_random_next, int64_t n_rows, uint16_t* d_len0, uint16_t* d_len1,
+                                    const uint8_t* d_is_random_next, const uint16_t* d_num_tokens, int64_t n_rows, uint16_t* d_len0, uint16_t* d_len1,
                                     int64_t* d_src0, int64_t* d_src1, int64_t* d_tok_off, int64_t* d_mlm_off,
                                     int64_t* out_totals, uint16_t* d_ids, int64_t ids_cap, uint8_t* d_flags,
                                     uint16_t* d_mlm_pos, uint16_t* d_mlm_label, uint16_t* d_mlm_token, int64_t mlm_cap,
@@ -376,7 +453,8 @@ static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, c
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   if (n_rows <= 0) return set_err(LDDL_EINVAL, "n_rows %lld: a table has one row at least", (long long)n_rows);
   if (!d_a || !d_a_off || !d_b || !d_b_off) return set_err(LDDL_EINVAL, "null column pointer");
-  if (!d_len0 || !d_len1 || !d_src0 || !d_src1 || (fill ? !d_is_random_next || !d_ids || !d_flags : !out_totals))
+  if (!d_len0 || !d_len1 || !d_src0 || !d_src1 || (code ? !d_num_tokens : fill && !d_is_random_next) ||
+      (fill ? !d_ids || !d_flags : !out_totals))
     return set_err(LDDL_EINVAL, "null pointer");
   const int n_static = (d_pos != nullptr) + (d_pos_off != nullptr) + (d_lab != nullptr) + (d_lab_off != nullptr);
   if (n_static != 0 && n_static != 4)
@@ -393,6 +471,7 @@ static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, c
   if (fill && (rc = collate_vocab(c, &P.V))) return rc;
   P.C = StringColumns{d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off};
   P.is_random_next = d_is_random_next;
+  P.num_tokens = d_num_tokens;
   P.n_rows = n_rows;
   P.len0 = d_len0;
   P.len1 = d_len1;
@@ -424,6 +503,10 @@ static int rows_from_strings_common(lddl_ctx* c, int fill, const uint8_t* d_a, c
   if ((rc = read_err(c, P.err, st, &e))) return rc;
   if (e) return rows_from_strings_error(e);
   out_totals[0] = c->h_tot[HW_NTOK];
+  if (code) {
+    out_totals[1] = c->h_tot[HW_PACK_ERR];
+    return 0;
+  }
   out_totals[1] = c->h_tot[HW_NMASK];
   out_totals[2] = c->h_tot[HW_PACK_ERR];
   return 0;
@@ -435,7 +518,8 @@ extern "C" int lddl_rows_from_strings_len(lddl_ctx* c, const uint8_t* d_a, const
                                           uint16_t* d_out_len0, uint16_t* d_out_len1, int64_t* d_out_src0,
                                           int64_t* d_out_src1, int64_t* d_out_tok_off, int64_t* d_out_mlm_off,
                                           int64_t out_totals[3], void* stream) {
-  return rows_from_strings_common(c, 0, d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off, nullptr, n_rows,
+  return rows_from_strings_common(c, 0, 0, d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off, nullptr, nullptr,
+                                  n_rows,
                                   d_out_len0, d_out_len1, d_out_src0, d_out_src1, d_out_tok_off, d_out_mlm_off, out_totals,
                                   nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
 }
@@ -448,9 +532,32 @@ extern "C" int lddl_rows_from_strings(lddl_ctx* c, const uint8_t* d_a, const int
                                       uint16_t* d_out_ids, int64_t ids_cap, uint8_t* d_out_flags, uint16_t* d_out_mlm_pos,
                                       uint16_t* d_out_mlm_label, uint16_t* d_out_mlm_token, int64_t mlm_cap, void* stream) {
   // read only by the fill pass
-  return rows_from_strings_common(c, 1, d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off, d_is_random_next,
-                                  n_rows, const_cast<uint16_t*>(d_len0), const_cast<uint16_t*>(d_len1),
+  return rows_from_strings_common(c, 1, 0, d_a, d_a_off, d_b, d_b_off, d_pos, d_pos_off, d_lab, d_lab_off, d_is_random_next,
+                                  nullptr, n_rows, const_cast<uint16_t*>(d_len0), const_cast<uint16_t*>(d_len1),
                                   const_cast<int64_t*>(d_src0), const_cast<int64_t*>(d_src1), nullptr,
                                   const_cast<int64_t*>(d_mlm_off), nullptr, d_out_ids, ids_cap, d_out_flags, d_out_mlm_pos,
                                   d_out_mlm_label, d_out_mlm_token, mlm_cap, stream);
+}
+
+// --------------------------------------- the same from a CodeBERT shard's strings --
+extern "C" int lddl_code_rows_from_strings_len(lddl_ctx* c, const uint8_t* d_doc, const int64_t* d_doc_off,
+                                               const uint8_t* d_code, const int64_t* d_code_off,
+                                               const uint16_t* d_num_tokens, int64_t n_rows, uint16_t* d_out_len0,
+                                               uint16_t* d_out_len1, int64_t* d_out_src0, int64_t* d_out_src1,
+                                               int64_t* d_out_tok_off, int64_t out_totals[2], void* stream) {
+  return rows_from_strings_common(c, 0, 1, d_doc, d_doc_off, d_code, d_code_off, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  d_num_tokens, n_rows, d_out_len0, d_out_len1, d_out_src0, d_out_src1, d_out_tok_off,
+                                  nullptr, out_totals, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int lddl_code_rows_from_strings(lddl_ctx* c, const uint8_t* d_doc, const int64_t* d_doc_off,
+                                           const uint8_t* d_code, const int64_t* d_code_off, const uint16_t* d_num_tokens,
+                                           int64_t n_rows, const uint16_t* d_len0, const uint16_t* d_len1,
+                                           const int64_t* d_src0, const int64_t* d_src1, uint16_t* d_out_ids,
+                                           int64_t ids_cap, uint8_t* d_out_flags, void* stream) {
+  // read only by the fill pass
+  return rows_from_strings_common(c, 1, 1, d_doc, d_doc_off, d_code, d_code_off, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                  d_num_tokens, n_rows, const_cast<uint16_t*>(d_len0), const_cast<uint16_t*>(d_len1),
+                                  const_cast<int64_t*>(d_src0), const_cast<int64_t*>(d_src1), nullptr, nullptr, nullptr,
+                                  d_out_ids, ids_cap, d_out_flags, nullptr, nullptr, nullptr, 0, stream);
 }

@@ -64,7 +64,10 @@ struct MaskParams {
 };
 
 // lddl_collate_rows_seq_len / lddl_collate_rows: batch row r is row
-// g = rows[r] (rows NULL: row0 + r) of a pack result's spans over the dense ids
+// g = rows[r] (rows NULL: row0 + r) of a pack result's spans over the dense ids.
+// The lddl_collate_code_rows* calls fill the same struct for CodeBERT rows:
+// mlm_off .. mlm_token and next_sentence_labels stay NULL, and the seq-len and
+// offsets passes read flags as well.
 struct CollateRowsParams {
   const uint16_t* ids;    // the dense ids (16 entries of padding behind the last)
   const int64_t* src0;    // [n_total] lddl_row_spans' outputs
@@ -95,7 +98,7 @@ struct CollateRowsParams {
 // lddl_collate_rows_cu_seqlens / lddl_collate_rows_unpadded (collate_unpadded.hip):
 // the same batch without its pad columns, row r at tokens [cu_seqlens[r],
 // cu_seqlens[r + 1]).  R.seq_len and R.attention_mask are unused; R.max_len is
-// the offsets pass's max over the rows of len0 + len1 + 3.
+// the offsets pass's max over the rows of len0 + len1 + 3 (CodeBERT: + 2 + s).
 struct CollateUnpaddedParams {
   CollateRowsParams R;     // input_ids, token_type_ids, labels: [total]
   int32_t* cu_seqlens;     // [n_rows + 1]: written by the offsets pass, checked by the fill pass
@@ -109,11 +112,14 @@ struct CollateUnpaddedParams {
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
 // lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
-// static masking.
+// static masking.  lddl_code_rows_from_strings[_len] fill it for a CodeBERT
+// shard: C.a / C.b are doc / code, num_tokens is set, and is_random_next, the
+// static columns and every mlm_* field are NULL.
 struct RowsFromStringsParams {
   CollateVocab V;         // fill pass only
   StringColumns C;
   const uint8_t* is_random_next;  // [n_rows] (bool bytes; fill pass)
+  const uint16_t* num_tokens;     // [n_rows] CodeBERT: a + b + 2 + s
   int64_t n_rows;
   uint16_t* len0;         // [n_rows] written by the length pass, checked by the fill pass
   uint16_t* len1;
@@ -129,7 +135,8 @@ struct RowsFromStringsParams {
   uint16_t* mlm_token;
   int64_t mlm_cap;
   unsigned long long* chunk_sum;  // length pass: [n_chunks] ids (low half) | masked entries (high half) of each chunk of rows
-  int64_t* totals;        // length pass: [3] ids, row tokens and masked entries of the table
+                                  // (CodeBERT: rows with s = 1 in the high half)
+  int64_t* totals;        // length pass: [3] ids, row tokens and masked entries (CodeBERT: rows with s = 1) of the table
   int64_t n_chunks;       // collate_chunks(n_rows)
   uint32_t* err;          // [1] as CollateParams::err
 };
@@ -145,7 +152,8 @@ enum : uint32_t {
   CERR_CU_SEQLENS = 7,  // collate_unpadded.hip: a row's cu_seqlens are not its [c, c + n) within the outputs
   CERR_ROW_COUNTS = 8,  // rows_from_strings.hip: a row's len / src / mlm_off are not what its strings give
   CERR_TABLE_CAP = 9,   // rows_from_strings.hip: the table ends beyond ids_cap / mlm_cap
-  CERR_NMASK = 10       // rows_from_strings.hip: more masked positions than the longest row has tokens
+  CERR_NMASK = 10,      // rows_from_strings.hip: more masked positions than the longest row has tokens
+  CERR_CODE_ROW = 11    // a CodeBERT row whose s is not 0 or 1 (num_tokens - a - b - 2, rows_from_strings.hip), or is 0 with a > 0
 };
 
 constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
@@ -155,12 +163,14 @@ constexpr int kChunk = 2048;
 inline int64_t collate_chunks(int64_t n_rows) { return (n_rows + kChunk - 1) / kChunk; }
 
 uint32_t collate_hash_host(const uint8_t* p, int n);
-hipError_t launch_collate_rows_len(const CollateRowsParams& P, int n_cu, hipStream_t s);
-hipError_t launch_collate_rows(const CollateRowsParams& P, int32_t mode, int n_cu, hipStream_t s);
-hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, hipStream_t s);
-hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, int32_t mode, int n_cu, hipStream_t s);
+// code: the rows are CodeBERT rows (modes 0 and 2 only)
+hipError_t launch_collate_rows_len(const CollateRowsParams& P, bool code, int n_cu, hipStream_t s);
+hipError_t launch_collate_rows(const CollateRowsParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
+hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, hipStream_t s);
+hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
+// (a CodeBERT shard when P.num_tokens is set)
 hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_rows_from_strings(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);

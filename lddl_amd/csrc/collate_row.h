@@ -1,5 +1,5 @@
-// What the collate kernels share about a `[CLS] A [SEP] B [SEP]` row, written
-// once: the row layout (collate.hip, collate_rows.hip, collate_unpadded.hip,
+// What the collate kernels share about a `[CLS] A [SEP] B [SEP]` row (BERT, and
+// CodeBERT with or without the first [SEP]), written once: the row layout (collate.hip, collate_rows.hip, collate_unpadded.hip,
 // rows_from_strings.hip), opening a batch row of a row table and labelling its
 // columns by mode (collate_rows.hip, collate_unpadded.hip), the second level
 // of the chunked offsets scans (collate_unpadded.hip, rows_from_strings.hip)
@@ -17,20 +17,25 @@
 namespace lddl {
 
 // ------------------------------------------------------------ the row layout --
-// A row of a = len(A) and b = len(B) tokens holds n = a + b + 3 columns:
+// A row of a = len(A) and b = len(B) tokens holds n = a + b + 2 + s columns,
+// s = 1 when a [SEP] follows segment 0:
 //   0 [CLS] | [1, a] A | a + 1 [SEP] | [a + 2, n - 2] B | n - 1 [SEP] | [n, ..) padding
 // (lddl/torch/bert.py:69-153).  token_type_ids is 1 on B and its [SEP]; the
 // special_tokens_mask is 1 on the three special tokens and, in a padded batch,
-// on the padding.
+// on the padding.  Every BERT row has s = 1.  A CodeBERT row (doc = segment 0,
+// code = segment 1; pretrain_codebert.py:425-433) of a document without
+// docstring segments has s = 0 and a = 0:
+//   0 [CLS] | [1, n - 2] code | n - 1 [SEP]
+// one sequence, token_type_ids 0 throughout.
 struct RowLayout {
-  int32_t a, n;
+  int32_t a, n, s = 1;
   __device__ __forceinline__ bool is_cls(int32_t j) const { return j == 0; }
-  __device__ __forceinline__ bool is_sep(int32_t j) const { return j == a + 1 || j == n - 1; }
+  __device__ __forceinline__ bool is_sep(int32_t j) const { return (s && j == a + 1) || j == n - 1; }
   __device__ __forceinline__ bool special(int32_t j) const { return is_cls(j) || is_sep(j); }
   __device__ __forceinline__ bool seg0(int32_t j) const { return j >= 1 && j <= a; }
-  __device__ __forceinline__ bool seg1(int32_t j) const { return j >= a + 2 && j < n - 1; }
+  __device__ __forceinline__ bool seg1(int32_t j) const { return j >= a + 1 + s && j < n - 1; }
   __device__ __forceinline__ bool pad(int32_t j) const { return j >= n; }
-  __device__ __forceinline__ int32_t token_type(int32_t j) const { return (j >= a + 2 && j < n) ? 1 : 0; }
+  __device__ __forceinline__ int32_t token_type(int32_t j) const { return (s && j >= a + 2 && j < n) ? 1 : 0; }
   // the id the row shows at column j < n, before any masking: at(j) is asked
   // for the columns of the two segments only
   template <class At>
@@ -42,6 +47,10 @@ struct RowLayout {
 };
 
 // ------------------------------------------------- a batch row of a row table --
+// Every reader of a row table takes the kind of its rows as a template
+// constant: CODE false, BERT rows (s = 1; a row whose flags lack bit 1 is
+// refused); CODE true, CodeBERT rows (s = flags bit 1).
+
 // the pack row of batch row r (rows NULL: row0 + r), or -1 when out of range
 __device__ __forceinline__ int64_t pack_row(const CollateRowsParams& P, int64_t r) {
   const int64_t g = P.rows ? P.rows[r] : P.row0 + r;
@@ -49,8 +58,10 @@ __device__ __forceinline__ int64_t pack_row(const CollateRowsParams& P, int64_t 
 }
 
 // n of pack row g
+template <bool CODE>
 __device__ __forceinline__ uint32_t row_tokens(const CollateRowsParams& P, int64_t g) {
-  return (uint32_t)P.len0[g] + (uint32_t)P.len1[g] + 3u;
+  const uint32_t s = CODE ? ((uint32_t)P.flags[g] >> 1) & 1u : 1u;
+  return (uint32_t)P.len0[g] + (uint32_t)P.len1[g] + 2u + s;
 }
 
 struct OpenRow {
@@ -58,23 +69,26 @@ struct OpenRow {
   uint32_t flags;
   RowLayout L;
   const uint16_t* s0;  // ids + src0 - 1: column j of segment 0 is s0[j]
-  const uint16_t* s1;  // ids + src1 - (a + 2)
+  const uint16_t* s1;  // ids + src1 - (a + 1 + s)
 };
 
 // Opens batch row r whose n may be `bound` at most: 0 and the row, or the error
 // code to set.  Nothing is loaded through a row index before it is
 // range-checked; the order of the checks decides which code a row with several
 // faults reports.
+template <bool CODE>
 __device__ __forceinline__ uint32_t open_row(const CollateRowsParams& P, int64_t r, int32_t bound, OpenRow& o) {
   o.g = pack_row(P, r);
   if (o.g < 0) return CERR_ROW_INDEX;
   o.flags = P.flags[o.g];
-  if (!(o.flags & 2u)) return CERR_NO_SEP;  // a CodeBERT row without docstring: no [SEP] after segment 0
+  o.L.s = CODE ? (int32_t)((o.flags >> 1) & 1u) : 1;
+  if (!CODE && !(o.flags & 2u)) return CERR_NO_SEP;  // a CodeBERT row without docstring: no [SEP] after segment 0
   o.L.a = P.len0[o.g];
-  o.L.n = o.L.a + (int32_t)P.len1[o.g] + 3;
+  if (CODE && !o.L.s && o.L.a > 0) return CERR_CODE_ROW;  // doc tokens and no [SEP] to end them: not the packer's
+  o.L.n = o.L.a + (int32_t)P.len1[o.g] + 2 + o.L.s;
   if (o.L.n > bound) return CERR_LONG;
   o.s0 = P.ids + P.src0[o.g] - 1;
-  o.s1 = P.ids + P.src1[o.g] - (o.L.a + 2);
+  o.s1 = P.ids + P.src1[o.g] - (o.L.a + 1 + o.L.s);
   return 0;
 }
 
@@ -212,6 +226,13 @@ template <class F>
 inline void dispatch_mode(int32_t mode, F f) {
   if (mode == COLLATE_SPECIAL_MASK) f(std::integral_constant<int, COLLATE_SPECIAL_MASK>{});
   else if (mode == COLLATE_STATIC) f(std::integral_constant<int, COLLATE_STATIC>{});
+  else f(std::integral_constant<int, COLLATE_DYNAMIC>{});
+}
+
+// the same for CodeBERT rows, which have no static masks: modes 0 and 2
+template <class F>
+inline void dispatch_code_mode(int32_t mode, F f) {
+  if (mode == COLLATE_SPECIAL_MASK) f(std::integral_constant<int, COLLATE_SPECIAL_MASK>{});
   else f(std::integral_constant<int, COLLATE_DYNAMIC>{});
 }
 

@@ -12,6 +12,11 @@
 //   token_type_ids[r] = 1 on [a + 2, n);  attention_mask[r] = 1 on [0, n)
 //   next_sentence_labels[r] = flags[g] & 1
 //   labels[r] by mode, as row_column (collate_row.h) has it.
+// The same kernels with CODE set collate CodeBERT rows (lddl_collate_code_rows;
+// pretrain_codebert.py:425-433, for which the reference has no loader): s =
+// flags bit 1 says whether the first [SEP] is there, n = a + b + 2 + s, a row
+// without it is one sequence (token_type_ids 0); modes 0 and 2 only, and no
+// next_sentence_labels.
 // The row layout, the row opener with its checks and the labelling are
 // collate_row.h's, shared with collate_unpadded.hip; this file adds what
 // padding needs: id 0, the attention mask and `special` on the pad columns.
@@ -31,8 +36,10 @@
 //
 // No input faults: the row index is range-checked before anything is loaded
 // through it, a row longer than seq_len, a static position >= seq_len and a
-// CodeBERT row without docstring (flags bit 1 clear: no [SEP] after segment 0,
-// bert.py has no such loader) set the error word and leave the row unwritten.
+// CodeBERT row without docstring given to the BERT instantiation (flags bit 1
+// clear: no [SEP] after segment 0, bert.py has no such loader) set the error
+// word and leave the row unwritten; so does, with CODE, a row that has doc
+// tokens and no [SEP] after them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -43,7 +50,8 @@
 
 namespace lddl {
 
-// max over the batch of len0 + len1 + 3: lane = row
+// max over the batch of len0 + len1 + 2 + s: lane = row
+template <bool CODE>
 __global__ __launch_bounds__(256) void collate_rows_len_kernel(CollateRowsParams P) {
   const int64_t nt = (int64_t)gridDim.x * 256;
   uint32_t m = 0;
@@ -53,14 +61,15 @@ __global__ __launch_bounds__(256) void collate_rows_len_kernel(CollateRowsParams
       set_err(P.err, CERR_ROW_INDEX, r);
       continue;
     }
-    m = max(m, row_tokens(P, g));
+    m = max(m, row_tokens<CODE>(P, g));
   }
   m = wave_incl_max(m);
   if ((threadIdx.x & 63) == 63 && m) atomicMax(P.max_len, (int32_t)m);
 }
 
-template <int MODE>
+template <int MODE, bool CODE>
 __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) {
+  static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
   // mode 1 only: per wave, label | token << 16 of every masked column
   __shared__ uint32_t s_mlm[MODE == COLLATE_STATIC ? 4 : 1][MODE == COLLATE_STATIC ? COLLATE_MAX_LEN : 1];
   const int lane = threadIdx.x & 63;
@@ -73,7 +82,7 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
                                       (uintptr_t)P.attention_mask | (uintptr_t)P.labels) & 15) == 0;
   for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < P.n_rows; r += nw) {
     OpenRow R;
-    uint32_t code = open_row(P, r, L, R);
+    uint32_t code = open_row<CODE>(P, r, L, R);
     if (MODE == COLLATE_STATIC && !code && !stage_static_masks(P, R.g, L, mlm)) code = CERR_POS_RANGE;
     if (code) {
       if (lane == 0) set_err(P.err, code, r);
@@ -103,24 +112,31 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
         o_lab[j] = c.lab;
       }
     }
-    if (lane == 0) P.next_sentence_labels[r] = R.flags & 1u;
+    if (!CODE && lane == 0) P.next_sentence_labels[r] = R.flags & 1u;
   }
 }
 
-hipError_t launch_collate_rows_len(const CollateRowsParams& P, int n_cu, hipStream_t s) {
+hipError_t launch_collate_rows_len(const CollateRowsParams& P, bool code, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
   int64_t g = (P.n_rows + 255) / 256;
   if (g > (int64_t)n_cu * 8) g = (int64_t)n_cu * 8;
-  hipLaunchKernelGGL(collate_rows_len_kernel, dim3((int)g), dim3(256), 0, s, P);
+  if (code) hipLaunchKernelGGL(collate_rows_len_kernel<true>, dim3((int)g), dim3(256), 0, s, P);
+  else hipLaunchKernelGGL(collate_rows_len_kernel<false>, dim3((int)g), dim3(256), 0, s, P);
   return hipGetLastError();
 }
 
-hipError_t launch_collate_rows(const CollateRowsParams& P, int32_t mode, int n_cu, hipStream_t s) {
+hipError_t launch_collate_rows(const CollateRowsParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.n_rows, n_cu)), block(256);
-  dispatch_mode(mode, [&](auto m) {
-    hipLaunchKernelGGL(collate_rows_kernel<decltype(m)::value>, grid, block, 0, s, P);
-  });
+  if (code) {
+    dispatch_code_mode(mode, [&](auto m) {
+      hipLaunchKernelGGL((collate_rows_kernel<decltype(m)::value, true>), grid, block, 0, s, P);
+    });
+  } else {
+    dispatch_mode(mode, [&](auto m) {
+      hipLaunchKernelGGL((collate_rows_kernel<decltype(m)::value, false>), grid, block, 0, s, P);
+    });
+  }
   return hipGetLastError();
 }
 

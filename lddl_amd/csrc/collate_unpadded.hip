@@ -14,6 +14,10 @@
 //     (collate_row.h), never on a pad column
 //   position_ids[t] = j;  next_sentence_labels[r] = flags[g] & 1
 //
+// With CODE the rows are CodeBERT rows (lddl_collate_code_rows_unpadded), as in
+// collate_rows.hip: n_r = a + b + 2 + s with s = flags bit 1, modes 0 and 2, no
+// next_sentence_labels.
+//
 // Offsets pass: cu_seqlens is an exclusive scan of n_r, the chunked scan of
 // collate_row.h over one quantity: every block sums its chunk of kChunk rows
 // (collate_cu_sum_kernel), then collate_cu_scan_kernel is the second level.
@@ -45,6 +49,7 @@
 namespace lddl {
 namespace {
 
+template <bool CODE>
 __global__ __launch_bounds__(256) void collate_cu_sum_kernel(CollateUnpaddedParams P) {
   __shared__ uint32_t s_sum;
   if (threadIdx.x == 0) s_sum = 0;
@@ -57,7 +62,7 @@ __global__ __launch_bounds__(256) void collate_cu_sum_kernel(CollateUnpaddedPara
       // an out-of-range row sets the error word and counts 0
       const int64_t g = pack_row(P.R, r);
       if (g < 0) set_err(P.R.err, CERR_ROW_INDEX, r);
-      const uint32_t v = g < 0 ? 0u : row_tokens(P.R, g);
+      const uint32_t v = g < 0 ? 0u : row_tokens<CODE>(P.R, g);
       s += v;
       m = max(m, v);
     }
@@ -72,6 +77,7 @@ __global__ __launch_bounds__(256) void collate_cu_sum_kernel(CollateUnpaddedPara
   if (threadIdx.x == 0) P.chunk_sum[blockIdx.x] = s_sum;
 }
 
+template <bool CODE>
 __global__ __launch_bounds__(256) void collate_cu_scan_kernel(CollateUnpaddedParams P) {
   __shared__ ChunkScanLds<1> S;
   chunk_scan_bases(S, P.n_chunks, [&](int64_t c, unsigned long long (&q)[1]) { q[0] = P.chunk_sum[c]; });
@@ -89,7 +95,7 @@ __global__ __launch_bounds__(256) void collate_cu_scan_kernel(CollateUnpaddedPar
     uint32_t v[1] = {0};
     if (r < P.R.n_rows) {
       const int64_t g = pack_row(P.R, r);
-      if (g >= 0) v[0] = row_tokens(P.R, g);
+      if (g >= 0) v[0] = row_tokens<CODE>(P.R, g);
     }
     chunk_scan_step(S, it, v, carry, end);
     if (r < P.R.n_rows) P.cu_seqlens[r + 1] = (int32_t)end[0];
@@ -98,8 +104,9 @@ __global__ __launch_bounds__(256) void collate_cu_scan_kernel(CollateUnpaddedPar
 
 }  // namespace
 
-template <int MODE>
+template <int MODE, bool CODE>
 __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedParams P) {
+  static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
   // mode 1 only: per wave, label | token << 16 of every masked token
   __shared__ uint32_t s_mlm[MODE == COLLATE_STATIC ? 4 : 1][MODE == COLLATE_STATIC ? COLLATE_MAX_LEN : 1];
   const CollateRowsParams& R = P.R;
@@ -112,7 +119,7 @@ __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedPa
                       (uintptr_t)R.labels) & 15) == 0;
   for (int64_t r = (int64_t)blockIdx.x * 4 + w; r < R.n_rows; r += nw) {
     OpenRow S;
-    uint32_t code = open_row(R, r, COLLATE_MAX_LEN, S);
+    uint32_t code = open_row<CODE>(R, r, COLLATE_MAX_LEN, S);
     int32_t n = 0;
     int64_t c0 = 0;
     if (!code) {
@@ -134,7 +141,7 @@ __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedPa
     if (wide) {
       // pair q holds tokens 2q - head and 2q - head + 1: 16-B aligned in the
       // stream.  The first pair of an odd start and the last of an odd end have
-      // one token of this row (n >= 3: never the same pair, never neither).
+      // one token of this row (n >= 2: never the same pair, never neither).
       const int32_t head = (int32_t)(c0 & 1);
       const int32_t nq = (head + n + 1) >> 1;
       for (int32_t q = lane; q < nq; q += 64) {
@@ -166,24 +173,35 @@ __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedPa
         o_lab[j] = t.lab;
       }
     }
-    if (lane == 0) R.next_sentence_labels[r] = S.flags & 1u;
+    if (!CODE && lane == 0) R.next_sentence_labels[r] = S.flags & 1u;
   }
 }
 
-hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, hipStream_t s) {
+hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, hipStream_t s) {
   if (P.R.n_rows <= 0) return hipSuccess;
   const dim3 grid((unsigned)P.n_chunks), block(256);
-  hipLaunchKernelGGL(collate_cu_sum_kernel, grid, block, 0, s, P);
-  hipLaunchKernelGGL(collate_cu_scan_kernel, grid, block, 0, s, P);
+  if (code) {
+    hipLaunchKernelGGL(collate_cu_sum_kernel<true>, grid, block, 0, s, P);
+    hipLaunchKernelGGL(collate_cu_scan_kernel<true>, grid, block, 0, s, P);
+  } else {
+    hipLaunchKernelGGL(collate_cu_sum_kernel<false>, grid, block, 0, s, P);
+    hipLaunchKernelGGL(collate_cu_scan_kernel<false>, grid, block, 0, s, P);
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, int32_t mode, int n_cu, hipStream_t s) {
+hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.R.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.R.n_rows, n_cu)), block(256);
-  dispatch_mode(mode, [&](auto m) {
-    hipLaunchKernelGGL(collate_unpadded_kernel<decltype(m)::value>, grid, block, 0, s, P);
-  });
+  if (code) {
+    dispatch_code_mode(mode, [&](auto m) {
+      hipLaunchKernelGGL((collate_unpadded_kernel<decltype(m)::value, true>), grid, block, 0, s, P);
+    });
+  } else {
+    dispatch_mode(mode, [&](auto m) {
+      hipLaunchKernelGGL((collate_unpadded_kernel<decltype(m)::value, false>), grid, block, 0, s, P);
+    });
+  }
   return hipGetLastError();
 }
 

@@ -18,6 +18,18 @@
 //     ([CLS], [SEP] or the A / B id there: a masked shard's A and B hold the
 //     masked tokens already).
 //
+// A CodeBERT shard (CODE; lddl_code_rows_from_strings, the columns doc, code and
+// num_tokens of pretrain_codebert.py:425-433, for which the reference has no
+// loader) goes through the same three kernels.  Per row a = #tokens of doc,
+// b = #tokens of code and s = num_tokens - a - b - 2, which says whether a
+// [SEP] follows the doc segment:
+//   len0[r] = a, len1[r] = b, flags[r] = s << 1, ids and src0 / src1 as above
+//   tok_off = exclusive scan of a + b + 2 + s
+// There are no static columns; the scan's second quantity is s in place of k
+// (read from num_tokens again, so nothing travels through mlm_off).  A row
+// whose s is not 0 or 1, or is 0 with a > 0 (doc tokens with no [SEP] to end
+// them), is refused with CERR_CODE_ROW by both passes.
+//
 // Work mapping, as collate.hip: one wave per row, four rows per block, 64
 // bytes per step, the owning lane looks its token up.  Ids go straight to
 // global memory from the owning lane, 2 B each (no LDS anywhere in this file);
@@ -80,8 +92,15 @@ __device__ __forceinline__ uint32_t static_columns(const RowsFromStringsParams& 
   return __ballot(bad) ? CERR_POS_RANGE : 0u;
 }
 
+// CodeBERT: s of row r whose segments hold na and nb tokens, or -1 when num_tokens[r] allows none
+__device__ __forceinline__ int32_t code_sep(const RowsFromStringsParams& P, int64_t r, int32_t na, int32_t nb) {
+  const int32_t s = (int32_t)P.num_tokens[r] - na - nb - 2;
+  return (s == 1 || (s == 0 && na == 0)) ? s : -1;
+}
+
 }  // namespace
 
+template <bool CODE>
 __global__ __launch_bounds__(256) void rows_len_kernel(RowsFromStringsParams P) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * 4;
@@ -89,8 +108,10 @@ __global__ __launch_bounds__(256) void rows_len_kernel(RowsFromStringsParams P) 
     int32_t na = count_tokens(P.C.a, P.C.a_off[r], P.C.a_off[r + 1]);
     int32_t nb = count_tokens(P.C.b, P.C.b_off[r], P.C.b_off[r + 1]);
     uint32_t code = (na > kMaxSeg || nb > kMaxSeg) ? (uint32_t)CERR_LONG : 0u;
-    int64_t np = 0;
-    if (P.C.pos && !code) {
+    int64_t np = 0;  // the high half of the chunk sum: masked positions, or (CODE) s
+    if (CODE) {
+      if (!code && (np = code_sep(P, r, na, nb)) < 0) code = CERR_CODE_ROW;
+    } else if (P.C.pos && !code) {
       const uint8_t* d;
       code = static_columns(P, r, na + nb + 3, d, np);
     }
@@ -105,6 +126,7 @@ __global__ __launch_bounds__(256) void rows_len_kernel(RowsFromStringsParams P) 
   }
 }
 
+template <bool CODE>
 __global__ __launch_bounds__(256) void rows_scan_kernel(RowsFromStringsParams P) {
   __shared__ ChunkScanLds<2> S;
   chunk_scan_bases(S, P.n_chunks, [&](int64_t c, unsigned long long (&q)[2]) {
@@ -114,36 +136,38 @@ __global__ __launch_bounds__(256) void rows_scan_kernel(RowsFromStringsParams P)
   });
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     P.totals[0] = (int64_t)S.total[0];
-    P.totals[1] = (int64_t)S.total[0] + 3 * P.n_rows;
+    P.totals[1] = (int64_t)S.total[0] + (CODE ? 2 * P.n_rows + (int64_t)S.total[1] : 3 * P.n_rows);
     P.totals[2] = (int64_t)S.total[1];
     if (P.tok_off) P.tok_off[0] = 0;
     if (P.mlm_off) P.mlm_off[0] = 0;
   }
   const int64_t lo = (int64_t)blockIdx.x * kChunk;
-  int64_t carry[2] = {(int64_t)S.base[0], (int64_t)S.base[1]}, end[2];  // ids, positions
+  int64_t carry[2] = {(int64_t)S.base[0], (int64_t)S.base[1]}, end[2];  // ids, positions (CODE: rows with s = 1)
   for (int it = 0; it < kChunk / 256; ++it) {
     const int64_t r = lo + it * 256 + threadIdx.x;
     uint32_t a = 0, b = 0, k = 0;
     if (r < P.n_rows) {
       a = P.len0[r];
       b = P.len1[r];
-      if (P.mlm_off) k = (uint32_t)P.mlm_off[r + 1];  // rows_len_kernel's k_r <= kMaxMask
+      if (CODE) k = code_sep(P, r, (int32_t)a, (int32_t)b) == 1;  // a row the length kernel refused counts 0
+      else if (P.mlm_off) k = (uint32_t)P.mlm_off[r + 1];  // rows_len_kernel's k_r <= kMaxMask
     }
     const uint32_t v[2] = {a + b, k};
     chunk_scan_step(S, it, v, carry, end);
     if (r < P.n_rows) {
       P.src0[r] = end[0] - (a + b);  // end[0]: the ids of rows [0, r]
       P.src1[r] = end[0] - b;
-      if (P.tok_off) P.tok_off[r + 1] = end[0] + 3 * (r + 1);
+      if (P.tok_off) P.tok_off[r + 1] = end[0] + (CODE ? 2 * (r + 1) + end[1] : 3 * (r + 1));
       if (P.mlm_off) P.mlm_off[r + 1] = end[1];
     }
   }
 }
 
+template <bool CODE>
 __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P) {
   const int lane = threadIdx.x & 63;
   const int64_t nw = (int64_t)gridDim.x * 4;
-  const bool stat = P.C.pos != nullptr;
+  const bool stat = !CODE && P.C.pos != nullptr;
   const CollateVocab& V = P.V;
   const StringColumns& C = P.C;
   {
@@ -166,7 +190,9 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
     // s0 is bounded before anything is added to it
     if (na != (int32_t)P.len0[r] || nb != (int32_t)P.len1[r] || s0 < 0 || s0 > P.ids_cap - na - nb || s1 != s0 + na)
       code = CERR_ROW_COUNTS;
-    const RowLayout S{na, na + nb + 3};
+    const int32_t sep = CODE ? code_sep(P, r, na, nb) : 1;
+    if (!code && sep < 0) code = CERR_CODE_ROW;
+    const RowLayout S{na, na + nb + 3};  // (the static columns': BERT rows)
     const uint8_t* d = nullptr;
     int64_t np = 0, m0 = 0;
     if (stat && !code) {
@@ -190,7 +216,7 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
       const int32_t id = vocab_lookup(V, C.b, i, b1, end);
       if (k < nb) ob[k] = (uint16_t)id;
     });
-    if (lane == 0) P.flags[r] = (uint8_t)((P.is_random_next[r] ? 1u : 0u) | 2u);
+    if (lane == 0) P.flags[r] = CODE ? (uint8_t)(sep << 1) : (uint8_t)((P.is_random_next[r] ? 1u : 0u) | 2u);
     if (stat && np > 0) {
       // the ids other lanes of this wave stored are read below: the stores are made visible, and no lane's load
       // is scheduled in front of the point all lanes have reached
@@ -215,14 +241,20 @@ __global__ __launch_bounds__(256) void rows_fill_kernel(RowsFromStringsParams P)
 
 hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(rows_len_kernel, dim3(grid_rows(P.n_rows, n_cu)), dim3(256), 0, s, P);
-  hipLaunchKernelGGL(rows_scan_kernel, dim3((unsigned)P.n_chunks), dim3(256), 0, s, P);
+  if (P.num_tokens) {
+    hipLaunchKernelGGL(rows_len_kernel<true>, dim3(grid_rows(P.n_rows, n_cu)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(rows_scan_kernel<true>, dim3((unsigned)P.n_chunks), dim3(256), 0, s, P);
+  } else {
+    hipLaunchKernelGGL(rows_len_kernel<false>, dim3(grid_rows(P.n_rows, n_cu)), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(rows_scan_kernel<false>, dim3((unsigned)P.n_chunks), dim3(256), 0, s, P);
+  }
   return hipGetLastError();
 }
 
 hipError_t launch_rows_from_strings(const RowsFromStringsParams& P, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
-  hipLaunchKernelGGL(rows_fill_kernel, dim3(grid_rows(P.n_rows, n_cu)), dim3(256), 0, s, P);
+  if (P.num_tokens) hipLaunchKernelGGL(rows_fill_kernel<true>, dim3(grid_rows(P.n_rows, n_cu)), dim3(256), 0, s, P);
+  else hipLaunchKernelGGL(rows_fill_kernel<false>, dim3(grid_rows(P.n_rows, n_cu)), dim3(256), 0, s, P);
   return hipGetLastError();
 }
 

@@ -16,6 +16,11 @@ csrc/rows_from_strings.hip): the shard's rows become a ``PackResult`` with
 spans on the GPU, and ``collate_rows`` / ``collate_rows_unpadded`` /
 ``RowBatches`` then serve files on disk as they serve a pack result.
 
+``CodeCollate`` is the same surface for the CodeBERT preprocessor's rows (doc /
+code / num_tokens, pretrain_codebert.py:425-433), for which the reference has
+no loader at all: ``collate_rows`` / ``collate_rows_unpadded`` over a CodeBERT
+pack result, ``load_rows`` / ``load_shards`` over CodeBERT shards.
+
 Differences from the reference, by design:
 * dynamic masking draws from a counter-based hash of (seed, batch counter, row,
   column), not torch's CPU generator: the same distribution (mask rate
@@ -89,6 +94,24 @@ def _table_columns(table, static):
           np.asarray(table.column('is_random_next').to_numpy(zero_copy_only=False), dtype=np.uint8))
 
 
+def _code_shard_columns(table):
+  """CodeCollate.load_rows' input -> ([doc, code] as (bytes, offsets), num_tokens uint16)"""
+  table = list([table] if hasattr(table, 'schema') else table)
+  if not table:
+    raise ValueError('no rows')
+  for t in table:
+    names = t.schema.names if hasattr(t, 'schema') else ()
+    if 'doc' not in names or 'code' not in names or 'num_tokens' not in names:
+      raise ValueError('not a CodeBERT shard (columns %s): doc, code and num_tokens are needed; BertCollate loads '
+                       'BERT shards' % (list(names),))
+  parts = [[_arrow_column(t.column(k)) for k in ('doc', 'code')] for t in table]
+  cols = [_merge_columns([c[k] for c in parts]) for k in range(2)]
+  nt = [np.asarray(t.column('num_tokens').to_numpy(zero_copy_only=False)) for t in table]
+  if any(len(x) and (x.min() < 0 or x.max() > 65535) for x in nt):
+    raise ValueError('num_tokens outside uint16')
+  return cols, np.concatenate(nt).astype(np.uint16)
+
+
 def _shard_columns(table):
   """load_rows' input -> ([A, B(, positions, labels)] as (bytes, offsets), is_random_next bytes, static)"""
   if hasattr(table, 'schema'):
@@ -103,7 +126,7 @@ def _shard_columns(table):
     return _sample_columns(table, static) + (static,)
   for t in table:
     if 'A' not in t.schema.names or 'B' not in t.schema.names:
-      raise ValueError('not a BERT shard (columns %s): CodeBERT shards have no loader' % (t.schema.names,))
+      raise ValueError('not a BERT shard (columns %s): CodeBERT shards are loaded by CodeCollate' % (t.schema.names,))
   static = 'masked_lm_positions' in table[0].schema.names
   for t in table:
     if ('masked_lm_positions' in t.schema.names) != static or (static and 'masked_lm_labels' not in t.schema.names):
@@ -162,8 +185,10 @@ def load_shards(collate, path_or_paths):
   files of a list) as one GPU row table: read with pyarrow in (partition, bin)
   order (shard_files), each row's bin from its file's suffix and its partition
   from ``part.<p>`` (the preprocessor's sink) or ``shard-<k>`` (the load
-  balancer's output), then one ``collate.load_rows``.  Files without A / B
-  columns (CodeBERT shards) raise ValueError."""
+  balancer's output), then one ``collate.load_rows``.  The collate decides
+  what is read: a BertCollate takes BERT shards (A / B / is_random_next and the
+  static columns), a CodeCollate CodeBERT shards (doc / code / num_tokens; the
+  id column is not loaded).  Shards of the other kind raise ValueError."""
   import pyarrow.parquet as pq
   if isinstance(path_or_paths, (str, bytes, os.PathLike)):
     path = os.fspath(path_or_paths)
@@ -179,8 +204,9 @@ def load_shards(collate, path_or_paths):
   tables, bins, part = [], [], []
   for name, pt, b in files:
     t = pq.read_table(name)
-    if 'A' not in t.schema.names or 'B' not in t.schema.names:
-      raise ValueError('%s is not a BERT shard (columns %s): CodeBERT shards have no loader' % (name, t.schema.names))
+    if any(k not in t.schema.names for k in collate.SHARD_COLUMNS):
+      raise ValueError('%s is not a %s shard (columns %s): %s' % (name, collate.SHARD_KIND, t.schema.names,
+                                                                 collate.OTHER_SHARDS))
     if t.num_rows == 0:
       continue  # every bin is written, even when empty
     tables.append(t)
@@ -193,20 +219,19 @@ def load_shards(collate, path_or_paths):
   return collate.load_rows(tables, np.concatenate(bins) if binned else None, np.concatenate(part), nbins)
 
 
-class BertCollate:
-  """``collate(batch) -> dict`` with the keys of bert.py:129-152 plus
-  ``labels`` (masked): input_ids, token_type_ids, attention_mask, labels,
-  next_sentence_labels -- int64 tensors on the GPU.
+class _RowCollate:
+  """What BertCollate and CodeCollate share: the constructor, the staging of
+  string columns, the collate of row-table batches (padded and padding-free),
+  the making of a row table and ``mask_tokens``.  CODE says which kind of row
+  the C calls are for."""
+  CODE = False
+  VOCAB = _lib.VOCAB_BERT
 
-  batch: a list of samples as the reference's DataLoader hands to its
-  collate_fn (tuples of 3 or 5 fields), or a pyarrow RecordBatch / Table of
-  the shard schema (zero-copy columns; ``collate_arrow``)."""
-
-  def __init__(self, vocab_file=_lib.VOCAB_BERT, device=None, sequence_length_alignment=8, ignore_index=-1,
+  def __init__(self, vocab_file=None, device=None, sequence_length_alignment=8, ignore_index=-1,
                mlm_probability=0.15, base_seed=12345, tokenizer=None):
     assert isinstance(sequence_length_alignment, int) and sequence_length_alignment >= 1
     assert isinstance(mlm_probability, (int, float)) and 0 <= mlm_probability <= 1
-    self.tok = tokenizer if tokenizer is not None else Tokenizer(vocab_file, device)
+    self.tok = tokenizer if tokenizer is not None else Tokenizer(vocab_file or self.VOCAB, device)
     self.device = self.tok.device
     self.sequence_length_alignment = sequence_length_alignment
     self.ignore_index = int(ignore_index)
@@ -215,14 +240,15 @@ class BertCollate:
     self.counter = 0  # one per collated batch: the dynamic masks differ per batch
 
   # ---- staging ------------------------------------------------------------
-  def _upload(self, cols, is_random_next):
-    """One pinned host buffer holding every column (16-B aligned pieces), one
-    H2D copy; returns device addresses of each piece."""
+  def _upload(self, cols, per_row):
+    """One pinned host buffer holding every column and the per-row array
+    (is_random_next bytes, or num_tokens) as 16-B aligned pieces, one H2D
+    copy; returns device addresses of each piece."""
     pieces = []
     for data, off in cols:
       pieces.append(data)
       pieces.append(off.view(np.uint8))
-    pieces.append(np.ascontiguousarray(is_random_next, dtype=np.uint8))
+    pieces.append(np.ascontiguousarray(per_row).view(np.uint8))
     starts, pos = [], 0
     for p in pieces:
       starts.append(pos)
@@ -235,6 +261,166 @@ class BertCollate:
     dev.copy_(host, non_blocking=True)
     base = dev.data_ptr()
     return dev, host, [base + s for s in starts]
+
+  def _row_batch(self, who, res, rows, row0, n_rows, mode):
+    """what collate_rows / collate_rows_unpadded (who) take -> (mode, rows, row0, n)"""
+    if not res.spans:
+      raise ValueError('%s needs a PackResult with spans (Packer.pack(..., spans=True))' % who)
+    if mode is None:
+      mode = MODE_STATIC if res.mlm_token is not None and not self.CODE else MODE_DYNAMIC
+    if mode not in (MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC):
+      raise ValueError('mode %r not in 0..2' % (mode,))
+    if mode == MODE_STATIC and self.CODE:
+      raise ValueError('CodeBERT rows have no static masks: mode 0 or 2')
+    if mode == MODE_STATIC and res.mlm_token is None:
+      raise ValueError('static mode needs a result packed with masking=True')
+    if rows is not None:
+      rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device).contiguous().view(-1)
+      n, row0 = rows.numel(), 0
+    else:
+      row0 = int(row0)
+      n = res.n_pairs - row0 if n_rows is None else int(n_rows)
+    if n <= 0:
+      raise ValueError('empty batch')  # max() of an empty sequence in bert.py:94-95
+    return mode, rows, row0, n
+
+  def _collate(self, unpadded, res, rows, row0, n_rows, mode):
+    """collate_rows (unpadded False) and collate_rows_unpadded of both classes:
+    the length call (lddl_collate[_code]_rows_seq_len / _cu_seqlens), the
+    outputs it sizes, the fill call, the batch counter and the dict."""
+    who = 'collate_rows_unpadded' if unpadded else 'collate_rows'
+    mode, rows, row0, n = self._row_batch(who, res, rows, row0, n_rows, mode)
+    L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
+    name = 'lddl_collate_code_rows' if self.CODE else 'lddl_collate_rows'
+    lens = (p(res.len0), p(res.len1)) + ((p(res.flags),) if self.CODE else ())
+    pick = (p(rows), row0, n, res.n_pairs)
+    if unpadded:
+      cu = torch.empty(n + 1, dtype=torch.int32, device=self.device)
+      total, longest = ctypes.c_int64(), ctypes.c_int64()
+      _check(getattr(L, name + '_cu_seqlens')(h, *lens, *pick, p(cu), ctypes.byref(total), ctypes.byref(longest), st))
+      T = int(total.value)
+      out = torch.empty((4, T), dtype=torch.int64, device=self.device)
+      shape = (p(cu), T)
+    else:
+      seq = ctypes.c_int64()
+      _check(getattr(L, name + '_seq_len')(h, *lens, *pick, self.sequence_length_alignment, ctypes.byref(seq), st))
+      S = int(seq.value)
+      out = torch.empty((4, n, S), dtype=torch.int64, device=self.device)
+      shape = (S,)
+    table = (p(res.ids), p(res.src0), p(res.src1), p(res.len0), p(res.len1), p(res.flags))
+    draw = (mode, self.ignore_index, self.mlm_probability, self.seed, self.counter)
+    outs = tuple(p(out[k]) for k in range(4))
+    if self.CODE:
+      nsl, mlm, tail = None, (), ()
+    else:
+      nsl = torch.empty(n, dtype=torch.int64, device=self.device)
+      mlm = (res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token) if mode == MODE_STATIC else (None,) * 4
+      mlm, tail = tuple(p(x) for x in mlm), (p(nsl),)
+    rc = getattr(L, name + ('_unpadded' if unpadded else ''))(h, *table, *pick, *mlm, *shape, *draw, *outs, *tail, st)
+    if mode != MODE_SPECIAL_MASK:
+      self.counter += 1
+    _check(rc)
+    batch = {'input_ids': out[0], 'token_type_ids': out[1], 'position_ids' if unpadded else 'attention_mask': out[2],
+             'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
+    if nsl is not None:
+      batch['next_sentence_labels'] = nsl
+    if unpadded:
+      batch['cu_seqlens'], batch['max_seqlen'] = cu, int(longest.value)
+    return batch
+
+  def _load_table(self, cols, per_row, static, bins, part, nbins):
+    """load_rows of both classes over staged columns: the length call, the
+    table it sizes, the fill call and the PackResult.  per_row: is_random_next
+    bytes, or (CodeCollate) num_tokens."""
+    from .pipeline import PackResult
+    n = len(per_row)
+    if n == 0:
+      raise ValueError('no rows')
+    L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
+    dev, host, ptrs = self._upload(cols, per_row)
+    if self.CODE:
+      inp = [p(x) for x in ptrs[:4]] + [p(ptrs[-1])]
+    else:
+      inp = [p(x) for x in ptrs[:8]] if static else [p(x) for x in ptrs[:4]] + [p(None)] * 4
+
+    def buf(m, dtype):
+      return torch.empty(max(m, 1), dtype=dtype, device=self.device)
+    len0, len1 = buf(n, torch.int16), buf(n, torch.int16)
+    src0, src1 = buf(n, torch.int64), buf(n, torch.int64)
+    tok_off = buf(n + 1, torch.int64)
+    mlm_off = buf(n + 1, torch.int64) if static else None
+    tot = (ctypes.c_int64 * 3)()
+    spans = (p(len0), p(len1), p(src0), p(src1))
+    try:
+      if self.CODE:
+        _check(L.lddl_code_rows_from_strings_len(h, *inp, n, *spans, p(tok_off), tot, st))
+      else:
+        _check(L.lddl_rows_from_strings_len(h, *inp, n, *spans, p(tok_off), p(mlm_off), tot, st))
+    except Exception:
+      torch.cuda.current_stream().synchronize()  # a call refused before its launch leaves the staging copy queued
+      raise
+    n_ids, n_masked, n_tokens = (int(tot[0]), 0, int(tot[1])) if self.CODE else (int(tot[0]), int(tot[1]), int(tot[2]))
+    ids = torch.empty(n_ids + 16, dtype=torch.int16, device=self.device)  # 16 zeroed entries behind the last id
+    ids[n_ids:].zero_()
+    flags = buf(n, torch.uint8)
+    mlm = [buf(n_masked, torch.int16) for _ in range(3)] if static else [None] * 3
+    if self.CODE:
+      _check(L.lddl_code_rows_from_strings(h, *inp, n, *spans, p(ids), n_ids, p(flags), st))
+    else:
+      _check(L.lddl_rows_from_strings(h, *inp, p(ptrs[-1]), n, *spans, p(mlm_off), p(ids), n_ids, p(flags), p(mlm[0]),
+                                      p(mlm[1]), p(mlm[2]), n_masked, st))
+    del dev, host  # the length call synchronised the stream behind the staging copy
+    part_h = np.zeros(n, np.int64) if part is None else np.ascontiguousarray(part, dtype=np.int64).reshape(-1)
+    bins_h = np.zeros(n, np.uint8) if bins is None else np.ascontiguousarray(bins, dtype=np.uint8).reshape(-1)
+    if len(part_h) != n or len(bins_h) != n:
+      raise ValueError('bins / part: one entry per row')
+    if bins is None:
+      nbins = 1
+    elif nbins is None:
+      nbins = int(bins_h.max()) + 1
+    if int(bins_h.max()) >= nbins:
+      raise ValueError('a bin id >= nbins %d' % nbins)
+    n_part = int(part_h.max()) + 1
+    bin_count = np.bincount(part_h * nbins + bins_h, minlength=n_part * nbins).reshape(n_part, nbins).astype(np.int64)
+    h2d = lambda a: torch.from_numpy(a).to(self.device)  # noqa: E731
+    res = PackResult(n, n_tokens, int(nbins), None, tok_off, len0, len1, flags, h2d(bins_h), h2d(part_h),
+                     h2d(bin_count))
+    res.ids, res.src0, res.src1 = ids, src0, src1
+    res.cls_id, res.sep_id = self.tok.cls_id, self.tok.sep_id
+    if static:
+      res.n_masked = n_masked
+      res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token = mlm_off, mlm[0], mlm[1], mlm[2]
+    return res
+
+  def mask_tokens(self, inputs, special_tokens_mask, counter=None):
+    """bert.py:156-196 on device tensors: masks ``inputs`` in place and
+    returns (inputs, labels).  counter: the batch counter of the draws
+    (default: the next one)."""
+    assert inputs.dtype == torch.int64 and inputs.is_cuda and inputs.is_contiguous()
+    sp = special_tokens_mask.to(device=self.device, dtype=torch.int64).contiguous()
+    assert sp.shape == inputs.shape
+    labels = torch.empty_like(inputs)
+    n, S = inputs.shape
+    if counter is None:
+      counter = self.counter
+      self.counter += 1
+    _lib.check(_lib.lib().lddl_mask_tokens(self.tok.handle, ctypes.c_void_p(inputs.data_ptr()),
+                                           ctypes.c_void_p(sp.data_ptr()), ctypes.c_void_p(labels.data_ptr()), n,
+                                           S, self.mlm_probability, self.ignore_index, self.seed, counter,
+                                           _stream()))
+    return inputs, labels
+
+
+class BertCollate(_RowCollate):
+  """``collate(batch) -> dict`` with the keys of bert.py:129-152 plus
+  ``labels`` (masked): input_ids, token_type_ids, attention_mask, labels,
+  next_sentence_labels -- int64 tensors on the GPU.
+
+  batch: a list of samples as the reference's DataLoader hands to its
+  collate_fn (tuples of 3 or 5 fields), or a pyarrow RecordBatch / Table of
+  the shard schema (zero-copy columns; ``collate_arrow``)."""
+  SHARD_COLUMNS, SHARD_KIND = ('A', 'B'), 'BERT'
+  OTHER_SHARDS = 'CodeBERT shards are loaded by CodeCollate'
 
   def _run(self, cols, is_random_next, static, mode=None):
     """lddl_collate_seq_len + lddl_collate_bert over staged columns.  mode None:
@@ -282,26 +468,6 @@ class BertCollate:
       assert 'masked_lm_labels' in table.schema.names
     return self._run(*_table_columns(table, static), static)
 
-  def _row_batch(self, who, res, rows, row0, n_rows, mode):
-    """what collate_rows / collate_rows_unpadded (who) take -> (mode, rows, row0, n)"""
-    if not res.spans:
-      raise ValueError('%s needs a PackResult with spans (Packer.pack(..., spans=True))' % who)
-    if mode is None:
-      mode = MODE_STATIC if res.mlm_token is not None else MODE_DYNAMIC
-    if mode not in (MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC):
-      raise ValueError('mode %r not in 0..2' % (mode,))
-    if mode == MODE_STATIC and res.mlm_token is None:
-      raise ValueError('static mode needs a result packed with masking=True')
-    if rows is not None:
-      rows = torch.as_tensor(rows, dtype=torch.int64, device=self.device).contiguous().view(-1)
-      n, row0 = rows.numel(), 0
-    else:
-      row0 = int(row0)
-      n = res.n_pairs - row0 if n_rows is None else int(n_rows)
-    if n <= 0:
-      raise ValueError('empty batch')  # max() of an empty sequence in bert.py:94-95
-    return mode, rows, row0, n
-
   def collate_rows(self, res, rows=None, row0=0, n_rows=None, mode=None):
     """A batch straight from a pack result on the GPU (lddl_collate_rows):
     the rows ``rows`` (an int64 CUDA tensor, or anything torch.as_tensor
@@ -314,24 +480,7 @@ class BertCollate:
     the host: the kernel reads the packer's own buffers.  ``res`` must have
     been packed with this collate's vocab, on its device; a CodeBERT result
     (rows without the [SEP] after segment 0) is refused by the C call."""
-    mode, rows, row0, n = self._row_batch('collate_rows', res, rows, row0, n_rows, mode)
-    L, st, p = _lib.lib(), _stream(), _ptr
-    seq = ctypes.c_int64()
-    _check(L.lddl_collate_rows_seq_len(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
-                                       self.sequence_length_alignment, ctypes.byref(seq), st))
-    S = int(seq.value)
-    out = torch.empty((4, n, S), dtype=torch.int64, device=self.device)
-    nsl = torch.empty(n, dtype=torch.int64, device=self.device)
-    mlm = (res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token) if mode == MODE_STATIC else (None,) * 4
-    rc = L.lddl_collate_rows(self.tok.handle, p(res.ids), p(res.src0), p(res.src1), p(res.len0), p(res.len1),
-                             p(res.flags), p(rows), row0, n, res.n_pairs, p(mlm[0]), p(mlm[1]), p(mlm[2]), p(mlm[3]),
-                             S, mode, self.ignore_index, self.mlm_probability, self.seed, self.counter,
-                             p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nsl), st)
-    if mode != MODE_SPECIAL_MASK:
-      self.counter += 1
-    _check(rc)
-    return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2], 'next_sentence_labels': nsl,
-            'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
+    return self._collate(False, res, rows, row0, n_rows, mode)
 
   def collate_rows_unpadded(self, res, rows=None, row0=0, n_rows=None, mode=None):
     """The batch of ``collate_rows`` without its padding
@@ -346,26 +495,7 @@ class BertCollate:
     with the pad columns dropped, bit for bit.  The batch counter advances as
     in ``collate_rows``.  ``sequence_length_alignment`` has no effect here:
     nothing is padded."""
-    mode, rows, row0, n = self._row_batch('collate_rows_unpadded', res, rows, row0, n_rows, mode)
-    L, st, p = _lib.lib(), _stream(), _ptr
-    cu = torch.empty(n + 1, dtype=torch.int32, device=self.device)
-    total, longest = ctypes.c_int64(), ctypes.c_int64()
-    _check(L.lddl_collate_rows_cu_seqlens(self.tok.handle, p(res.len0), p(res.len1), p(rows), row0, n, res.n_pairs,
-                                          p(cu), ctypes.byref(total), ctypes.byref(longest), st))
-    T = int(total.value)
-    out = torch.empty((4, T), dtype=torch.int64, device=self.device)
-    nsl = torch.empty(n, dtype=torch.int64, device=self.device)
-    mlm = (res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token) if mode == MODE_STATIC else (None,) * 4
-    rc = L.lddl_collate_rows_unpadded(self.tok.handle, p(res.ids), p(res.src0), p(res.src1), p(res.len0),
-                                      p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs, p(mlm[0]), p(mlm[1]),
-                                      p(mlm[2]), p(mlm[3]), p(cu), T, mode, self.ignore_index, self.mlm_probability,
-                                      self.seed, self.counter, p(out[0]), p(out[1]), p(out[2]), p(out[3]), p(nsl), st)
-    if mode != MODE_SPECIAL_MASK:
-      self.counter += 1
-    _check(rc)
-    return {'input_ids': out[0], 'token_type_ids': out[1], 'position_ids': out[2], 'next_sentence_labels': nsl,
-            'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3], 'cu_seqlens': cu,
-            'max_seqlen': int(longest.value)}
+    return self._collate(True, res, rows, row0, n_rows, mode)
 
   def load_rows(self, table, bins=None, part=None, nbins=None):
     """The rows of a shard as a GPU row table, once (lddl_rows_from_strings_len
@@ -383,58 +513,8 @@ class BertCollate:
     them nbins defaults to max(bins) + 1.  The columns are staged in one pinned
     buffer and copied once; the staging is released when the call returns.
     Fields that only a pack has stay None: tokens, ntok, ids_off, pack."""
-    from .pipeline import PackResult
     cols, rn, static = _shard_columns(table)
-    n = len(rn)
-    if n == 0:
-      raise ValueError('no rows')
-    L, st, p = _lib.lib(), _stream(), _ptr
-    dev, host, ptrs = self._upload(cols, rn)
-    inp = [p(x) for x in ptrs[:8]] if static else [p(x) for x in ptrs[:4]] + [p(None)] * 4
-
-    def buf(m, dtype):
-      return torch.empty(max(m, 1), dtype=dtype, device=self.device)
-    len0, len1 = buf(n, torch.int16), buf(n, torch.int16)
-    src0, src1 = buf(n, torch.int64), buf(n, torch.int64)
-    tok_off = buf(n + 1, torch.int64)
-    mlm_off = buf(n + 1, torch.int64) if static else None
-    tot = (ctypes.c_int64 * 3)()
-    try:
-      _check(L.lddl_rows_from_strings_len(self.tok.handle, *inp, n, p(len0), p(len1), p(src0), p(src1), p(tok_off),
-                                          p(mlm_off), tot, st))
-    except Exception:
-      torch.cuda.current_stream().synchronize()  # a call refused before its launch leaves the staging copy queued
-      raise
-    n_ids, n_masked, n_tokens = int(tot[0]), int(tot[1]), int(tot[2])
-    ids = torch.empty(n_ids + 16, dtype=torch.int16, device=self.device)  # 16 zeroed entries behind the last id
-    ids[n_ids:].zero_()
-    flags = buf(n, torch.uint8)
-    mlm = [buf(n_masked, torch.int16) for _ in range(3)] if static else [None] * 3
-    _check(L.lddl_rows_from_strings(self.tok.handle, *inp, p(ptrs[-1]), n, p(len0), p(len1), p(src0), p(src1),
-                                    p(mlm_off), p(ids), n_ids, p(flags), p(mlm[0]), p(mlm[1]), p(mlm[2]), n_masked,
-                                    st))
-    del dev, host  # the length call synchronised the stream behind the staging copy
-    part_h = np.zeros(n, np.int64) if part is None else np.ascontiguousarray(part, dtype=np.int64).reshape(-1)
-    bins_h = np.zeros(n, np.uint8) if bins is None else np.ascontiguousarray(bins, dtype=np.uint8).reshape(-1)
-    if len(part_h) != n or len(bins_h) != n:
-      raise ValueError('bins / part: one entry per row')
-    if bins is None:
-      nbins = 1
-    elif nbins is None:
-      nbins = int(bins_h.max()) + 1
-    if int(bins_h.max()) >= nbins:
-      raise ValueError('a bin id >= nbins %d' % nbins)
-    n_part = int(part_h.max()) + 1
-    bin_count = np.bincount(part_h * nbins + bins_h, minlength=n_part * nbins).reshape(n_part, nbins).astype(np.int64)
-    h2d = lambda a: torch.from_numpy(a).to(self.device)  # noqa: E731
-    res = PackResult(n, n_tokens, int(nbins), None, tok_off, len0, len1, flags, h2d(bins_h), h2d(part_h),
-                     h2d(bin_count))
-    res.ids, res.src0, res.src1 = ids, src0, src1
-    res.cls_id, res.sep_id = self.tok.cls_id, self.tok.sep_id
-    if static:
-      res.n_masked = n_masked
-      res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token = mlm_off, mlm[0], mlm[1], mlm[2]
-    return res
+    return self._load_table(cols, rn, static, bins, part, nbins)
 
   # ---- the reference's two steps, separately ----------------------------------
   def to_encoded_inputs(self, batch):
@@ -444,23 +524,51 @@ class BertCollate:
       return self(batch)
     return self._run(*_sample_columns(batch, False), False, mode=MODE_SPECIAL_MASK)
 
-  def mask_tokens(self, inputs, special_tokens_mask, counter=None):
-    """bert.py:156-196 on device tensors: masks ``inputs`` in place and
-    returns (inputs, labels).  counter: the batch counter of the draws
-    (default: the next one)."""
-    assert inputs.dtype == torch.int64 and inputs.is_cuda and inputs.is_contiguous()
-    sp = special_tokens_mask.to(device=self.device, dtype=torch.int64).contiguous()
-    assert sp.shape == inputs.shape
-    labels = torch.empty_like(inputs)
-    n, S = inputs.shape
-    if counter is None:
-      counter = self.counter
-      self.counter += 1
-    _lib.check(_lib.lib().lddl_mask_tokens(self.tok.handle, ctypes.c_void_p(inputs.data_ptr()),
-                                           ctypes.c_void_p(sp.data_ptr()), ctypes.c_void_p(labels.data_ptr()), n,
-                                           S, self.mlm_probability, self.ignore_index, self.seed, counter,
-                                           _stream()))
-    return inputs, labels
+
+class CodeCollate(_RowCollate):
+  """The loader of CodeBERT rows (pretrain_codebert.py:425-433: doc, code,
+  num_tokens), which the reference lacks: same constructor as BertCollate (the
+  CodeBERT vocabulary by default), batches from a CodeBERT pack result or from
+  CodeBERT shards.  A row shows ``[CLS] doc [SEP] code [SEP]`` with
+  token_type_ids 1 on code and its [SEP], or, when its document has no
+  docstring (flags bit 1 clear), ``[CLS] code [SEP]`` with token_type_ids 0:
+  what a BERT tokenizer gives for a pair and for a single sequence.  There is
+  no next_sentence_labels and no static masking; mode defaults to dynamic and
+  draws as BertCollate does, keyed by (seed, batch counter, row, column)."""
+  CODE = True
+  VOCAB = _lib.VOCAB_CODEBERT
+  SHARD_COLUMNS, SHARD_KIND = ('doc', 'code', 'num_tokens'), 'CodeBERT'
+  OTHER_SHARDS = 'BERT shards are loaded by BertCollate'
+
+  def collate_rows(self, res, rows=None, row0=0, n_rows=None, mode=None):
+    """A padded batch of CodeBERT rows (lddl_collate_code_rows), picked as in
+    ``BertCollate.collate_rows``: input_ids, token_type_ids, attention_mask and
+    labels (mode 0: special_tokens_mask, 1 on [CLS], each [SEP] and the
+    padding) as int64 [n, S].  mode 2 (the default) is mode 0 followed by
+    ``mask_tokens`` at the same seed and counter, bit for bit, and advances
+    the batch counter.  On rows that have the first [SEP] the four tensors are
+    those of ``BertCollate.collate_rows``."""
+    return self._collate(False, res, rows, row0, n_rows, mode)
+
+  def collate_rows_unpadded(self, res, rows=None, row0=0, n_rows=None, mode=None):
+    """``collate_rows`` at the same seed and counter with the pad columns
+    dropped, bit for bit (lddl_collate_code_rows_cu_seqlens +
+    lddl_collate_code_rows_unpadded): input_ids, token_type_ids, position_ids
+    and labels (mode 0: special_tokens_mask) as int64 [T], cu_seqlens as int32
+    [n + 1] and max_seqlen as a Python int."""
+    return self._collate(True, res, rows, row0, n_rows, mode)
+
+  def load_rows(self, table, bins=None, part=None, nbins=None):
+    """The rows of a CodeBERT shard as a GPU row table, once
+    (lddl_code_rows_from_strings_len + lddl_code_rows_from_strings): a
+    ``pipeline.PackResult`` with spans, as ``BertCollate.load_rows`` returns.
+    table: a pyarrow Table / RecordBatch with doc, code (string or
+    large_string) and num_tokens columns, or a list of such tables; the id
+    column is not loaded.  A row's num_tokens says whether a [SEP] follows its
+    doc segment (doc + code + 3 tokens) or not (code + 2, with an empty doc);
+    any other value is refused.  bins / part / nbins as there."""
+    cols, nt = _code_shard_columns(table)
+    return self._load_table(cols, nt, False, bins, part, nbins)
 
 
 def plan_row_batches(bins, batch_size, seed=12345, epoch=0, drop_last=False, n_rows=None):
@@ -493,7 +601,8 @@ def plan_row_batches(bins, batch_size, seed=12345, epoch=0, drop_last=False, n_r
 
 def plan_token_batches(lengths, max_tokens, max_rows=None, seed=12345, epoch=0):
   """The batches of one epoch for a padding-free collate, on the host: a list
-  of int64 index arrays.  lengths: the tokens of every row (len0 + len1 + 3).
+  of int64 index arrays.  lengths: the tokens of every row (len0 + len1 + 3; a CodeBERT
+  row without docstring has one fewer).
   All rows are permuted by a generator seeded by (seed, epoch), built as in
   plan_row_batches, and the permutation is cut in order: a batch is closed
   when the next row would take it over max_tokens tokens or max_rows rows.
@@ -533,7 +642,7 @@ class RowBatches:
 
   With ``max_tokens`` in place of ``batch_size`` (exactly one of the two) the
   batches are for ``collate_rows_unpadded``: plan_token_batches over a host
-  copy of len0 + len1 + 3, at most max_tokens tokens (and max_rows rows) each;
+  copy of len0 + len1 + 2 + ((flags >> 1) & 1), at most max_tokens tokens (and max_rows rows) each;
   bins are ignored and drop_last has no meaning."""
 
   def __init__(self, res, batch_size=None, seed=12345, epoch=0, drop_last=False, max_tokens=None, max_rows=None):
@@ -552,7 +661,8 @@ class RowBatches:
       n = res.n_pairs
       l0 = res.len0[:n].cpu().numpy().view(np.uint16).astype(np.int64)  # int16 views of uint16
       l1 = res.len1[:n].cpu().numpy().view(np.uint16).astype(np.int64)
-      self.lengths = l0 + l1 + 3
+      fl = res.flags[:n].cpu().numpy().astype(np.int64)
+      self.lengths = l0 + l1 + 2 + ((fl >> 1) & 1)  # bit 1: the [SEP] after segment 0 (every BERT row has it)
     elif res.nbins > 1:
       self.bins = res.bins[:res.n_pairs].cpu().numpy()
 

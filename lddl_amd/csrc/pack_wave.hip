@@ -418,8 +418,9 @@ struct WaveRng {
 // scratch jq[q]; then the swaps in batches of 64 positions [qmin, qb]: the
 // batch's slots -- its 64 positions (lane t = position qb - t) and the <= 64
 // distinct positions below it that its draws hit -- are gathered into two
-// registers per lane, the 64 swaps run in order on them (readlane +
-// lane select), and the slots are scattered back.  Per 64 swaps: one coalesced
+// registers per lane (two draws on one position share the slot of the first
+// lane that drew it), the 64 swaps run in order on them (readlane + lane
+// select), and the slots are scattered back.  Per 64 swaps: one coalesced
 // read + write and <= 64 parallel gathers, where the swap loop paid a
 // dependent global round trip per swap.
 __device__ __forceinline__ void shuffle_global(WaveRng& rng, int np, int32_t* order, int32_t* jq, int lane) {
@@ -432,15 +433,17 @@ __device__ __forceinline__ void shuffle_global(WaveRng& rng, int np, int32_t* or
     const int j = vq ? jq[q] : 0;
     int va = vq ? order[q] : 0;
     const bool low = vq && j < qmin;
-    // the first lane whose draw hits the same position below the batch
-    int first = 64;
-    for (uint64_t m = __ballot(low); m;) {
-      const int a = __ffsll((unsigned long long)m) - 1;
-      const int ja = __builtin_amdgcn_readlane(j, a);
-      const bool same = low && j == ja;
-      if (same) first = a;
-      m &= ~__ballot(same);
+    // the first lane whose draw hits the same position below the batch: the
+    // lanes holding the same j find each other with one ballot per bit of j
+    // (j < qmin), each lane narrowing its own mask on the vector unit (a scan
+    // over the ballot took a scalar round per distinct j, ~64 per batch)
+    uint64_t same = __ballot(low);
+    for (int k = 32 - __clz(qmin - 1); k-- > 0;) {
+      const bool bk = (j >> k) & 1;
+      const uint64_t m = __ballot(low && bk);
+      same &= bk ? m : ~m;
     }
+    const int first = low ? (int)__builtin_ctzll(same) : 64;
     const bool own = low && first == lane;
     int vb = own ? order[j] : 0;
     const int sj = !vq ? lane : j >= qmin ? qb - j : 64 + first;  // slot of position j
@@ -459,19 +462,28 @@ __device__ __forceinline__ void shuffle_global(WaveRng& rng, int np, int32_t* or
   }
 }
 
-// binning reads the shuffled order once with each record's num_tokens packed
-// in (rec | nt << 21; the record reads are random), then every bin pass
-// reads it linearly
+// the order carries each record's num_tokens from its start (rec | nt << 21:
+// the shuffle moves the packed words), so binning never gathers the records'
+// lengths through the shuffled order
 constexpr int PACKED_REC_BITS = 21;
 __device__ __forceinline__ bool order_packable(int np, int max_seq) {
   return np < (1 << PACKED_REC_BITS) && max_seq < (1 << (32 - PACKED_REC_BITS));
 }
-__device__ __forceinline__ void pack_order_nt(int32_t* order, const PairRec* out, int np, int lane) {
-  for (int k = lane; k < np; k += 64) {
-    const int rec = order[k];
-    order[k] = rec | ((int)out[rec].num_tokens << PACKED_REC_BITS);
+// 2 .. 64 bins: a wave counts and places them with one bin per lane
+// (bin_pairs); one bin needs neither, more take the pass per bin
+__device__ __forceinline__ bool bins_by_lane(int nb) { return nb > 1 && nb <= 64; }
+// the rows of a 64-row step that share a bin, from one ballot per bit of the
+// bin id (as bin.hip's peers): `own` the rows in this lane's row's bin b,
+// `mine` the rows in bin == lane
+__device__ __forceinline__ void bin_masks(int b, bool in, int nb, int lane, uint64_t& own, uint64_t& mine) {
+  own = __ballot(in);
+  mine = lane < nb ? own : 0ull;
+  for (int k = 0; (1 << k) < nb; ++k) {
+    const bool bk = (b >> k) & 1;
+    const uint64_t m = __ballot(in && bk);
+    own &= bk ? m : ~m;
+    mine &= ((lane >> k) & 1) ? m : ~m;
   }
-  group_sync();
 }
 
 // smallest k in [k0, n) with (k == n-1) or (sum lens[k0..k] >= target);
@@ -542,14 +554,37 @@ __device__ __forceinline__ PartOpen open_part(const PackParams& P, int64_t p) {
 }
 
 // random.shuffle(partition_pairs) over the identity order of np records: in
-// LDS (D.order) when LDSOK and they fit, else in P.order
+// LDS (D.order) when LDSOK and they fit, else in P.order, each word with its
+// record's num_tokens packed in where that fits.  Binning's count pass rides
+// on the same read of the records (the counts do not depend on the order):
+// bin_count[p * nb + b] is final here, bin_pairs takes each bin's first
+// position from it.
 template <bool LDSOK>
 __device__ __forceinline__ void shuffle_pairs(const PackParams& P, const PartOpen& O, const PackDyn& D, WaveRng& rng,
-                                              int np, int lane) {
+                                              int64_t p, int np, int lane) {
   const bool ores = LDSOK && np <= P.cap_pairs;
+  const bool packed = !ores && order_packable(np, P.max_seq);
+  const int nb = P.nbins;
+  const bool by_lane = bins_by_lane(nb);
+  const PairRec* out = P.pairs + O.pb;
   int32_t* gorder = P.order + O.pb;
-  if (ores) for (int k = lane; k < np; k += 64) D.order[k] = (uint16_t)k;
-  else for (int k = lane; k < np; k += 64) gorder[k] = k;
+  group_sync();  // (the records, written by other lanes)
+  int cnt = 0;
+  for (int k = 0; k < np; k += 64) {
+    const int kk = k + lane;
+    const bool in = kk < np;
+    const int nt = in ? (int)out[kk].num_tokens : 1;
+    if (in) {
+      if (ores) D.order[kk] = (uint16_t)kk;
+      else gorder[kk] = packed ? kk | (nt << PACKED_REC_BITS) : kk;
+    }
+    if (by_lane) {
+      uint64_t own, mine;
+      bin_masks(bin_of(nt, P.bin_size, nb), in, nb, lane, own, mine);
+      cnt += __popcll(mine);
+    }
+  }
+  if (by_lane && lane < nb) P.bin_count[p * nb + lane] = cnt;
   group_sync();
   if (ores) {
     // lane 0 alone touches the order array here (program order suffices)
@@ -564,7 +599,19 @@ __device__ __forceinline__ void shuffle_pairs(const PackParams& P, const PartOpe
 }
 
 // stable bin partition of the shuffled order + token offsets (MASK: and the
-// masked-entry offsets), then the partition's totals
+// masked-entry offsets), then the partition's totals.  2 .. 64 bins, two
+// passes over the order whatever the bin count:
+//   scatter  64 rows per step in order: a row's rank among the step's rows of
+//            its bin from the bin-id ballots, the bin's next free position
+//            from `seen` (lane = bin; it starts at the bin's first position,
+//            the exclusive scan of shuffle_pairs' counts), read with one
+//            ds_bpermute; binned[seen[b] + rank] = the order's word, its
+//            num_tokens still packed in
+//   offsets  one linear pass over binned: a wave scan of num_tokens per 64
+//            rows gives tok_local (MASK: a second one over mref >> 48 gives
+//            mloc), and the packed words are cut down to the record index
+// One bin is the offsets pass alone, over the order; more than 64 bins take
+// one filtering pass per bin.
 template <int MASK, bool LDSOK>
 __device__ __forceinline__ void bin_pairs(const PackParams& P, const PartOpen& O, const PackDyn& D, int64_t p, int np,
                                           int lane) {
@@ -573,45 +620,85 @@ __device__ __forceinline__ void bin_pairs(const PackParams& P, const PartOpen& O
   int32_t* gorder = P.order + pb;
   const bool ores = LDSOK && np <= P.cap_pairs;
   const bool packed = !ores && order_packable(np, P.max_seq);
-  if (packed) pack_order_nt(gorder, out, np, lane);
-  auto ord_at = [&](int k) -> int { return ores ? (int)D.order[k] : packed ? gorder[k] & ((1 << PACKED_REC_BITS) - 1) : gorder[k]; };
-  auto ntk_at = [&](int k, int rec) -> int {
-    return ores ? (int)D.ntk[rec] : packed ? (int)((uint32_t)gorder[k] >> PACKED_REC_BITS) : (int)out[rec].num_tokens;
+  constexpr int REC_MASK = (1 << PACKED_REC_BITS) - 1;
+  // (word: an entry of the order; packed, its record's num_tokens rides in the high bits)
+  auto word_at = [&](int k) -> int { return ores ? (int)D.order[k] : gorder[k]; };
+  auto rec_of = [&](int w) -> int { return packed ? w & REC_MASK : w; };
+  auto ntk_of = [&](int w) -> int {
+    return packed ? (int)((uint32_t)w >> PACKED_REC_BITS) : ores ? (int)D.ntk[w] : (int)out[w].num_tokens;
   };
   const int nb = P.nbins;
   int32_t* binned = P.binned + pb;
   int64_t* tl = P.tok_local + pb;
-  int pos = 0;
   int64_t acc = 0, macc = 0;
-  for (int b = 0; b < nb; ++b) {
-    int cnt = 0;
+  if (bins_by_lane(nb)) {
+    const int cnt = lane < nb ? (int)P.bin_count[p * nb + lane] : 0;
+    int seen = wave_incl_add(cnt) - cnt;
     for (int k = 0; k < np; k += 64) {
       const int kk = k + lane;
-      int rec = 0, nt = 0;
-      bool in = false;
-      if (kk < np) {
-        rec = ord_at(kk);
-        nt = ntk_at(kk, rec);
-        in = bin_of(nt, P.bin_size, nb) == b;
-      }
-      const uint64_t m = __ballot(in);
-      const int before = __popcll(m & ((1ull << lane) - 1ull));
-      const int tinc = wave_incl_add(in ? nt : 0);
+      const bool in = kk < np;
+      const int w = in ? word_at(kk) : 0;
+      const int nt = in ? ntk_of(w) : 1;
+      const int b = bin_of(nt, P.bin_size, nb);
+      uint64_t own, mine;
+      bin_masks(b, in, nb, lane, own, mine);
+      const int at = __shfl(seen, b);
+      if (in) binned[at + bits_below(own)] = w;
+      seen += __popcll(mine);
+    }
+    group_sync();
+    for (int k = 0; k < np; k += 64) {
+      const int kk = k + lane;
+      const bool in = kk < np;
+      const int w = in ? binned[kk] : 0;
+      const int rec = rec_of(w);
+      const int nt = in ? ntk_of(w) : 0;
+      const int tinc = wave_incl_add(nt);
       if (in) {
-        binned[pos + before] = rec;
-        tl[pos + before] = acc + tinc - nt;
+        if (packed) binned[kk] = rec;
+        tl[kk] = acc + tinc - nt;
       }
       if constexpr (MASK) {
         const int nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
         const int minc = wave_incl_add(nmk);
-        if (in) P.mloc[pb + pos + before] = macc + minc - nmk;
+        if (in) P.mloc[pb + kk] = macc + minc - nmk;
         macc += lane_get(minc, 63);
       }
-      pos += __popcll(m);
-      cnt += __popcll(m);
       acc += lane_get(tinc, 63);
     }
-    if (lane == 0) P.bin_count[p * nb + b] = cnt;
+  } else {
+    int pos = 0;
+    for (int b = 0; b < nb; ++b) {
+      int cnt = 0;
+      for (int k = 0; k < np; k += 64) {
+        const int kk = k + lane;
+        int rec = 0, nt = 0;
+        bool in = false;
+        if (kk < np) {
+          const int w = word_at(kk);
+          rec = rec_of(w);
+          nt = ntk_of(w);
+          in = nb == 1 || bin_of(nt, P.bin_size, nb) == b;
+        }
+        const uint64_t m = __ballot(in);
+        const int before = bits_below(m);
+        const int tinc = wave_incl_add(in ? nt : 0);
+        if (in) {
+          binned[pos + before] = rec;
+          tl[pos + before] = acc + tinc - nt;
+        }
+        if constexpr (MASK) {
+          const int nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
+          const int minc = wave_incl_add(nmk);
+          if (in) P.mloc[pb + pos + before] = macc + minc - nmk;
+          macc += lane_get(minc, 63);
+        }
+        pos += __popcll(m);
+        cnt += __popcll(m);
+        acc += lane_get(tinc, 63);
+      }
+      if (lane == 0) P.bin_count[p * nb + b] = cnt;
+    }
   }
   if (lane == 0) {
     P.part_npairs[p] = np;
@@ -1190,7 +1277,7 @@ __global__ __launch_bounds__(64, PACK_OCC) void pack_bert_wave_kernel(PackParams
     return;
   }
   wave_sync();
-  shuffle_pairs<LDSOK>(P, O, D, rng, np, lane);
+  shuffle_pairs<LDSOK>(P, O, D, rng, p, np, lane);
   PW_STAMP(4)
   bin_pairs<MASK, LDSOK>(P, O, D, p, np, lane);
   PW_STAMP(5)
@@ -1426,7 +1513,7 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
   }
   group_sync();
   // random.shuffle(partition_pairs) (:476) and the binning: the BERT packer's, arrays in global memory
-  shuffle_pairs<false>(P, O, PackDyn{}, rng, np, lane);
+  shuffle_pairs<false>(P, O, PackDyn{}, rng, p, np, lane);
   bin_pairs<0, false>(P, O, PackDyn{}, p, np, lane);
 }
 

@@ -108,18 +108,10 @@ def aggregate(corpus_on_device, part_doc_off=None, target_seq_length=128, tokeni
                     nsent[:nc], ntok[:nc], coff, pco)
 
 
-def _file_batches(part_chunk_off, max_parts, batch_rows):
-  """runs of whole partitions of about batch_rows chunks: (p0, p1) pairs"""
-  n_part = len(part_chunk_off) - 1
-  if max_parts is not None:
-    n_part = min(n_part, max_parts)
-  p = 0
-  while p < n_part:
-    q = p + 1
-    while q < n_part and part_chunk_off[q + 1] - part_chunk_off[p] <= batch_rows:
-      q += 1
-    yield p, q
-    p = q
+def _plan(result, max_parts, part_base):
+  """writer.FilePlan of a BartResult: a partition is one file of its chunks"""
+  from .writer import FilePlan
+  return FilePlan(np.diff(result.part_chunk_off)[:, None], False, max_parts, part_base)
 
 
 def write_bart_shards(result, out_dir, part_base=0, compression='snappy', batch_rows=1 << 16, max_parts=None,
@@ -128,36 +120,28 @@ def write_bart_shards(result, out_dir, part_base=0, compression='snappy', batch_
   result becomes ``part.{part_base + p}.parquet`` with the one string column
   ``sentences``; every partition's file is created, empty ones included.
   executor / pending as writer.write_shards: a writer.ProcessEncoder or a
-  thread pool takes the encodes and their futures go to `pending`; without
-  one the files are written before the call returns.  Returns the files."""
-  import concurrent.futures
+  thread pool takes the encodes and their futures go to `pending` (an
+  executor without that list is a ValueError); without one the files are
+  written before the call returns.  Returns the files."""
   import pyarrow.parquet as pq
   from . import writer
+  sink = writer.EncodeSink(executor, pending)
   os.makedirs(out_dir, exist_ok=True)
-  pco = result.part_chunk_off
-  own = executor is None
-  proc = isinstance(executor, writer.ProcessEncoder)
-  pool = concurrent.futures.ThreadPoolExecutor(writer.encode_workers()) if own else executor
-  files, mine = [], []
-  for p0, p1 in _file_batches(pco, max_parts, batch_rows):
-    c0, n = int(pco[p0]), int(pco[p1] - pco[p0])
-    flist = [(os.path.join(out_dir, 'part.%d.parquet' % (part_base + p)), int(pco[p] - c0), int(pco[p + 1] - c0))
-             for p in range(p0, p1)]
-    if proc:
-      off, data = result.render(c0, n, stream, host=False)
-      mine.extend(executor.submit_batch(n, [('sentences', 'str', off, data)], SCHEMA, flist, compression, [], stream))
+  plan = _plan(result, max_parts, part_base)
+  files = []
+  for f, g, c0, c1 in plan.batches(batch_rows):
+    n = c1 - c0
+    flist = plan.files(f, g, out_dir, 'parquet')
+    off, data = result.render(c0, n, stream, host=not sink.proc)
+    if sink.proc:
+      sink.futs.extend(executor.submit_batch(n, [('sentences', 'str', off, data)], SCHEMA, flist, compression, [],
+                                             stream))
     else:
-      off, data = result.render(c0, n, stream)
       for path, lo, hi in flist:
         t = pa.Table.from_arrays([writer._arrow(pa.string(), off, data, lo, hi)], schema=SCHEMA)
-        mine.append(pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=False))
-    files.extend(f[0] for f in flist)
-  if own:
-    for fu in mine:
-      fu.result()
-    pool.shutdown()
-  elif pending is not None:
-    pending.extend(mine)
+        sink.futs.append(sink.pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=False))
+    files.extend(f_[0] for f_ in flist)
+  sink.close()
   return files
 
 
@@ -167,15 +151,12 @@ def write_bart_txt(result, out_dir, part_base=0, batch_rows=1 << 20, max_parts=N
   to_textfiles, the convention writer.write_txt documents).  Every
   partition's file is created.  Returns the files."""
   os.makedirs(out_dir, exist_ok=True)
-  pco = result.part_chunk_off
+  plan = _plan(result, max_parts, part_base)
   files = []
-  for p0, p1 in _file_batches(pco, max_parts, batch_rows):
-    c0, n = int(pco[p0]), int(pco[p1] - pco[p0])
-    off, data = result.render(c0, n, stream)
+  for f, g, c0, c1 in plan.batches(batch_rows):
+    off, data = result.render(c0, c1 - c0, stream)
     raw = data.tobytes()
-    for p in range(p0, p1):
-      lo, hi = int(pco[p] - c0), int(pco[p + 1] - c0)
-      path = os.path.join(out_dir, '%d.txt' % (part_base + p))
+    for path, lo, hi in plan.files(f, g, out_dir, 'txt'):
       with open(path, 'wb') as fh:
         fh.write(b'\n'.join(raw[off[i]:off[i + 1]] for i in range(lo, hi)))
       files.append(path)

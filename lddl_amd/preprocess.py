@@ -63,8 +63,10 @@ chunk whose marker carries the same key and whose files all exist; chunk
 seed + p), so a restart may use another rank count.
 """
 import argparse
+import concurrent.futures
 import hashlib
 import json
+import multiprocessing
 import os
 import re
 import sys
@@ -73,6 +75,7 @@ import time
 import numpy as np
 
 from . import synth
+from .hostinfo import cpu_share
 
 
 # ----------------------------------------------------------------- input --
@@ -389,15 +392,21 @@ def _split_warm(_):
   return os.getpid()
 
 
-def _split_worker(a, b):
+def _split_piece(fe, a, b):
+  """records [a, b) of the order, split: (corpus, doc ids, seconds); fe: the
+  state the split workers inherit through _FE"""
   ts = time.perf_counter()
-  corpus, ids = split_chunk(_FE['index'], _FE['order'][a:b], _FE['codebert'], _FE['split'], _FE.get('bart', False))
-  if _FE.get('bart', False):  # (BART keeps the id in the text: no id list travels back to the parent)
+  corpus, ids = split_chunk(fe['index'], fe['order'][a:b], fe['codebert'], fe['split'], fe.get('bart', False))
+  if fe.get('bart', False):  # (BART keeps the id in the text: no id list travels back to the parent)
     ids = None
-  elif _FE['codebert']:  # the writer's id column, built here in the worker, off the writer's path
+  elif fe['codebert']:  # the writer's id column, built here in the worker, off the writer's path
     from .writer import str_array
     ids = str_array(ids)
   return corpus, ids, time.perf_counter() - ts
+
+
+def _split_worker(a, b):
+  return _split_piece(_FE, a, b)
 
 
 def chunk_pieces(part_end, lo, a, b, n):
@@ -441,6 +450,178 @@ def concat_ids(ids):
     return [x for i in ids for x in i]
   import pyarrow as pa
   return pa.concat_arrays(ids)
+
+
+def chunk_plan(pro, sizes, rank, world, chunk_bytes):
+  """(lo, hi, part_end, chunks) of rank `rank` of `world`: its contiguous
+  partition range, part_end[p - lo] = its bytes up to the end of partition p,
+  and its pipeline chunks (a, b): runs of whole partitions, each closed by the
+  first partition that brings it to chunk_bytes (the last takes the rest).
+  pro: partition offsets into the record order; sizes: the records' bytes."""
+  n_part = len(pro) - 1
+  lo, hi = rank * n_part // world, (rank + 1) * n_part // world
+  cum = np.concatenate([[0], np.cumsum(sizes[pro[lo]:pro[hi]])])
+  part_end = cum[pro[lo + 1:hi + 1] - pro[lo]]
+  bounds, acc0 = [lo], 0
+  for p in range(lo, hi):
+    if part_end[p - lo] - acc0 >= chunk_bytes and p + 1 < hi:
+      bounds.append(p + 1)
+      acc0 = part_end[p - lo]
+  bounds.append(hi)
+  return lo, hi, part_end, [(a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+
+
+class Workers:
+  """The host workers of one CLI run, as a context manager: the parquet
+  encoder (`encoder`: 'procs', a writer.ProcessEncoder; 'threads'; None) and
+  nw forked processes that split sentences ahead of the GPU.  Enter it before
+  the process touches the GPU: the split workers read their records from the
+  index (integers only are inherited) and never see a GPU context.  However
+  the block is left, a failed start included, the split pool ends, then the
+  encoder, and the index closes; t takes the start and teardown seconds.
+  early_exit: split_ahead may end the split workers once every split is in.
+  fe: more state for them (bart=True)."""
+
+  def __init__(self, t, index, order, codebert, split, nw, encoder, early_exit=False, **fe):
+    self.t, self.index, self.nw, self.encoder, self.early_exit = t, index, nw, encoder, early_exit
+    self.fe = dict(index=index, order=order, codebert=codebert, split=split, **fe)
+    self.enc = self.pool = None
+
+  def __enter__(self):
+    from . import writer
+    try:
+      # the encoder forks first, for the CPU share: started beside 16 busy
+      # split workers its pool took 0.17-0.29 s to come up, here 0.15 s
+      # (profiles/r5_cli_encstart.txt).  The split pool is then forked beside
+      # the encoder's executor threads.
+      t0 = time.perf_counter()
+      if self.encoder == 'procs':
+        self.enc = writer.ProcessEncoder()
+      elif self.encoder == 'threads':
+        self.enc = concurrent.futures.ThreadPoolExecutor(writer.encode_workers())
+      self.t['enc_start_s'] = time.perf_counter() - t0
+      if self.nw > 0:
+        t0 = time.perf_counter()
+        # (niced: the CPU share is shared with this process, whose thread drives
+        # the GPU and the writer; LDDL_WORKER_NICE=0 keeps the default priority.
+        # An executor, not multiprocessing.Pool: the Pool's handler threads poll
+        # at 0.1 s, and its terminate / join took 0.12-0.25 s at the end)
+        self.pool = concurrent.futures.ProcessPoolExecutor(self.nw, mp_context=multiprocessing.get_context('fork'),
+                                                           initializer=_nice_worker)
+        self._warm()
+        self.t['pool_start_s'] = time.perf_counter() - t0
+    except BaseException:
+      self.close()
+      raise
+    return self
+
+  def _warm(self):
+    """the first task forks every worker, while _FE holds their state"""
+    _FE.update(self.fe)
+    try:
+      list(self.pool.map(_split_warm, range(self.nw)))
+    finally:
+      _FE.clear()
+
+  def __exit__(self, *exc):
+    self.close()
+
+  def close(self):
+    t0 = time.perf_counter()
+    try:
+      if self.pool is not None:
+        self.pool.shutdown(wait=True, cancel_futures=True)
+      self.t['teardown_split_s'] = time.perf_counter() - t0
+    finally:
+      try:
+        if self.enc is not None:
+          self.enc.close() if self.encoder == 'procs' else self.enc.shutdown(wait=True)
+      finally:
+        self.index.close()
+        self.t['teardown_s'] = time.perf_counter() - t0
+    if getattr(self.enc, 'close_s', None):  # (absent when close() raised: that error propagates)
+      self.t['teardown_enc_exit_s'], self.t['teardown_enc_unpin_s'], self.t['teardown_enc_rm_s'] = self.enc.close_s
+
+  def submit(self, pro, pieces):
+    """futures of (corpus, doc ids, seconds), one per partition run of
+    `pieces` on the pool, or without one a single finished one for them all"""
+    if self.pool is not None:
+      return [self.pool.submit(_split_worker, int(pro[a]), int(pro[b])) for a, b in pieces]
+    f = concurrent.futures.Future()
+    f.set_result(_split_piece(self.fe, int(pro[pieces[0][0]]), int(pro[pieces[-1][1]])))
+    return [f]
+
+
+def split_ahead(ws, pro, part_end, lo, chunks, todo, ahead=2):
+  """A generator of (c, a, b, corpora, ids, split_seconds, wait_seconds) per
+  chunk c = partitions [a, b) of `todo` (indices into chunks), in order;
+  corpora: its pieces (pipeline.upload_pieces stages them without a host
+  concat), ids: their doc ids as one list / Arrow array (None for BART).  With
+  a pool the first `ahead` chunks are submitted by this call, so they split
+  while the caller brings up the GPU, and the chunks up to k + ahead while
+  chunk k is consumed.  A chunk is split as pieces of ~1/(2 nw) of it (whole
+  partitions) on all the workers at once: the GPU packs its partitions in
+  parallel, so it wants many, while its split should not wait on one worker."""
+  futs = {}
+  if ws.pool is not None:
+    for c in todo[:ahead]:
+      futs[c] = ws.submit(pro, chunk_pieces(part_end, lo, *chunks[c], 2 * ws.nw))
+  return _split_consume(ws, pro, part_end, lo, chunks, todo, ahead, futs)
+
+
+def _split_consume(ws, pro, part_end, lo, chunks, todo, ahead, futs):
+  n = 2 * ws.nw if ws.pool is not None else 1
+  for i, c in enumerate(todo):
+    a, b = chunks[c]
+    tw = time.perf_counter()
+    got = [f.result() for f in (futs.pop(c) if c in futs else ws.submit(pro, chunk_pieces(part_end, lo, a, b, n)))]
+    ids = None if got[0][1] is None else concat_ids([g[1] for g in got])
+    wait = time.perf_counter() - tw
+    if ws.pool is not None and i + ahead < len(todo):
+      k = todo[i + ahead]
+      futs[k] = ws.submit(pro, chunk_pieces(part_end, lo, *chunks[k], n))
+    elif ws.pool is not None and not futs and ws.early_exit:
+      # every split is in: the workers exit (0.2-0.4 s after a C2-size run)
+      # beside the last chunks' GPU work and writes (close() does not wait for them)
+      ws.pool.shutdown(wait=False)
+    yield c, a, b, [g[0] for g in got], ids, sum(g[2] for g in got), wait
+
+
+class Settler:
+  """The chunks whose parquet encodes still run, oldest first: chunk k's run
+  while chunk k + 1 splits, uploads and packs, and its --resume marker is
+  saved once all of its files are encoded (in chunk order).  Left by an
+  exception, the block still saves the markers of the chunks whose files all
+  get written."""
+
+  def __init__(self, sink, key, resume, t):
+    self.sink, self.key, self.resume, self.t = sink, key, resume, t
+    self.inflight = []  # (a, b, files, futures, counts, n_pairs) per chunk
+    t['write_wait_s'] = 0.0
+
+  def __enter__(self):
+    return self
+
+  def __exit__(self, et, ev, tb):
+    if et is not None:
+      try:
+        self.settle(0)
+      except Exception:  # (an encode failed too: no marker for its chunk, nor for the later ones)
+        pass
+
+  def settle(self, keep):
+    """finish the oldest chunks: those whose encodes are done, and while more
+    than `keep` chunks are in flight, the oldest one (waiting for it)"""
+    while self.inflight:
+      if len(self.inflight) <= keep and not all(f.done() for f in self.inflight[0][3]):
+        break
+      a, b, files, futs, counts, n_pairs = self.inflight.pop(0)
+      tw = time.perf_counter()
+      for f in futs:
+        f.result()
+      self.t['write_wait_s'] += time.perf_counter() - tw
+      if self.resume:
+        save_marker(self.sink, a, b, self.key, files, counts, n_pairs)
 
 
 def input_files(args, codebert=False):
@@ -505,259 +686,154 @@ def _dist_init(world):
   return dist.new_group(backend='gloo')
 
 
+def _ranks():
+  """(rank, world, local rank) of a torch.distributed.run launch"""
+  return int(os.environ.get('RANK', 0)), int(os.environ.get('WORLD_SIZE', 1)), int(os.environ.get('LOCAL_RANK', 0))
+
+
+def _encoder(args, threads):
+  """Workers' `encoder`: None for txt, forked processes, or with
+  LDDL_ENCODE_PROCS=0 a thread pool (`threads`) or the writer's own (None)"""
+  if args.output_format == 'txt':
+    return None
+  if os.environ.get('LDDL_ENCODE_PROCS', '1') != '0':
+    return 'procs'
+  return 'threads' if threads else None
+
+
+def resumed_chunks(args, codebert, vocab, how, n_part, sink, chunks, nbins):
+  """--resume: (run key, {chunk index: marker} of the chunks an earlier run
+  with this key completed); without the flag (None, {})"""
+  if not args.resume:
+    return None, {}
+  key = run_key(args, codebert, input_files(args, codebert)[0], vocab, how, n_part)
+  done = {}
+  for c, (a, b) in enumerate(chunks):
+    m = load_marker(sink, a, b, key)
+    if m is not None and np.asarray(m['counts']).shape == (b - a, nbins):
+      done[c] = m
+  return key, done
+
+
+def balance_stage(args, counts, lo, sink, rank, world, gloo):
+  """--num-shards: balance_dask_output's job (load_balance.py:321-369) from
+  the packer's counts: one all-gather (RCCL) instead of its per-file count
+  pass + MPI Allreduce (:222-233); the plan is the same on every rank; shard k
+  is written by rank k % world from slices of the part files.  Returns the
+  shard files this rank wrote."""
+  from . import balance
+  if world > 1:
+    import torch.distributed as dist
+    allc = balance.gather_bin_counts(counts if dist.get_backend() == 'nccl' else counts.cpu(), lo)
+  else:
+    allc = counts.cpu().numpy()
+  shards, ns = balance.balance_counts(allc, args.num_shards, args.bin_size is not None, outdir=sink)
+  written = balance.write_shards(shards, sink, rank, world)
+  if world > 1:
+    dist.barrier(group=gloo)
+  if rank == 0:
+    balance.store_num_samples(ns, sink)
+    if not args.keep_orig:
+      for p in out_all_parts(sink, *allc.shape, args.bin_size is not None):
+        if os.path.exists(p):
+          os.remove(p)
+      if args.resume:  # the markers name the part files just removed
+        import shutil
+        shutil.rmtree(os.path.join(sink, DONE_DIR), ignore_errors=True)
+  return written
+
+
 def main(args, codebert=False):
   """Returns (files written by this rank, timings dict)."""
   import torch
-  from . import pipeline, writer, balance
+  from . import pipeline, writer
   _check(args)
-  rank = int(os.environ.get('RANK', 0))
-  world = int(os.environ.get('WORLD_SIZE', 1))
-  local = int(os.environ.get('LOCAL_RANK', 0))
+  rank, world, local = _ranks()
   vocab = args.vocab_file or (pipeline.VOCAB_CODEBERT if codebert else pipeline.VOCAB_BERT)
   if not os.path.isfile(vocab):
     raise ValueError('--vocab-file must be a local vocab.txt (no hub access): %s' % vocab)
+  masking = args.masking and not codebert
   t = {}
   wall0 = t0 = time.perf_counter()
   gloo = _dist_init(world)
   split, how = (None, 'code-lines') if codebert else sentence_splitter(args.sentence_splitter)
   index, order, pro = plan_input(args, codebert, rank, world, gloo)
   n_part = len(pro) - 1
-  lo, hi = rank * n_part // world, (rank + 1) * n_part // world
   t['host_read_s'] = time.perf_counter() - t0
   # chunks of this rank's partitions, ~--chunk-mb raw MB each
-  sizes = index.len[order[pro[lo]:pro[hi]]]
-  cum = np.concatenate([[0], np.cumsum(sizes)])
-  part_end = cum[pro[lo + 1:hi + 1] - pro[lo]]
-  chunk_b = max(1, int(args.chunk_mb * (1 << 20)))
-  bounds = [lo]
-  acc0 = 0
-  for p in range(lo, hi):
-    if part_end[p - lo] - acc0 >= chunk_b and p + 1 < hi:
-      bounds.append(p + 1)
-      acc0 = part_end[p - lo]
-  bounds.append(hi)
-  chunks = [(a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+  lo, hi, part_end, chunks = chunk_plan(pro, index.len[order], rank, world, max(1, int(args.chunk_mb * (1 << 20))))
   sink = os.path.abspath(os.path.expanduser(args.sink))
   nbins = args.target_seq_length // args.bin_size if args.bin_size else 1
-  done, key = {}, None
-  if args.resume:
-    key = run_key(args, codebert, input_files(args, codebert)[0], vocab, how, n_part)
-    for c, (a, b) in enumerate(chunks):
-      m = load_marker(sink, a, b, key)
-      if m is not None and np.asarray(m['counts']).shape == (b - a, nbins):
-        done[c] = m
+  key, done = resumed_chunks(args, codebert, vocab, how, n_part, sink, chunks, nbins)
   todo = [c for c in range(len(chunks)) if c not in done]
-
-  # the parquet encodes: a pool of processes forked first, before the GPU is
-  # touched and before the split pool exists (a process forked beside a live
-  # executor's threads can inherit their locks held; 16 forks beside 16 busy
-  # split workers had also taken 0.17-0.29 s of the CPU share;
-  # writer.ProcessEncoder; LDDL_ENCODE_PROCS=0: a thread pool)
-  import concurrent.futures
-  enc = None
-  t0 = time.perf_counter()
-  if args.output_format != 'txt':
-    if os.environ.get('LDDL_ENCODE_PROCS', '1') != '0':
-      enc = writer.ProcessEncoder()
-    else:
-      enc = concurrent.futures.ThreadPoolExecutor(writer.encode_workers())
-  t['enc_start_s'] = time.perf_counter() - t0
-
-  def close_enc():
-    if enc is not None:
-      enc.close() if isinstance(enc, writer.ProcessEncoder) else enc.shutdown(wait=False)
-
-  # split workers: forked here, before anything touches the GPU; they read
-  # their records from the index (integers only are inherited)
-  sw = args.split_workers
-  if sw is None:  # the host CPU share: affinity capped at LDDL_CPU_SHARE / 16 (hostinfo.cpu_share)
-    from .hostinfo import cpu_share
-    sw = cpu_share()
+  # (default: the host CPU share, affinity capped at LDDL_CPU_SHARE / 16: hostinfo.cpu_share)
+  sw = cpu_share() if args.split_workers is None else args.split_workers
   # (a chunk's pieces are whole partitions: no more workers than partitions to split)
   n_todo = sum(chunks[c][1] - chunks[c][0] for c in todo)
   nw = min(max(0, sw), n_todo) if n_todo > 1 else 0
-  pool = None
   if not codebert and split is _rule_split:
     from . import splitnative
     if splitnative.available():
       splitnative.props_table()  # (loaded here once; the forked workers share it)
-  if nw > 0:
-    import concurrent.futures
-    import multiprocessing
-    _FE.update(index=index, order=order, codebert=codebert, split=split)
+  with Workers(t, index, order, codebert, split, nw, _encoder(args, True),
+               early_exit=os.environ.get('LDDL_SPLIT_EARLY_EXIT', '1') != '0') as ws:
+    # the first chunks split while this process brings up the GPU context and
+    # the device tables
+    splits = split_ahead(ws, pro, part_end, lo, chunks, todo)
     t0 = time.perf_counter()
-    # (niced: the CPU share is shared with this process, whose thread drives
-    # the GPU and the writer; LDDL_WORKER_NICE=0 keeps the default priority.
-    # An executor, not multiprocessing.Pool: the Pool's handler threads poll
-    # at 0.1 s, and its terminate / join took 0.12-0.25 s at the end)
-    try:
-      pool = concurrent.futures.ProcessPoolExecutor(nw, mp_context=multiprocessing.get_context('fork'),
-                                                    initializer=_nice_worker)
-      try:
-        list(pool.map(_split_warm, range(nw)))  # (the first task forks every worker, while _FE holds the state)
-      finally:
-        _FE.clear()
-    except BaseException:
-      if pool is not None:
-        pool.shutdown(wait=True, cancel_futures=True)
-      close_enc()
-      raise
-    t['pool_start_s'] = time.perf_counter() - t0
-
-  # a chunk is split as pieces of ~1/(2 nw) of it (whole partitions) on all
-  # the workers at once: the GPU packs a chunk's partitions in parallel, one
-  # wave each, so a chunk costs about one partition's latency and wants many
-  # partitions, while its split should not wait on one worker
-  def pieces(c):
-    a, b = chunks[c]
-    return chunk_pieces(part_end, lo, a, b, 2 * nw if pool is not None else 1)
-
-  def submit(c):
-    if pool is not None:
-      return [pool.submit(_split_worker, int(pro[a]), int(pro[b])) for a, b in pieces(c)]
-    ts = time.perf_counter()
-    a, b = chunks[c]
-    corpus, ids = split_chunk(index, order[int(pro[a]):int(pro[b])], codebert, split)
-
-    class Done:
-      def result(self):
-        return corpus, ids, time.perf_counter() - ts
-    return [Done()]
-
-  def gather(fs):
-    """the pieces of a chunk, in order: (corpora, doc ids, split seconds);
-    pipeline.upload_pieces stages them for the GPU without a host concat"""
-    got = [f_.result() for f_ in fs]
-    return [g[0] for g in got], concat_ids([g[1] for g in got]), sum(g[2] for g in got)
-
-  # the first chunks split while this process brings up the GPU context and
-  # the device tables
-  ahead = 2  # chunks split ahead of the GPU
-  futs = {c: submit(c) for c in todo[:ahead]} if pool is not None else {}
-  t0 = time.perf_counter()
-  device = torch.device('cuda', local)
-  try:
+    device = torch.device('cuda', local)
     torch.cuda.set_device(device)
-    pk = pipeline.Packer(vocab, local, masking=args.masking and not codebert)
-  except BaseException:
-    if pool is not None:
-      pool.shutdown(wait=True, cancel_futures=True)
-    close_enc()
-    raise
-  t['gpu_init_s'] = time.perf_counter() - t0
-  out = []
-  counts = torch.zeros(hi - lo, nbins, dtype=torch.int64, device=device)  # rows per (partition, bin)
-  t.update(host_split_s=0.0, split_wait_s=0.0, gpu_s=0.0, write_s=0.0, pairs=0, split_workers=nw,
-           chunks_skipped=len(done))
-  for c, m in done.items():
-    a, b = chunks[c]
-    counts[a - lo:b - lo] = torch.tensor(m['counts'], dtype=torch.int64)
-    out += [os.path.join(sink, f) for f in m['files']]
-    t['pairs'] += m['n_pairs']
-  # parquet encodes of chunk k run on this pool while chunk k+1 splits,
-  # uploads, tokenizes and packs; a chunk's --resume marker is saved once
-  # all of its files are encoded (in chunk order)
-  inflight = []  # (a, b, files, futures, counts, n_pairs) per chunk, oldest first
-
-  def settle(keep):
-    """finish the oldest chunks: those whose encodes are done, and while more
-    than `keep` chunks are in flight, the oldest one (waiting for it)"""
-    while inflight:
-      if len(inflight) <= keep and not all(f_.done() for f_ in inflight[0][3]):
-        break
-      a_, b_, files_, futs_, cnt_, np_ = inflight.pop(0)
-      tw_ = time.perf_counter()
-      for f_ in futs_:
-        f_.result()
-      t['write_wait_s'] += time.perf_counter() - tw_
-      if args.resume:
-        save_marker(sink, a_, b_, key, files_, cnt_, np_)
-
-  t['write_wait_s'] = 0.0
-  try:
-    for i, c in enumerate(todo):
+    pk = pipeline.Packer(vocab, local, masking=masking)
+    t['gpu_init_s'] = time.perf_counter() - t0
+    out = []
+    counts = torch.zeros(hi - lo, nbins, dtype=torch.int64, device=device)  # rows per (partition, bin)
+    t.update(host_split_s=0.0, split_wait_s=0.0, gpu_s=0.0, write_s=0.0, pairs=0, split_workers=nw,
+             chunks_skipped=len(done))
+    for c, m in done.items():
       a, b = chunks[c]
-      tw = time.perf_counter()
-      corpus, ids, ts = gather(futs.pop(c) if c in futs else submit(c))
-      t['split_wait_s'] += time.perf_counter() - tw
-      t['host_split_s'] += ts
-      if pool is not None and i + ahead < len(todo):
-        futs[todo[i + ahead]] = submit(todo[i + ahead])  # overlaps this chunk's GPU work and parquet writes
-      elif pool is not None and not futs and os.environ.get('LDDL_SPLIT_EARLY_EXIT', '1') != '0':
-        # every split is in: the workers exit (0.2-0.4 s after a C2-size
-        # run) beside the last chunks' GPU work and writes
-        pool.shutdown(wait=False)
+      counts[a - lo:b - lo] = torch.tensor(m['counts'], dtype=torch.int64)
+      out += [os.path.join(sink, f) for f in m['files']]
+      t['pairs'] += m['n_pairs']
+    with Settler(sink, key, args.resume, t) as encodes:
+      for c, a, b, corpus, ids, ts, wait in splits:
+        t['split_wait_s'] += wait
+        t['host_split_s'] += ts
+        t0 = time.perf_counter()
+        sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
+        ids_d, ntok, toff = pk.tokenize(sh)
+        # partition p packs after random.seed(args.seed + global p)
+        res = pk.pack(sh, ids_d, ntok, toff, target_seq_length=args.target_seq_length,
+                      short_seq_prob=args.short_seq_prob, duplicate_factor=args.duplicate_factor, seed=args.seed + a,
+                      bin_size=args.bin_size, codebert=codebert, masking=masking,
+                      masked_lm_ratio=args.masked_lm_ratio, spans=True)
+        counts[a - lo:b - lo] = res.bin_count.view(b - a, -1).to(torch.int64)
+        torch.cuda.synchronize()
+        t['gpu_s'] += time.perf_counter() - t0
+        t0 = time.perf_counter()
+        clear_markers(sink, a, b)
+        kw = dict(bin_size=args.bin_size, codebert=codebert, masking=masking, doc_ids=ids, part_base=a)
+        cf = []
+        if ws.enc is None:
+          wrote = writer.write_txt(pk, res, sink, **kw)
+        else:
+          wrote = writer.write_shards(pk, res, sink, executor=ws.enc, pending=cf, **kw)
+          for k_ in ('setup_s', 'render_s', 'table_s'):  # (the writer's stages: table_s = slot copies + hand-off)
+            t['writer_' + k_] = t.get('writer_' + k_, 0.0) + writer.LAST_STATS.get(k_, 0.0)
+        out += wrote
+        encodes.inflight.append((a, b, wrote, cf, counts[a - lo:b - lo].tolist(), res.n_pairs))
+        encodes.settle(2)  # at most two chunks' encodes behind the GPU
+        t['write_s'] += time.perf_counter() - t0
+        t['pairs'] += res.n_pairs
       t0 = time.perf_counter()
-      sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
-      ids_d, ntok, toff = pk.tokenize(sh)
-      # partition p packs after random.seed(args.seed + global p)
-      res = pk.pack(sh, ids_d, ntok, toff, target_seq_length=args.target_seq_length, short_seq_prob=args.short_seq_prob,
-                    duplicate_factor=args.duplicate_factor, seed=args.seed + a, bin_size=args.bin_size,
-                    codebert=codebert, masking=args.masking and not codebert, masked_lm_ratio=args.masked_lm_ratio,
-                    spans=True)
-      counts[a - lo:b - lo] = res.bin_count.view(b - a, -1).to(torch.int64)
-      torch.cuda.synchronize()
-      t['gpu_s'] += time.perf_counter() - t0
-      t0 = time.perf_counter()
-      clear_markers(sink, a, b)
-      kw = dict(bin_size=args.bin_size, codebert=codebert, masking=args.masking and not codebert, doc_ids=ids,
-                part_base=a)
-      cf = []
-      if enc is None:
-        wrote = writer.write_txt(pk, res, sink, **kw)
-      else:
-        wrote = writer.write_shards(pk, res, sink, executor=enc, pending=cf, **kw)
-        for k_ in ('setup_s', 'render_s', 'table_s'):  # (the writer's stages: table_s = slot copies + hand-off)
-          t['writer_' + k_] = t.get('writer_' + k_, 0.0) + writer.LAST_STATS.get(k_, 0.0)
-      out += wrote
-      inflight.append((a, b, wrote, cf, counts[a - lo:b - lo].tolist(), res.n_pairs))
-      settle(2)  # at most two chunks' encodes behind the GPU
-      t['write_s'] += time.perf_counter() - t0
-      t['pairs'] += res.n_pairs
-    t0 = time.perf_counter()
-    settle(0)
-    t['drain_s'] = time.perf_counter() - t0  # the last chunks' encodes
-    if isinstance(enc, writer.ProcessEncoder):
-      t['enc_slot_wait_s'], t['enc_copy_s'] = enc.wait_s, enc.copy_s
-  finally:
-    t0 = time.perf_counter()
-    if pool is not None:
-      pool.shutdown(wait=True, cancel_futures=True)
-    t['teardown_split_s'] = time.perf_counter() - t0
-    if enc is not None:
-      enc.close() if isinstance(enc, writer.ProcessEncoder) else enc.shutdown(wait=True)
-    index.close()
-    t['teardown_s'] = time.perf_counter() - t0
-    if getattr(enc, 'close_s', None):  # (absent when close() raised: that error propagates)
-      t['teardown_enc_exit_s'], t['teardown_enc_unpin_s'], t['teardown_enc_rm_s'] = enc.close_s
+      encodes.settle(0)
+      t['drain_s'] = time.perf_counter() - t0  # the last chunks' encodes
+    if ws.encoder == 'procs':
+      t['enc_slot_wait_s'], t['enc_copy_s'] = ws.enc.wait_s, ws.enc.copy_s
   if args.num_shards:
-    # balance_dask_output's job (load_balance.py:321-369) from the packer's
-    # counts: one all-gather (RCCL) instead of its per-file count pass + MPI
-    # Allreduce (:222-233); the plan is the same on every rank; shard k is
-    # written by rank k % world from slices of the part files
     t0 = time.perf_counter()
-    if world > 1:
-      import torch.distributed as dist
-      allc = balance.gather_bin_counts(counts if dist.get_backend() == 'nccl' else counts.cpu(), lo)
-    else:
-      allc = counts.cpu().numpy()
-    shards, ns = balance.balance_counts(allc, args.num_shards, args.bin_size is not None, outdir=sink)
-    written = balance.write_shards(shards, sink, rank, world)
-    if world > 1:
-      import torch.distributed as dist
-      dist.barrier(group=gloo)
-    if rank == 0:
-      balance.store_num_samples(ns, sink)
-      if not args.keep_orig:
-        for p in out_all_parts(sink, allc.shape[0], nbins, args.bin_size is not None):
-          if os.path.exists(p):
-            os.remove(p)
-        if args.resume:  # the markers name the part files just removed
-          import shutil
-          shutil.rmtree(os.path.join(sink, DONE_DIR), ignore_errors=True)
+    out = balance_stage(args, counts, lo, sink, rank, world, gloo)
     t['balance_s'] = time.perf_counter() - t0
-    t['shards'] = len(written)
-    out = written
+    t['shards'] = len(out)
   t['wall_s'] = time.perf_counter() - wall0
   # the part of the host split hidden behind the GPU and the writer
   t['host_split_hidden_s'] = max(0.0, t['host_split_s'] - t['split_wait_s'])
@@ -773,12 +849,15 @@ def out_all_parts(sink, n_part, nbins, binned):
   return [os.path.join(sink, 'part.%d.parquet' % p) for p in range(n_part)]
 
 
-def console_script(argv=None, codebert=False):
-  args = attach_args(codebert=codebert).parse_args(argv)
+def _run(fn, *args):
   tic = time.perf_counter()
-  files, t = main(args, codebert)
+  files, t = fn(*args)
   print('rank %d: %d files, %s' % (t['rank'], len(files), {k: v for k, v in t.items() if k != 'rank'}))
   print('Running the pipeline took {} s'.format(time.perf_counter() - tic))
+
+
+def console_script(argv=None, codebert=False):
+  _run(main, attach_args(codebert=codebert).parse_args(argv), codebert)
 
 
 # ----------------------------------------------------------------- BART --
@@ -838,64 +917,23 @@ def bart_main(args):
   GPU: word counts, chunk plan and the `sentences` column (lddl_amd/bart.py).
   Rank r of a torch.distributed.run launch takes the contiguous partition
   range r of world."""
-  import concurrent.futures
-  import multiprocessing
   import torch
-  from . import bart, pipeline, writer
-  from .hostinfo import cpu_share
+  from . import bart, pipeline
   from .tokenizer import Tokenizer
-  rank = int(os.environ.get('RANK', 0))
-  world = int(os.environ.get('WORLD_SIZE', 1))
-  local = int(os.environ.get('LOCAL_RANK', 0))
+  rank, world, local = _ranks()
   t = {}
   wall0 = t0 = time.perf_counter()
   gloo = _dist_init(world)
   split, how = sentence_splitter(args.sentence_splitter)
   index, order, pro = plan_bart_input(args, rank, world, gloo)
   n_part = len(pro) - 1
-  lo, hi = rank * n_part // world, (rank + 1) * n_part // world
   t['host_read_s'] = time.perf_counter() - t0
-  sizes = index.len[order[pro[lo]:pro[hi]]]
-  cum = np.concatenate([[0], np.cumsum(sizes)])
-  part_end = cum[pro[lo + 1:hi + 1] - pro[lo]]
-  bounds, acc0 = [lo], 0
-  for p in range(lo, hi):
-    if part_end[p - lo] - acc0 >= BART_CHUNK_BYTES and p + 1 < hi:
-      bounds.append(p + 1)
-      acc0 = part_end[p - lo]
-  bounds.append(hi)
-  chunks = [(a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+  lo, hi, part_end, chunks = chunk_plan(pro, index.len[order], rank, world, BART_CHUNK_BYTES)
   sink = os.path.abspath(os.path.expanduser(args.sink))
   os.makedirs(sink, exist_ok=True)
-  # the encoder and the split workers fork before the GPU is touched, as in main()
-  enc = writer.ProcessEncoder() if args.output_format != 'txt' and os.environ.get('LDDL_ENCODE_PROCS', '1') != '0' \
-      else None
   nw = min(cpu_share(), hi - lo) if hi - lo > 1 else 0
-  pool = None
-  try:
-    if nw > 0:
-      _FE.update(index=index, order=order, codebert=False, split=split, bart=True)
-      try:
-        pool = concurrent.futures.ProcessPoolExecutor(nw, mp_context=multiprocessing.get_context('fork'),
-                                                      initializer=_nice_worker)
-        list(pool.map(_split_warm, range(nw)))
-      finally:
-        _FE.clear()
-
-    def submit(c):
-      a, b = chunks[c]
-      if pool is not None:
-        return [pool.submit(_split_worker, int(pro[x]), int(pro[y]))
-                for x, y in chunk_pieces(part_end, lo, a, b, 2 * nw)]
-      ts = time.perf_counter()
-      corpus, ids = split_chunk(index, order[int(pro[a]):int(pro[b])], False, split, True)
-
-      class Done:
-        def result(self):
-          return corpus, ids, time.perf_counter() - ts
-      return [Done()]
-
-    futs = {c: submit(c) for c in range(min(2, len(chunks)))} if pool is not None else {}
+  with Workers(t, index, order, False, split, nw, _encoder(args, False), bart=True) as ws:
+    splits = split_ahead(ws, pro, part_end, lo, chunks, range(len(chunks)))
     t0 = time.perf_counter()
     device = torch.device('cuda', local)
     torch.cuda.set_device(device)
@@ -903,15 +941,11 @@ def bart_main(args):
     t['gpu_init_s'] = time.perf_counter() - t0
     t.update(host_split_s=0.0, split_wait_s=0.0, gpu_s=0.0, write_s=0.0, chunks_out=0, split_workers=nw)
     out, pending = [], []
-    for c, (a, b) in enumerate(chunks):
-      tw = time.perf_counter()
-      got = [f_.result() for f_ in (futs.pop(c) if c in futs else submit(c))]
-      t['split_wait_s'] += time.perf_counter() - tw
-      t['host_split_s'] += sum(g[2] for g in got)
-      if pool is not None and c + 2 < len(chunks):
-        futs[c + 2] = submit(c + 2)
+    for c, a, b, corpus, _, ts, wait in splits:
+      t['split_wait_s'] += wait
+      t['host_split_s'] += ts
       t0 = time.perf_counter()
-      sh = pipeline.upload_pieces([g[0] for g in got], pro[a:b + 1] - pro[a], device)
+      sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
       res = bart.aggregate(sh, None, args.target_seq_length, tok)
       torch.cuda.synchronize()
       t['gpu_s'] += time.perf_counter() - t0
@@ -919,19 +953,13 @@ def bart_main(args):
       if args.output_format == 'txt':
         out += bart.write_bart_txt(res, sink, part_base=a)
       else:
-        out += bart.write_bart_shards(res, sink, part_base=a, executor=enc, pending=pending)
+        out += bart.write_bart_shards(res, sink, part_base=a, executor=ws.enc, pending=pending)
       t['write_s'] += time.perf_counter() - t0
       t['chunks_out'] += res.n_chunks
     t0 = time.perf_counter()
     for f_ in pending:
       f_.result()
     t['drain_s'] = time.perf_counter() - t0
-  finally:
-    if pool is not None:
-      pool.shutdown(wait=True, cancel_futures=True)
-    if enc is not None:
-      enc.close()
-    index.close()
   t['wall_s'] = time.perf_counter() - wall0
   t.update(rank=rank, world=world, partitions=[lo, hi], documents=int(pro[hi] - pro[lo]), sentence_splitter=how,
            n_partitions=n_part)
@@ -939,11 +967,7 @@ def bart_main(args):
 
 
 def bart_console_script(argv=None):
-  args = attach_bart_args().parse_args(argv)
-  tic = time.perf_counter()
-  files, t = bart_main(args)
-  print('rank %d: %d files, %s' % (t['rank'], len(files), {k: v for k, v in t.items() if k != 'rank'}))
-  print('Running the pipeline took {} s'.format(time.perf_counter() - tic))
+  _run(bart_main, attach_bart_args().parse_args(argv))
 
 
 def codebert_console_script(argv=None):

@@ -486,6 +486,97 @@ def _host_var(arr, r0, n):
   return off - off[0], data
 
 
+FILE_NAMES = {'parquet': ('part.%d.parquet', 'part.%d.parquet_%d'), 'txt': ('%d.txt', '%d_%d.txt')}
+
+
+class FilePlan:
+  """The output files of one pack (or BART aggregate) call.  Rows are in
+  file order, (partition, bin) major: file f = partition f // nbins, bin
+  f % nbins = rows [file_start[f], file_start[f + 1]).  bin_count: rows per
+  (partition, bin); unbinned, a partition is one file.  Only the first
+  max_parts partitions are written: nfiles files, n_rows rows."""
+
+  def __init__(self, bin_count, binned, max_parts=None, part_base=0):
+    counts = np.asarray(bin_count, dtype=np.int64)
+    if not binned:
+      counts = counts.sum(axis=1, keepdims=True)
+    self.binned, self.nbins, self.part_base = binned, counts.shape[1], part_base
+    self.file_start = np.zeros(counts.size + 1, dtype=np.int64)
+    np.cumsum(counts.ravel(), out=self.file_start[1:])
+    self.nfiles = counts.size if max_parts is None else min(counts.size, max_parts * self.nbins)
+    self.n_rows = int(self.file_start[self.nfiles])
+
+  def batches(self, batch_rows):
+    """(f, g, r0, r1): runs of whole files [f, g) = rows [r0, r1) of up to
+    batch_rows rows (one file when it alone has more)"""
+    fs, f = self.file_start, 0
+    while f < self.nfiles:
+      g = f + 1
+      while g < self.nfiles and fs[g + 1] - fs[f] <= batch_rows:
+        g += 1
+      yield f, g, int(fs[f]), int(fs[g])
+      f = g
+
+  def files(self, f, g, out_dir, kind):
+    """(path, lo, hi) of files [f, g), rows relative to file f's first;
+    kind: the FILE_NAMES entry ('parquet' or 'txt')"""
+    fs, out = self.file_start, []
+    plain, per_bin = FILE_NAMES[kind]
+    for fi in range(f, g):
+      p, b = divmod(fi, self.nbins)
+      name = per_bin % (self.part_base + p, b) if self.binned else plain % (self.part_base + p)
+      out.append((os.path.join(out_dir, name), int(fs[fi] - fs[f]), int(fs[fi + 1] - fs[f])))
+    return out
+
+
+def pack_plan(res, bin_size, max_parts, part_base):
+  """the FilePlan of a pipeline.PackResult"""
+  n_part = res.bin_count.shape[0]
+  return FilePlan(res.bin_count.cpu().numpy().reshape(n_part, res.nbins), bin_size is not None, max_parts, part_base)
+
+
+def mlm_positions(packer, res, r0, r1, n_rows, cache, stream=None, host=True):
+  """masked_lm_positions of rows [r0, r1) as (offsets, bytes): render_npy,
+  or where its header table does not apply npy_positions on the host copy of
+  the call's n_rows rows (`cache`, a list, keeps it between batches)"""
+  pos = render_npy(packer, res, r0, r1 - r0, stream, host=host)
+  if pos is None:
+    if not cache:
+      moff = res.mlm_off[:n_rows + 1].cpu().numpy()
+      cache.extend([moff, res.mlm_pos[:int(moff[-1])].cpu().numpy().view(np.uint16)])
+    moff, mpos = cache
+    m0 = int(moff[r0])
+    pos = npy_positions(moff[r0:r1 + 1] - m0, mpos[m0:int(moff[r1])])
+  return pos
+
+
+class EncodeSink:
+  """Where a writer's parquet encodes go: a thread pool of its own, whose
+  files close() waits for, or the caller's executor (a ProcessEncoder or a
+  thread pool), where close() hands the open futures to the caller's list."""
+
+  @staticmethod
+  def check(executor, pending):
+    if executor is not None and pending is None:
+      raise ValueError('executor needs pending: the list that takes the futures of the encodes')
+
+  def __init__(self, executor, pending):
+    self.check(executor, pending)
+    self.own, self.pending = executor is None, pending
+    self.proc = isinstance(executor, ProcessEncoder)
+    self.workers = executor.workers if self.proc else encode_workers()
+    self.pool = concurrent.futures.ThreadPoolExecutor(self.workers) if self.own else executor
+    self.futs = []
+
+  def close(self):
+    if self.own:
+      for fu in self.futs:
+        fu.result()
+      self.pool.shutdown()
+    else:
+      self.pending.extend(self.futs)
+
+
 LAST_STATS = {}  # the last write_shards call's stage seconds (bench.py reports them)
 
 
@@ -498,122 +589,75 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
   for every bin b (binned).  doc_ids: CodeBERT 'id' strings (list or Arrow array) per document of
   the packed corpus.  max_parts: only the first max_parts partitions.
   executor / pending: the parquet encodes go to the caller's thread pool and
-  their futures to the caller's list, and this call returns once the string
+  their futures to the caller's list (an executor without that list is a
+  ValueError), and this call returns once the string
   columns are rendered and on the host (the device buffers are free again):
   the encodes run on while the caller's next chunk splits and packs.
   Rows are rendered in batches of whole files of about batch_rows rows, so
   the files of one batch encode while the next renders.
   Returns the list of files (written once the futures are done)."""
   t_start = time.perf_counter()
+  EncodeSink.check(executor, pending)
   os.makedirs(out_dir, exist_ok=True)
   binned = bin_size is not None
-  nbins = res.nbins if binned else 1
-  n_part = res.bin_count.shape[0]
-  counts = res.bin_count.cpu().numpy().reshape(n_part, res.nbins)
-  if not binned:
-    counts = counts.sum(axis=1, keepdims=True)
-  file_rows = counts.ravel()  # (partition, bin) major order == row order
-  file_start = np.zeros(len(file_rows) + 1, dtype=np.int64)
-  np.cumsum(file_rows, out=file_start[1:])
-  assert file_start[-1] == res.n_pairs, (file_start[-1], res.n_pairs)
-  sch = schema(codebert, masking and not codebert, binned)
+  masking = masking and not codebert
+  plan = pack_plan(res, bin_size, max_parts, part_base)
+  assert plan.file_start[-1] == res.n_pairs, (plan.file_start[-1], res.n_pairs)
+  sch = schema(codebert, masking, binned)
   # dictionary pages only where values repeat (flags, lengths, bins, the
   # CodeBERT id of a document's rows): the segment / label strings are unique
   # per row and the encoder would build and then discard a dictionary for them
   dict_cols = [n_ for n_ in sch.names if n_ not in DENSE_COLS]
-  nfiles = len(file_rows) if max_parts is None else min(len(file_rows), max_parts * nbins)
-  n_rows = int(file_start[nfiles])  # rows of the files written
+  n_rows = plan.n_rows  # rows of the files written
   num_tokens = np.diff(res.tok_off[:n_rows + 1].cpu().numpy()).astype(np.uint16)
   flags = res.flags[:n_rows].cpu().numpy()
   bins = res.bins[:n_rows].cpu().numpy().astype(np.int64)
-  docs = None
   if codebert:
     if doc_ids is None:
       raise ValueError('CodeBERT shards need doc_ids (the id column)')
     docs = np_array(row_docs(packer, res, n_rows, stream))
     ids_arr = doc_ids if isinstance(doc_ids, pa.Array) else str_array(doc_ids)
     ids_col = ids_arr.take(docs) if n_rows else str_array([])
-  host_mlm = []  # (offsets, positions) on the host, fetched only for the host npy path
-
-  def mlm_host():
-    if not host_mlm:
-      moff = res.mlm_off[:n_rows + 1].cpu().numpy()
-      host_mlm.extend([moff, res.mlm_pos[:int(moff[-1])].cpu().numpy().view(np.uint16)])
-    return host_mlm
+  host_mlm = []  # mlm_positions' cache
   files = []
-  f = 0
-  workers = encode_workers()
+  sink = EncodeSink(executor, pending)
   st = {'setup_s': time.perf_counter() - t_start, 'render_s': 0.0, 'table_s': 0.0, 'backpressure_s': 0.0,
-        'drain_s': 0.0, 'batches': 0, 'workers': workers}
-  own = executor is None
-  proc = isinstance(executor, ProcessEncoder)
-  if proc:
-    st['workers'] = executor.workers
-  pool = concurrent.futures.ThreadPoolExecutor(workers) if own else executor
-  mine = []
+        'drain_s': 0.0, 'batches': 0, 'workers': sink.workers}
+  seg0, seg1 = ('doc', 'code') if codebert else ('A', 'B')
   # render in batches of whole files (>= batch_rows rows, or one big file)
-  while f < nfiles:
-    g = f + 1
-    while g < nfiles and file_start[g + 1] - file_start[f] <= batch_rows:
-      g += 1
-    r0, r1 = int(file_start[f]), int(file_start[g])
+  for f, g, r0, r1 in plan.batches(batch_rows):
     n = r1 - r0
+    flist = plan.files(f, g, out_dir, 'parquet')
+    files.extend(f_[0] for f_ in flist)
     t0 = time.perf_counter()
-    if proc:
-      c0, c1 = seg_columns(packer, res, r0, n, codebert, stream, host=False)
-      var = {('doc' if codebert else 'A'): c0, ('code' if codebert else 'B'): c1}
-      if masking and not codebert:
-        var['masked_lm_labels'] = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream, host=False)
-        pos = render_npy(packer, res, r0, n, stream, host=False)
-        if pos is None:
-          moff_all, mpos_all = mlm_host()
-          m0 = int(moff_all[r0])
-          pos = npy_positions(moff_all[r0:r1 + 1] - m0, mpos_all[m0:int(moff_all[r1])])
-        var['masked_lm_positions'] = pos
+    host = not sink.proc  # (ProcessEncoder: the columns stay device tensors, which it copies into its shared slot)
+    var = dict(zip((seg0, seg1), seg_columns(packer, res, r0, n, codebert, stream, host=host)))
+    if masking:
+      var['masked_lm_labels'] = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream, host=host)
+      var['masked_lm_positions'] = mlm_positions(packer, res, r0, r1, n_rows, host_mlm, stream, host=host)
+    if sink.proc:
       if codebert:
         var['id'] = _host_var(ids_col, r0, n)
       fixed = {'is_random_next': ('bool', (flags[r0:r1] & 1).astype(bool)), 'num_tokens': ('u16', num_tokens[r0:r1]),
                'bin_id': ('i64', bins[r0:r1])}
       specs = [(nm, 'bin' if nm == 'masked_lm_positions' else 'str') + tuple(var[nm]) if nm in var else
                (nm, fixed[nm][0], fixed[nm][1], None) for nm in sch.names]
-      flist = []
-      for fi in range(f, g):
-        p, b = divmod(fi, nbins)
-        name = 'part.%d.parquet' % (part_base + p)
-        if binned:
-          name += '_%d' % b
-        flist.append((os.path.join(out_dir, name), int(file_start[fi] - r0), int(file_start[fi + 1] - r0)))
       t1 = time.perf_counter()
       st['render_s'] += t1 - t0
       st['batches'] += 1
-      mine.extend(executor.submit_batch(n, specs, sch, flist, compression, dict_cols, stream))
-      files.extend(f_[0] for f_ in flist)
+      sink.futs.extend(executor.submit_batch(n, specs, sch, flist, compression, dict_cols, stream))
       st['table_s'] += time.perf_counter() - t1
-      f = g
       continue
-    c0, c1 = seg_columns(packer, res, r0, n, codebert, stream)
-    if masking and not codebert:
-      lab = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream)
-      pos = render_npy(packer, res, r0, n, stream)
-      if pos is None:
-        moff_all, mpos_all = mlm_host()
-        m0 = int(moff_all[r0])
-        pos = npy_positions(moff_all[r0:r1 + 1] - m0, mpos_all[m0:int(moff_all[r1])])
     t1 = time.perf_counter()
     st['render_s'] += t1 - t0
     st['batches'] += 1
     # one table over the batch's rows; a file is a zero-copy slice of it
-    cols, raw = {}, {}
+    raw = {nm: (sch.field(nm).type,) + tuple(c) for nm, c in var.items()}
+    cols = {'num_tokens': np_array(num_tokens[r0:r1])}
     if codebert:
       cols['id'] = ids_col.slice(r0, n)
-      raw['doc'], raw['code'] = (pa.string(),) + tuple(c0), (pa.string(),) + tuple(c1)
     else:
-      raw['A'], raw['B'] = (pa.string(),) + tuple(c0), (pa.string(),) + tuple(c1)
       cols['is_random_next'] = np_array((flags[r0:r1] & 1).astype(bool))
-    cols['num_tokens'] = np_array(num_tokens[r0:r1])
-    if masking and not codebert:
-      raw['masked_lm_positions'] = (pa.binary(),) + tuple(pos)
-      raw['masked_lm_labels'] = (pa.string(),) + tuple(lab)
     if binned:
       cols['bin_id'] = np_array(bins[r0:r1])
     for nm, (typ, off, data) in raw.items():
@@ -621,31 +665,18 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
     arrs = [cols[name] for name in sch.names]
     large = any(a.type != fd.type for a, fd in zip(arrs, sch))
     tb = None if large else pa.Table.from_arrays(arrs, names=sch.names)
-    for fi in range(f, g):
-      lo, hi = int(file_start[fi] - r0), int(file_start[fi + 1] - r0)
-      p, b = divmod(fi, nbins)
+    for path, lo, hi in flist:
       t = file_table(sch, cols, raw, lo, hi, tb)
-      name = 'part.%d.parquet' % (part_base + p)
-      if binned:
-        name += '_%d' % b
-      path = os.path.join(out_dir, name)
-      mine.append(pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=dict_cols))
-      files.append(path)
+      sink.futs.append(sink.pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=dict_cols))
     t2 = time.perf_counter()
     st['table_s'] += t2 - t1
     # the parquet encoder releases the GIL: files of a batch encode in
     # parallel on the host cores while the next batch renders on the GPU
-    while len(mine) > 4 * workers:
-      mine.pop(0).result()
+    while len(sink.futs) > 4 * sink.workers:
+      sink.futs.pop(0).result()
     st['backpressure_s'] += time.perf_counter() - t2
-    f = g
   t3 = time.perf_counter()
-  if own:
-    for fu in mine:
-      fu.result()
-    pool.shutdown()
-  else:
-    pending.extend(mine)
+  sink.close()
   st['drain_s'] = time.perf_counter() - t3
   st['total_s'] = time.perf_counter() - t_start
   LAST_STATS.clear()
@@ -679,17 +710,8 @@ def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False
   field, rows in shuffled order within a bin == this packer's row order).
   Every file is created, empty ones included.  Returns the files."""
   os.makedirs(out_dir, exist_ok=True)
-  binned = bin_size is not None
-  nbins = res.nbins if binned else 1
-  n_part = res.bin_count.shape[0]
-  counts = res.bin_count.cpu().numpy().reshape(n_part, res.nbins)
-  if not binned:
-    counts = counts.sum(axis=1, keepdims=True)
-  file_rows = counts.ravel()
-  file_start = np.zeros(len(file_rows) + 1, dtype=np.int64)
-  np.cumsum(file_rows, out=file_start[1:])
-  nfiles = len(file_rows) if max_parts is None else min(len(file_rows), max_parts * nbins)
-  n_rows = int(file_start[nfiles])
+  plan = pack_plan(res, bin_size, max_parts, part_base)
+  n_rows = plan.n_rows
   num_tokens = np.diff(res.tok_off[:n_rows + 1].cpu().numpy())
   flags = res.flags[:n_rows].cpu().numpy()
   if codebert:
@@ -702,21 +724,14 @@ def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False
     moff_all = res.mlm_off[:n_rows + 1].cpu().numpy()
     mpos_all = res.mlm_pos[:int(moff_all[-1])].cpu().numpy().view(np.uint16)
   files = []
-  f = 0
-  while f < nfiles:
-    g = f + 1
-    while g < nfiles and file_start[g + 1] - file_start[f] <= batch_rows:
-      g += 1
-    r0, r1 = int(file_start[f]), int(file_start[g])
+  for f, g, r0, r1 in plan.batches(batch_rows):
     n = r1 - r0
     (o0, d0), (o1, d1) = seg_columns(packer, res, r0, n, codebert, stream)
     if masking and not codebert:
       ol, dl = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream)
     b0, b1 = d0.tobytes(), d1.tobytes()
     bl = dl.tobytes() if masking and not codebert else b''
-    for fi in range(f, g):
-      lo, hi = int(file_start[fi] - r0), int(file_start[fi + 1] - r0)
-      p, b = divmod(fi, nbins)
+    for path, lo, hi in plan.files(f, g, out_dir, 'txt'):
       lines = []
       for i in range(lo, hi):
         r = r0 + i
@@ -731,10 +746,7 @@ def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False
         else:
           lines.append('is_random_next: {} - [CLS] {} [SEP] {} [SEP] - {}'.format(bool(flags[r] & 1), a, bb,
                                                                                  int(num_tokens[r])))
-      name = ('%d_%d.txt' % (part_base + p, b)) if binned else ('%d.txt' % (part_base + p))
-      path = os.path.join(out_dir, name)
       with open(path, 'w', encoding='utf-8', newline='') as fh:
         fh.write('\n'.join(lines))
       files.append(path)
-    f = g
   return files

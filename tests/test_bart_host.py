@@ -123,3 +123,29 @@ def test_cli_plan_keeps_input_order_and_whole_lines(tmp_path):
   assert sents == ['id1 First doc.', 'It has two.', 'id2 Second doc here.', 'id3 Third.', 'Doc!']
   assert corpus.doc_sent_off.tolist() == [0, 2, 3, 5]
   index.close()
+
+
+def test_bart_file_plan_takes_partitions_as_files():
+  """the BART writers' plan: a partition's chunks are one file (writer.FilePlan, one bin)"""
+  from lddl_amd import bart
+  from types import SimpleNamespace
+  res = SimpleNamespace(part_chunk_off=np.array([0, 4, 4, 9, 10], np.int64))
+  plan = bart._plan(res, None, 5)
+  assert (plan.nfiles, plan.n_rows, plan.nbins) == (4, 10, 1)
+  assert list(plan.batches(5)) == [(0, 2, 0, 4), (2, 3, 4, 9), (3, 4, 9, 10)]
+  assert plan.files(0, 2, 'o', 'parquet') == [(os.path.join('o', 'part.5.parquet'), 0, 4),
+                                              (os.path.join('o', 'part.6.parquet'), 4, 4)]
+  assert plan.files(2, 4, 'o', 'txt') == [(os.path.join('o', '7.txt'), 0, 5), (os.path.join('o', '8.txt'), 5, 6)]
+  plan = bart._plan(res, 3, 0)
+  assert (plan.nfiles, plan.n_rows) == (3, 9) and list(plan.batches(1 << 16)) == [(0, 3, 0, 9)]
+  assert bart._plan(res, 9, 0).nfiles == 4
+
+
+def test_write_bart_shards_executor_needs_pending(tmp_path):
+  import concurrent.futures
+  from lddl_amd import bart
+  out = tmp_path / 'o'
+  with concurrent.futures.ThreadPoolExecutor(1) as ex:
+    with pytest.raises(ValueError):
+      bart.write_bart_shards(None, str(out), executor=ex)
+  assert not out.exists()

@@ -385,3 +385,209 @@ def test_file_table_rebases_offsets_past_2gib():
   assert t.column('A').to_pylist() == ['xyz'] and t.column('num_tokens').to_pylist() == [9]
   with pytest.raises(pa.ArrowInvalid):  # the old per-file slice + cast
     pa.Table.from_arrays([cols['A']], names=['A']).slice(1, 1).cast(pa.schema([('A', pa.string())]))
+
+
+# ---- the chunk plan, the worker scope and the split-ahead iterator ------------
+def _chunk_loop(pro, sizes, rank, world, chunk_b):
+  """the chunk bounds as main() and bart_main() each spelled them out"""
+  n_part = len(pro) - 1
+  lo, hi = rank * n_part // world, (rank + 1) * n_part // world
+  cum = np.concatenate([[0], np.cumsum(sizes[pro[lo]:pro[hi]])])
+  part_end = cum[pro[lo + 1:hi + 1] - pro[lo]]
+  bounds = [lo]
+  acc0 = 0
+  for p in range(lo, hi):
+    if part_end[p - lo] - acc0 >= chunk_b and p + 1 < hi:
+      bounds.append(p + 1)
+      acc0 = part_end[p - lo]
+  bounds.append(hi)
+  return lo, hi, part_end, [(a, b) for a, b in zip(bounds[:-1], bounds[1:]) if b > a]
+
+
+MAIN_CHUNK_BYTES = max(1, int(preprocess.attach_args().parse_args(['--sink', 'x']).chunk_mb * (1 << 20)))
+CHUNK_PLANS = {
+    'one partition': ([0, 5], [10, 20, 30, 40, 50], 1, 60),
+    'threshold first reached at the last partition': ([0, 2, 4, 6], [10] * 6, 1, 60),
+    'zero-byte partitions': ([0, 0, 2, 2, 2, 5, 5], [7, 9, 11, 13, 15], 1, 16),
+    'a rank with no partition': ([0, 3, 6], [5] * 6, 3, 10),
+    'one chunk per partition': ([0, 1, 3, 6, 7], [3, 1, 4, 1, 5, 9, 2], 1, 1),
+    "main's threshold": (list(range(0, 41, 4)), [3 << 20] * 40, 2, MAIN_CHUNK_BYTES),
+    "bart_main's threshold": (list(range(0, 41, 4)), [3 << 20] * 40, 2, preprocess.BART_CHUNK_BYTES),
+}
+
+
+@pytest.mark.parametrize('name', sorted(CHUNK_PLANS))
+def test_chunk_plan_is_the_loop_it_replaces(name):
+  pro, sizes, world, thr = CHUNK_PLANS[name]
+  pro, sizes = np.asarray(pro, np.int64), np.asarray(sizes, np.int64)
+  for rank in range(world):
+    lo, hi, part_end, chunks = preprocess.chunk_plan(pro, sizes, rank, world, thr)
+    wlo, whi, wend, wchunks = _chunk_loop(pro, sizes, rank, world, thr)
+    assert (lo, hi, chunks) == (wlo, whi, wchunks) and np.array_equal(part_end, wend)
+    # the chunks are non-empty runs of whole partitions that cover [lo, hi) in order
+    assert [a for a, _ in chunks] + [hi] == [lo] + [b for _, b in chunks] if chunks else lo == hi
+    assert all(a < b for a, b in chunks)
+  ranks = [preprocess.chunk_plan(pro, sizes, r, world, thr) for r in range(world)]
+  assert ranks[0][0] == 0 and ranks[-1][1] == len(pro) - 1 and all(x[1] == y[0] for x, y in zip(ranks, ranks[1:]))
+  if name == 'one partition':
+    assert ranks[0][3] == [(0, 1)]
+  if name == 'threshold first reached at the last partition':
+    assert ranks[0][3] == [(0, 3)]  # no empty chunk after it
+  if name == 'a rank with no partition':
+    assert [r[:2] for r in ranks] == [(0, 0), (0, 1), (1, 2)] and ranks[0][3] == [] and len(ranks[0][2]) == 0
+  if name == 'one chunk per partition':
+    assert ranks[0][3] == [(p, p + 1) for p in range(4)]
+  if name.endswith('threshold'):  # 12 MB partitions: the third closes a 32 MB chunk
+    assert thr == 32 << 20 and ranks[0][3] == [(0, 3), (3, 5)] and ranks[1][3] == [(5, 8), (8, 10)]
+
+
+@pytest.fixture
+def small_index(tmp_path):
+  """three files, 45 records, in 9 partitions"""
+  from lddl_amd import readers
+  files = []
+  for k in range(3):
+    lines = ['doc-%d-%d %s\n' % (k, j, 'Some words here. ' * (1 + (j * 7 + k) % 5)) for j in range(15)]
+    files.append(_write(tmp_path / 'src' / ('f%d.txt' % k), ''.join(lines).encode()))
+  index = readers.RecordIndex.build(files)
+  order = preprocess.sample_order(len(index), 3, 1.0)
+  return index, order, preprocess.partition_by_size(index.len[order], 9)
+
+
+def _procs(ws):
+  """the worker processes of a scope's split pool and encoder"""
+  ex = [ws.pool] + ([ws.enc.ex] if ws.encoder == 'procs' else [])
+  return [p for e in ex if e is not None for p in list((e._processes or {}).values())]
+
+
+def _assert_all_down(ws, procs):
+  import multiprocessing
+  assert not multiprocessing.active_children()
+  assert procs and not any(p.is_alive() for p in procs)
+  if ws.encoder == 'procs':
+    assert not os.path.exists(ws.enc.dir)
+  elif ws.enc is not None:
+    assert ws.enc._shutdown
+  assert preprocess._FE == {} and ws.index._mm == {}
+
+
+@pytest.mark.parametrize('procs', ['1', '0'])
+@pytest.mark.parametrize('how', ['normal', 'body raises', 'pool start raises'])
+def test_workers_scope_ends_every_worker_on_every_route(small_index, monkeypatch, how, procs):
+  """the encoder and the split pool of a CLI run end on every way out of the
+  scope, with the caller's exception unchanged; _FE holds the workers' state
+  only while they fork"""
+  from lddl_amd import writer
+  index, order, pro = small_index
+  monkeypatch.setenv('LDDL_ENCODE_WORKERS', '2')
+  monkeypatch.setenv('LDDL_ENCODE_PROCS', procs)
+  kind = preprocess._encoder(preprocess.attach_args().parse_args(['--sink', 'x']), True)
+  assert kind == ('procs' if procs == '1' else 'threads')
+  err = RuntimeError('boom')
+  started = []
+  real_warm = preprocess.Workers._warm
+
+  def warm(self):
+    real_warm(self)
+    assert preprocess._FE == {}
+    started.extend(_procs(self))
+    if how == 'pool start raises':
+      raise err
+  monkeypatch.setattr(preprocess.Workers, '_warm', warm)
+  t = {}
+  ws = preprocess.Workers(t, index, order, False, preprocess._rule_split, 2, kind)
+  if how == 'normal':
+    with ws:
+      assert preprocess._FE == {} and len(started) == (4 if kind == 'procs' else 2)
+      assert isinstance(ws.enc, writer.ProcessEncoder) == (kind == 'procs') and ws.enc is not None
+      corpus, ids, _ = ws.submit(pro, [(0, 2)])[0].result()  # the forked workers hold the state
+      want, wids = preprocess.split_chunk(index, order[pro[0]:pro[2]], False, preprocess._rule_split)
+      assert ids == wids and bytes(corpus.data[:corpus.nbytes]) == bytes(want.data[:want.nbytes])
+  else:
+    with pytest.raises(RuntimeError) as ei:
+      with ws:
+        assert how == 'body raises'
+        raise err
+    assert ei.value is err
+  _assert_all_down(ws, started)
+  assert {'enc_start_s', 'teardown_split_s', 'teardown_s'} <= set(t)
+  assert ('pool_start_s' in t) == (how != 'pool start raises')
+  assert ('teardown_enc_exit_s' in t) == (kind == 'procs')
+
+
+def _whole(index, order, pro, a, b):
+  return preprocess.split_chunk(index, order[int(pro[a]):int(pro[b])], False, preprocess._rule_split)
+
+
+@pytest.mark.parametrize('nw', [0, 2])
+def test_split_ahead_yields_every_chunk_split_as_at_once(small_index, nw):
+  """the pieces of every chunk, from the pool or inline, are the chunk split
+  at once; chunks come in order; at most two beyond the one being consumed
+  are ever submitted; a todo list leaves the other chunks alone"""
+  index, order, pro = small_index
+  lo, hi, part_end, chunks = preprocess.chunk_plan(pro, index.len[order], 0, 1, 1)
+  assert len(chunks) == 9
+  chunks = [(0, 3), (3, 4)] + chunks[4:]  # a chunk of several pieces
+  for todo in (list(range(len(chunks))), [0, 2, 5]):
+    with preprocess.Workers({}, index, order, False, preprocess._rule_split, nw, None, early_exit=True) as ws:
+      assert (ws.pool is not None) == (nw > 0)
+      workers, manager = _procs(ws), ws.pool and ws.pool._executor_manager_thread
+      submitted, consumed = [], [0]
+      real = ws.submit
+
+      def counting(pro_, pieces):
+        submitted.append((pieces[0][0], pieces[-1][1], consumed[0]))
+        return real(pro_, pieces)
+      ws.submit = counting
+      splits = preprocess.split_ahead(ws, pro, part_end, lo, chunks, todo)
+      assert len(submitted) == (min(2, len(todo)) if nw else 0)  # split while the caller brings up the GPU
+      got = []
+      for c, a, b, corpora, ids, ts, wait in splits:
+        consumed[0] += 1
+        got.append(c)
+        assert (a, b) == chunks[c] and ts >= 0 and wait >= 0
+        assert len(corpora) == (len(preprocess.chunk_pieces(part_end, lo, a, b, 2 * nw)) if nw else 1)
+        one, _ = preprocess.concat_corpora(corpora, [[]] * len(corpora))
+        want, wids = _whole(index, order, pro, a, b)
+        assert ids == wids
+        assert bytes(one.data[:one.nbytes]) == bytes(want.data[:want.nbytes])
+        np.testing.assert_array_equal(one.sent_off, want.sent_off)
+        np.testing.assert_array_equal(one.doc_sent_off, want.doc_sent_off)
+      assert got == todo
+      # every listed chunk submitted once, none more than two ahead of the one being consumed
+      assert sorted((a, b) for a, b, _ in submitted) == [chunks[c] for c in todo]
+      ahead = [todo.index(chunks.index((a, b))) - at for a, b, at in submitted]
+      assert max(ahead) == (2 if nw else 0) and min(ahead) >= 0
+      if nw:  # early_exit: the workers were told to go once the last split was in
+        with pytest.raises(RuntimeError):
+          ws.pool.submit(preprocess._split_warm, 0)
+    if nw:  # (told to go early, the workers end on their own: the executor's thread reaps them, not the scope's exit)
+      manager.join(60)
+      assert not manager.is_alive() and not any(p.is_alive() for p in workers)
+  import multiprocessing
+  assert not multiprocessing.active_children()
+
+
+def test_settler_saves_markers_in_chunk_order(tmp_path):
+  """a chunk's marker is written once its encodes are done, oldest first, and
+  at most `keep` chunks stay in flight"""
+  import concurrent.futures
+  sink = str(tmp_path)
+  t = {}
+  s = preprocess.Settler(sink, 'k', True, t)
+  f0, f1, f2 = (concurrent.futures.Future() for _ in range(3))
+  s.inflight.append((0, 1, [], [f0], [[1]], 1))
+  s.inflight.append((1, 2, [], [f1], [[2]], 2))
+  f1.set_result(None)
+  s.settle(2)
+  assert preprocess.load_marker(sink, 0, 1, 'k') is None and preprocess.load_marker(sink, 1, 2, 'k') is None
+  f0.set_result(None)
+  s.inflight.append((2, 3, [], [f2], [[3]], 3))
+  s.settle(2)  # the two finished chunks go, the third is still encoding
+  assert preprocess.load_marker(sink, 0, 1, 'k')['n_pairs'] == 1 and preprocess.load_marker(sink, 1, 2, 'k') is not None
+  assert preprocess.load_marker(sink, 2, 3, 'k') is None and len(s.inflight) == 1
+  f2.set_exception(OSError('disk'))
+  with pytest.raises(OSError):
+    s.settle(0)
+  assert preprocess.load_marker(sink, 2, 3, 'k') is None and t['write_wait_s'] >= 0
+  preprocess.Settler(sink, None, False, t).settle(0)

@@ -6,6 +6,7 @@ import os
 
 import numpy as np
 import pyarrow as pa
+import pytest
 
 from lddl_amd import writer
 
@@ -138,3 +139,75 @@ def test_host_var_all_empty_strings():
   assert off.tolist() == [0, 0, 0] and data.size == 0
   off, data = writer._host_var(b, 2, 2)
   assert off.tolist() == [0, 0, 2] and bytes(data) == b'yz'
+
+
+# ---- the file plan and the encode sink ----------------------------------------
+def _plan_loops(counts, binned, max_parts, batch_rows):
+  """file_start, nfiles, n_rows and the batches as write_shards and write_txt
+  each spelled them out"""
+  counts = np.asarray(counts, np.int64)
+  nbins = counts.shape[1] if binned else 1
+  if not binned:
+    counts = counts.sum(axis=1, keepdims=True)
+  file_rows = counts.ravel()
+  file_start = np.zeros(len(file_rows) + 1, dtype=np.int64)
+  np.cumsum(file_rows, out=file_start[1:])
+  nfiles = len(file_rows) if max_parts is None else min(len(file_rows), max_parts * nbins)
+  batches, f = [], 0
+  while f < nfiles:
+    g = f + 1
+    while g < nfiles and file_start[g + 1] - file_start[f] <= batch_rows:
+      g += 1
+    batches.append((f, g, int(file_start[f]), int(file_start[g])))
+    f = g
+  return file_start, nfiles, int(file_start[nfiles]), batches
+
+
+PLAN_COUNTS = [[5, 0, 7, 1], [0, 0, 0, 0], [30, 2, 0, 4], [1, 1, 1, 1], [0, 9, 0, 0]]  # empty files, one of 30 rows
+
+
+@pytest.mark.parametrize('part_base', [0, 11])
+@pytest.mark.parametrize('max_parts', [None, 1, 3, 5, 9])
+@pytest.mark.parametrize('binned', [False, True])
+def test_file_plan(binned, max_parts, part_base):
+  plan = writer.FilePlan(PLAN_COUNTS, binned, max_parts, part_base)
+  nb = 4 if binned else 1
+  for batch_rows in (1, 10, 29, 30, 1 << 16):  # (binned, the 30-row file is larger than the first four)
+    fs, nfiles, n_rows, batches = _plan_loops(PLAN_COUNTS, binned, max_parts, batch_rows)
+    assert np.array_equal(plan.file_start, fs) and (plan.nfiles, plan.n_rows, plan.nbins) == (nfiles, n_rows, nb)
+    got = list(plan.batches(batch_rows))
+    assert got == batches
+    # whole files, each once and in order; no file split; the rows add up
+    assert [b[0] for b in got] + [nfiles] == [0] + [b[1] for b in got]
+    assert all((r0, r1) == (fs[f], fs[g]) and g > f for f, g, r0, r1 in got)
+    assert all(r1 - r0 <= batch_rows or g == f + 1 for f, g, r0, r1 in got)
+    assert sum(r1 - r0 for _, _, r0, r1 in got) == n_rows
+    for f, g, r0, r1 in got:
+      for kind in ('parquet', 'txt'):
+        files = plan.files(f, g, 'out', kind)
+        assert [(lo + r0, hi + r0) for _, lo, hi in files] == [(fs[i], fs[i + 1]) for i in range(f, g)]
+        for i, (path, _, _) in zip(range(f, g), files):
+          p, b = part_base + i // nb, i % nb
+          want = {('parquet', False): 'part.%d.parquet' % p, ('parquet', True): 'part.%d.parquet_%d' % (p, b),
+                  ('txt', False): '%d.txt' % p, ('txt', True): '%d_%d.txt' % (p, b)}[kind, binned]
+          assert path == os.path.join('out', want)
+  assert plan.nfiles == min(5, max_parts or 5) * nb
+  assert plan.n_rows == sum(sum(r) for r in PLAN_COUNTS[:max_parts])
+
+
+def test_file_plan_without_partitions():
+  plan = writer.FilePlan(np.zeros((0, 4), np.int64), True)
+  assert (plan.nfiles, plan.n_rows, list(plan.batches(10))) == (0, 0, [])
+  assert writer.FilePlan(np.zeros((0, 1), np.int64), False).nfiles == 0
+
+
+def test_write_shards_executor_needs_pending(tmp_path):
+  """an executor without the list for its futures is refused before anything is written"""
+  import concurrent.futures
+  out = tmp_path / 'o'
+  with concurrent.futures.ThreadPoolExecutor(1) as ex:
+    with pytest.raises(ValueError):
+      writer.write_shards(None, None, str(out), executor=ex)
+    sink = writer.EncodeSink(ex, [])
+    assert not sink.own and not sink.proc and sink.pool is ex
+  assert not out.exists()

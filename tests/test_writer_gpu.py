@@ -461,3 +461,97 @@ def test_render_npy_matches_host(packer):
                                   ctypes.c_void_p(res.mlm_pos.data_ptr()), big, 1, ctypes.c_void_p(hdr.data_ptr()),
                                   hlen, int(k[big]) - 1, ctypes.c_void_p(o.data_ptr()), None, 0, ctypes.byref(nb), None)
   assert rc == -1
+
+
+def _three_partitions(tmp_path, monkeypatch):
+  """three input files of ~1.5 KB: three partitions, and with --chunk-mb
+  0.0005 (524 bytes) three chunks; two encode workers (each is a fork of
+  the test process)"""
+  monkeypatch.setenv('LDDL_ENCODE_WORKERS', '2')
+  src = tmp_path / 'wiki' / 'en'
+  src.mkdir(parents=True)
+  for k in range(3):
+    with open(str(src / ('wiki_%d.txt' % k)), 'w', encoding='utf-8') as f:
+      for d in range(12):
+        body = ' '.join('Sentence %d of it has some words.' % s for s in range(2 + (d + k) % 4))
+        f.write('wiki-%d-%d %s\n' % (k, d, body))
+  return ['--wikipedia', str(tmp_path / 'wiki'), '--target-seq-length', '128', '--sentence-splitter', 'rules',
+          '--seed', '3', '--sample-ratio', '1.0', '--chunk-mb', '0.0005']
+
+
+@pytest.mark.parametrize('where', ['second chunk', 'before the chunk loop'])
+def test_cli_host_error_ends_workers_and_keeps_markers_true(gpu, tmp_path, monkeypatch, where):
+  """a Python exception in the host code of a run -- in the writer on the
+  second chunk, or between the Packer's construction and the chunk loop --
+  propagates as it is, and leaves no worker process, no encoder slot
+  directory, and markers only for the chunks whose files are written"""
+  import multiprocessing
+  from lddl_amd import preprocess, writer
+  sink = tmp_path / 'out'
+  argv = _three_partitions(tmp_path, monkeypatch) + ['--sink', str(sink), '--split-workers', '2', '--resume']
+  err = RuntimeError('injected')
+  encoders, calls = [], []
+  real_init, real_write = writer.ProcessEncoder.__init__, writer.write_shards
+
+  def init(self, *a, **kw):
+    encoders.append(self)
+    real_init(self, *a, **kw)
+
+  def write(*a, **kw):
+    calls.append(kw['part_base'])
+    if len(calls) == 2:
+      raise err
+    return real_write(*a, **kw)
+
+  def boom(*a, **kw):
+    raise err
+  monkeypatch.setattr(writer.ProcessEncoder, '__init__', init)
+  if where == 'second chunk':
+    monkeypatch.setattr(writer, 'write_shards', write)
+  else:
+    monkeypatch.setattr(preprocess, 'Settler', boom)
+  before = {p.pid for p in multiprocessing.active_children()}
+  with pytest.raises(RuntimeError) as ei:
+    preprocess.main(preprocess.attach_args().parse_args(argv))
+  assert ei.value is err
+  assert not [p for p in multiprocessing.active_children() if p.pid not in before]
+  assert len(encoders) == 1 and os.path.basename(encoders[0].dir).startswith('lddl_enc_')
+  assert not os.path.exists(encoders[0].dir) and preprocess._FE == {}
+  done = sink / preprocess.DONE_DIR
+  markers = sorted(os.listdir(str(done))) if done.exists() else []
+  if where == 'second chunk':
+    assert calls == [0, 1] and markers == ['chunk_0_1.json']
+    monkeypatch.setattr(writer, 'write_shards', real_write)
+    files, t = preprocess.main(preprocess.attach_args().parse_args(argv))
+    assert (t['chunks'], t['chunks_skipped']) == (3, 1)
+    assert sorted(os.path.basename(f) for f in files) == ['part.%d.parquet' % p for p in range(3)]
+  else:
+    assert markers == []
+
+
+BASE_KEYS = {'host_read_s', 'enc_start_s', 'gpu_init_s', 'host_split_s', 'split_wait_s', 'gpu_s', 'write_s', 'pairs',
+             'split_workers', 'chunks_skipped', 'write_wait_s', 'drain_s', 'teardown_split_s', 'teardown_s', 'wall_s',
+             'host_split_hidden_s', 'rank', 'world', 'partitions', 'documents', 'chunks', 'sentence_splitter',
+             'n_partitions'}
+PARQUET_KEYS = {'writer_setup_s', 'writer_render_s', 'writer_table_s', 'enc_slot_wait_s', 'enc_copy_s',
+                'teardown_enc_exit_s', 'teardown_enc_unpin_s', 'teardown_enc_rm_s'}
+TIMING_KEYS = {
+    'parquet with a pool': (['--split-workers', '2'], BASE_KEYS | PARQUET_KEYS | {'pool_start_s'}),
+    'parquet, --split-workers 0': (['--split-workers', '0'], BASE_KEYS | PARQUET_KEYS),
+    'txt': (['--split-workers', '0', '--output-format', 'txt'], BASE_KEYS),
+    '--num-shards': (['--split-workers', '0', '--num-shards', '2'], BASE_KEYS | PARQUET_KEYS | {'balance_s', 'shards'}),
+}
+
+
+@pytest.mark.parametrize('name', sorted(TIMING_KEYS))
+def test_cli_timing_keys(gpu, tmp_path, monkeypatch, name):
+  """the keys of the timing dict main() returns (the benchmark copies every
+  numeric one into its line).  The sets are the parent's: this test, run on
+  the tree before the chunk runner, worker scope and file plan were shared,
+  passed with these literals"""
+  from lddl_amd import preprocess
+  flags, want = TIMING_KEYS[name]
+  _, t = preprocess.main(preprocess.attach_args().parse_args(
+      _three_partitions(tmp_path, monkeypatch) + ['--sink', str(tmp_path / 'out')] + flags))
+  assert set(t) == want
+  assert t['chunks'] == 3 and t['split_workers'] == int(flags[1])

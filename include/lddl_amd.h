@@ -678,6 +678,54 @@ int lddl_bart_render(lddl_ctx *ctx, const uint8_t *d_data, int64_t nbytes, const
                      int64_t n_chunks, int64_t c0, int64_t n, int64_t *d_out_off, uint8_t *d_out_bytes,
                      int64_t out_cap, int64_t *out_nbytes, void *stream);
 
+/* ---- Sentence split: raw records to the sentence-split corpus ---------------
+ * The corpus lddl_tokenize and lddl_bart_* read (d_data, d_sent_off,
+ * d_doc_sent_off) made on the device from raw records: d_buf [nbytes] holds
+ * the records back to back, record r = bytes [rec_off[r], rec_off[r + 1]),
+ * document r of the result.  The split is the front end's rule-based one
+ * (preprocess._rule_split; the reference calls nltk.sent_tokenize at
+ * pretrain.py:82-97 `_to_document` and bart/pretrain.py:82-86), each piece
+ * stripped of whitespace and the empty ones dropped, with Python's str
+ * semantics per code point.  mode 0 (BERT) first splits the id off as
+ * readers.py:142-147 does: the id ends at the first whitespace character,
+ * the body starts one character after it; mode 1 (BART) splits the whole
+ * record.  No byte outside [0, nbytes) is read (no padding is needed), no
+ * record reads into its neighbour, and every record must be strict UTF-8.
+ *
+ * lddl_set_split_props: the code point properties the rules read, one byte
+ * per code point (bit 0 str.isspace, 1 isupper, 2 isdigit, 3 "lowers to one
+ * alphabetic character"), copied to the device; n must be 0x110000.
+ * LDDL_EINVAL otherwise. */
+int lddl_set_split_props(lddl_ctx *ctx, const uint8_t *host_tab, int64_t n);
+
+/* The length call (replaces the host's pretrain.py:82-97 / bart/pretrain.py:82-86
+ * and readers.py:142-147 seams): d_out_doc_sent_off [n_rec + 1] (int64) = the
+ * sentences per record in exclusive-scan form, d_out_id_end [n_rec] (int64;
+ * may be NULL in mode 1) = where each record's id ends in d_buf (its id is
+ * [rec_off[r], id_end[r]); rec_off[r] in mode 1), out_totals = {n_sent, the
+ * sentences' bytes}.  Synchronises the stream once.  LDDL_EINVAL: a NULL
+ * pointer, a negative count, a mode other than 0 or 1, no property table,
+ * d_rec_off not starting at 0, running backwards or not ending at nbytes;
+ * LDDL_ECAPACITY: nbytes >= 2^31; LDDL_EFORMAT: a record that is not strict
+ * UTF-8, *out_bad_rec = the lowest such record (-1 otherwise) and the outputs
+ * undefined. */
+int lddl_split_len(lddl_ctx *ctx, const uint8_t *d_buf, int64_t nbytes, const int64_t *d_rec_off, int64_t n_rec,
+                   int32_t mode, int64_t *d_out_doc_sent_off, int64_t *d_out_id_end, int64_t out_totals[2],
+                   int64_t *out_bad_rec, void *stream);
+
+/* The fill call: d_out_data [out_bytes + 16] = the sentences back to back and
+ * 16 zero bytes (lddl_tokenize's padding), d_out_sent_off [n_sent + 1] (int64)
+ * their offsets from 0.  d_doc_sent_off, n_sent and out_bytes are
+ * lddl_split_len's for the same input; nothing of that call is kept in the
+ * ctx, so its passes run again and the three are compared with what they
+ * give before anything is stored: a difference is LDDL_EINVAL with nothing
+ * written, and no store leaves [0, out_bytes + 16) / [0, n_sent].
+ * Synchronises the stream once (before the stores, which are queued on it).
+ * Other errors as lddl_split_len. */
+int lddl_split(lddl_ctx *ctx, const uint8_t *d_buf, int64_t nbytes, const int64_t *d_rec_off, int64_t n_rec,
+               int32_t mode, const int64_t *d_doc_sent_off, int64_t n_sent, int64_t out_bytes, uint8_t *d_out_data,
+               int64_t *d_out_sent_off, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,11 @@ SIGNATURES = {
     'lddl_bart_render': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                  c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64),
                                  c_void_p]),
+    'lddl_set_split_props': (c_int, [c_void_p, c_void_p, c_int64]),
+    'lddl_split_len': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p,
+                               ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p]),
+    'lddl_split': (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int64,
+                           c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

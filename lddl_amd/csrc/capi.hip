@@ -39,6 +39,7 @@ static void free_ctx(lddl_ctx* c) {
   (void)hipFree(c->d_ovf);
   (void)hipFree(c->d_counter);
   (void)hipFree(c->d_ctab);
+  (void)hipFree(c->d_split_props);
   (void)hipFree(c->d_nrec);
   if (c->tm) {
     for (int k = 0; k < 3; ++k)

@@ -107,6 +107,11 @@ enum CtxWs {
   CW_PCH,          // tokenize: WordPiece head per record slot
   CW_CHUNK_PART,   // lddl_row_spans: the partition of every 64 rows
   CW_PART_PB,      // lddl_row_spans: per partition, launch_chunk_parts' pair base
+  CW_SPLIT_REC,    // lddl_split[_len]: per record, body start / stripped end / sentences (int32 each), then its
+                   // own doc_sent_off (int64)
+  CW_SPLIT_PIECE,  // lddl_split: sentence starts per piece (int32), then their exclusive scan (int64)
+  CW_SPLIT_MAP,    // lddl_split: a bit per input byte, set where a record's first sentence starts
+  CW_SPLIT_SENT,   // lddl_split: per sentence, its start and its end / length in the input (int32 each)
   CW_COUNT
 };
 
@@ -122,6 +127,8 @@ enum HostWord {
   HW_PACK_ERR,      // lddl_pack_bert / _codebert: the partitions' PACK_E* flags or-ed (int32);
                     // lddl_rows_from_strings_len: the table's row tokens (one 24-byte copy with its neighbours)
   HW_BART_NSENT = HW_PACK_ERR,  // the same word; lddl_bart_plan_len: doc_sent_off's last entry, compared with n_sent
+  HW_SPLIT_NSENT = HW_NPAIRS, HW_SPLIT_BYTES = HW_NTOK, HW_SPLIT_BAD = HW_PACK_ERR,  // the same words;
+                    // lddl_split[_len]: the sentences, their bytes, the lowest record that is not UTF-8
   HW_NMASK,         // lddl_pack_bert (masking): the masked entries; lddl_rows_from_strings_len: the same of the table
   HW_MARENA_USED,   // lddl_pack_bert (masking): the arena entries the bump allocator handed out
   HW_NDENSE,        // lddl_pack_bert / _codebert: the tokenizer's dense ids
@@ -205,6 +212,8 @@ struct lddl_ctx {
   // collate: whole-token vocab table (built on first use)
   uint2* d_ctab = nullptr;
   uint32_t ctab_mask = 0;
+  // sentence split: the code point properties (lddl_set_split_props)
+  uint8_t* d_split_props = nullptr;
 };
 
 template <class T>

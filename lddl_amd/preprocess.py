@@ -233,6 +233,15 @@ def attach_bool_arg(parser, flag_name, default=False, help_str=None):
   parser.set_defaults(**{attr: default})
 
 
+def attach_split_device_arg(p):
+  """--split-device {host,gpu}: this front end's own flag (the reference has no counterpart)"""
+  p.add_argument('--split-device', type=str, default='host', choices=['host', 'gpu'],
+                 help='where the sentence split runs: host (default; the forked split workers) or gpu (the '
+                      'rule-based splitter as kernels, lddl_amd/splitgpu.py: the workers only gather the raw '
+                      'records; needs --sentence-splitter rules; same output files)')
+  return p
+
+
 def attach_args(parser=None, codebert=False):
   """The reference's flags (pretrain.py:618-880; pretrain_codebert.py's
   --code variant).  --schedule / --local-* are accepted for compatibility;
@@ -268,6 +277,7 @@ def attach_args(parser=None, codebert=False):
   attach_bool_arg(p, 'masking', default=False, help_str='static masking (pretrain.py:859-866)')
   p.add_argument('--masked-lm-ratio', type=float, default=0.15)
   p.add_argument('--sentence-splitter', type=str, default='auto', choices=['auto', 'punkt', 'rules'])
+  attach_split_device_arg(p)
   p.add_argument('--chunk-mb', type=float, default=32.0,
                  help='raw MB of partitions per pipeline chunk (host split of the next chunks overlaps the GPU and '
                       'the writer on chunk k)')
@@ -392,10 +402,43 @@ def _split_warm(_):
   return os.getpid()
 
 
+def gpu_split_check(args, how, codebert=False):
+  """--split-device gpu: the rule-based splitter of BERT / BART records only"""
+  if getattr(args, 'split_device', 'host') != 'gpu':
+    return False
+  if codebert:
+    raise ValueError('--split-device gpu: the codebert sub-command splits lines, not sentences; its split stays '
+                     'on the host')
+  if how != 'rules':
+    raise ValueError('--split-device gpu runs the rule-based splitter and --sentence-splitter resolved to %s: '
+                     'pass --sentence-splitter rules' % how)
+  return True
+
+
+def gather_records(index, idx):
+  """records idx of the index as one buffer + offsets (not decoded, not split)"""
+  from .splitgpu import join_records
+  return join_records(index.raws(idx))
+
+
+def concat_records(pieces):
+  """(buf, rec_off) of consecutive gathered pieces"""
+  if len(pieces) == 1:
+    return pieces[0]
+  off, base = [np.zeros(1, np.int64)], 0
+  for _, ro in pieces:
+    off.append(ro[1:] + base)
+    base += int(ro[-1])
+  return np.concatenate([b for b, _ in pieces]), np.concatenate(off)
+
+
 def _split_piece(fe, a, b):
   """records [a, b) of the order, split: (corpus, doc ids, seconds); fe: the
-  state the split workers inherit through _FE"""
+  state the split workers inherit through _FE.  With gather=True (--split-device
+  gpu) the records are only gathered: ((buf, rec_off), None, seconds)."""
   ts = time.perf_counter()
+  if fe.get('gather', False):
+    return gather_records(fe['index'], fe['order'][a:b]), None, time.perf_counter() - ts
   corpus, ids = split_chunk(fe['index'], fe['order'][a:b], fe['codebert'], fe['split'], fe.get('bart', False))
   if fe.get('bart', False):  # (BART keeps the id in the text: no id list travels back to the parent)
     ids = None
@@ -757,6 +800,7 @@ def main(args, codebert=False):
   wall0 = t0 = time.perf_counter()
   gloo = _dist_init(world)
   split, how = (None, 'code-lines') if codebert else sentence_splitter(args.sentence_splitter)
+  on_gpu = gpu_split_check(args, how, codebert)
   index, order, pro = plan_input(args, codebert, rank, world, gloo)
   n_part = len(pro) - 1
   t['host_read_s'] = time.perf_counter() - t0
@@ -771,12 +815,15 @@ def main(args, codebert=False):
   # (a chunk's pieces are whole partitions: no more workers than partitions to split)
   n_todo = sum(chunks[c][1] - chunks[c][0] for c in todo)
   nw = min(max(0, sw), n_todo) if n_todo > 1 else 0
-  if not codebert and split is _rule_split:
+  if on_gpu:
+    from . import splitgpu, splitnative
+    splitnative.props_table()
+  elif not codebert and split is _rule_split:
     from . import splitnative
     if splitnative.available():
       splitnative.props_table()  # (loaded here once; the forked workers share it)
   with Workers(t, index, order, codebert, split, nw, _encoder(args, True),
-               early_exit=os.environ.get('LDDL_SPLIT_EARLY_EXIT', '1') != '0') as ws:
+               early_exit=os.environ.get('LDDL_SPLIT_EARLY_EXIT', '1') != '0', gather=on_gpu) as ws:
     # the first chunks split while this process brings up the GPU context and
     # the device tables
     splits = split_ahead(ws, pro, part_end, lo, chunks, todo)
@@ -789,6 +836,8 @@ def main(args, codebert=False):
     counts = torch.zeros(hi - lo, nbins, dtype=torch.int64, device=device)  # rows per (partition, bin)
     t.update(host_split_s=0.0, split_wait_s=0.0, gpu_s=0.0, write_s=0.0, pairs=0, split_workers=nw,
              chunks_skipped=len(done))
+    if on_gpu:
+      t['gpu_split_s'] = 0.0
     for c, m in done.items():
       a, b = chunks[c]
       counts[a - lo:b - lo] = torch.tensor(m['counts'], dtype=torch.int64)
@@ -799,7 +848,12 @@ def main(args, codebert=False):
         t['split_wait_s'] += wait
         t['host_split_s'] += ts
         t0 = time.perf_counter()
-        sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
+        if on_gpu:  # (host_split_s is then the workers' gather time)
+          sh, ids = splitgpu.split_device(pk.tok, concat_records(corpus), False, pro[a:b + 1] - pro[a])
+          torch.cuda.synchronize()
+          t['gpu_split_s'] += time.perf_counter() - t0
+        else:
+          sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
         ids_d, ntok, toff = pk.tokenize(sh)
         # partition p packs after random.seed(args.seed + global p)
         res = pk.pack(sh, ids_d, ntok, toff, target_seq_length=args.target_seq_length,
@@ -838,7 +892,7 @@ def main(args, codebert=False):
   # the part of the host split hidden behind the GPU and the writer
   t['host_split_hidden_s'] = max(0.0, t['host_split_s'] - t['split_wait_s'])
   t.update(rank=rank, world=world, partitions=[lo, hi], documents=int(pro[hi] - pro[lo]), chunks=len(chunks),
-           sentence_splitter=how, n_partitions=n_part)
+           sentence_splitter='rules-gpu' if on_gpu else how, n_partitions=n_part)
   return out, t
 
 
@@ -863,7 +917,8 @@ def console_script(argv=None, codebert=False):
 # ----------------------------------------------------------------- BART --
 def attach_bart_args(parser=None):
   """The reference's BART flags (bart/pretrain.py:187-286) and
-  --sentence-splitter, which the other two sub-commands have too.
+  --sentence-splitter, which the other two sub-commands have too (the
+  sub-command's own --split-device is added by bart_parser).
   --short-seq-prob is accepted and unused, as in the reference;
   --schedule / --local-* are accepted and ignored."""
   p = parser or argparse.ArgumentParser('lddl_amd preprocessor for the BART pretraining task')
@@ -925,6 +980,10 @@ def bart_main(args):
   wall0 = t0 = time.perf_counter()
   gloo = _dist_init(world)
   split, how = sentence_splitter(args.sentence_splitter)
+  on_gpu = gpu_split_check(args, how)
+  if on_gpu:
+    from . import splitgpu, splitnative
+    splitnative.props_table()
   index, order, pro = plan_bart_input(args, rank, world, gloo)
   n_part = len(pro) - 1
   t['host_read_s'] = time.perf_counter() - t0
@@ -932,7 +991,7 @@ def bart_main(args):
   sink = os.path.abspath(os.path.expanduser(args.sink))
   os.makedirs(sink, exist_ok=True)
   nw = min(cpu_share(), hi - lo) if hi - lo > 1 else 0
-  with Workers(t, index, order, False, split, nw, _encoder(args, False), bart=True) as ws:
+  with Workers(t, index, order, False, split, nw, _encoder(args, False), bart=True, gather=on_gpu) as ws:
     splits = split_ahead(ws, pro, part_end, lo, chunks, range(len(chunks)))
     t0 = time.perf_counter()
     device = torch.device('cuda', local)
@@ -940,12 +999,19 @@ def bart_main(args):
     tok = Tokenizer(device=local)  # (the ctx of the C calls; the vocabulary is not read)
     t['gpu_init_s'] = time.perf_counter() - t0
     t.update(host_split_s=0.0, split_wait_s=0.0, gpu_s=0.0, write_s=0.0, chunks_out=0, split_workers=nw)
+    if on_gpu:
+      t['gpu_split_s'] = 0.0
     out, pending = [], []
     for c, a, b, corpus, _, ts, wait in splits:
       t['split_wait_s'] += wait
       t['host_split_s'] += ts
       t0 = time.perf_counter()
-      sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
+      if on_gpu:  # (host_split_s is then the workers' gather time)
+        sh, _ = splitgpu.split_device(tok, concat_records(corpus), True, pro[a:b + 1] - pro[a])
+        torch.cuda.synchronize()
+        t['gpu_split_s'] += time.perf_counter() - t0
+      else:
+        sh = pipeline.upload_pieces(corpus, pro[a:b + 1] - pro[a], device)
       res = bart.aggregate(sh, None, args.target_seq_length, tok)
       torch.cuda.synchronize()
       t['gpu_s'] += time.perf_counter() - t0
@@ -961,13 +1027,19 @@ def bart_main(args):
       f_.result()
     t['drain_s'] = time.perf_counter() - t0
   t['wall_s'] = time.perf_counter() - wall0
-  t.update(rank=rank, world=world, partitions=[lo, hi], documents=int(pro[hi] - pro[lo]), sentence_splitter=how,
-           n_partitions=n_part)
+  t.update(rank=rank, world=world, partitions=[lo, hi], documents=int(pro[hi] - pro[lo]),
+           sentence_splitter='rules-gpu' if on_gpu else how, n_partitions=n_part)
   return out, t
 
 
+def bart_parser():
+  """the `bart` sub-command's parser: attach_bart_args (the reference's flags and the splitter choice) and
+  --split-device"""
+  return attach_split_device_arg(attach_bart_args())
+
+
 def bart_console_script(argv=None):
-  _run(bart_main, attach_bart_args().parse_args(argv))
+  _run(bart_main, bart_parser().parse_args(argv))
 
 
 def codebert_console_script(argv=None):

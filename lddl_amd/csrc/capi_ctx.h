@@ -72,6 +72,7 @@ enum PackWs {
   PW_MARENA,       // masking: the arena of masked entries
   PW_MCAND,        // masking: per partition, MLM_MAX_SEQ candidate positions
   PW_FS_DENSE,     // per filtered sentence: its offset in the tokenizer's dense ids
+  PW_SPAN,         // per binned position: the row's SpanRec, streamed by lddl_row_spans
   PW_COUNT
 };
 

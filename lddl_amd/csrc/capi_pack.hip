@@ -141,7 +141,7 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
       (rc = ws_get(k->ws, PW_BIN_COUNT, (size_t)n_part * nbins, &P.bin_count)) ||
       (rc = ws_get(k->ws, PW_BIN_CURSOR, (size_t)n_part * nbins, &P.bin_cursor)) ||
       (rc = ws_get(k->ws, PW_PART_ERR, n_part, &P.part_err)) || (rc = ws_get(k->ws, PW_KEPT, n_sent + n_part + 1, &P.kept)) ||
-      (rc = ws_get(k->ws, PW_FS_DENSE, n_sent, &P.fs_dense)))
+      (rc = ws_get(k->ws, PW_FS_DENSE, n_sent, &P.fs_dense)) || (rc = ws_get(k->ws, PW_SPAN, npair_cap, &P.span)))
     return rc;
   {
     uint32_t* mts;
@@ -382,6 +382,7 @@ extern "C" int lddl_row_spans(lddl_ctx* c, lddl_pack* pk, int64_t* d_out_src0, i
         (rc = ws_get(c, CW_PART_PB, (size_t)P.n_part, &part_pb)))
       return rc;
     HIP_TRY(launch_chunk_parts(M.V.pair_base, P.doc_sent_off, P.part_doc_off, P.dup, P.n_part, chunk_part, part_pb, st));
+    M.span = P.span;
     M.chunk_part = chunk_part;
     M.part_pb = part_pb;
     HIP_TRY(launch_row_spans(M, k->last_npairs, st));

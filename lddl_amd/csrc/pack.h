@@ -18,6 +18,17 @@ struct PairRec {
 };
 static_assert(sizeof(PairRec) == 32, "PairRec is 32 B");
 
+// A row as lddl_row_spans describes it: its two runs of the dense ids.  The
+// wave packers' last binning pass stores one per binned position (pb + i, as
+// binned[]); pack_row.h's span_rec derives it from the row's PairRec.
+struct SpanRec {
+  int64_t src0, src1;   // dense-id offset of segment 0 / 1 (0 when empty)
+  uint16_t len0, len1;
+  uint16_t flags;       // PairRec's
+  uint16_t num_tokens;
+};
+static_assert(sizeof(SpanRec) == 24, "SpanRec is 24 B");
+
 enum : int32_t { PACK_OK = 0, PACK_EASSERT = 1, PACK_EINDEX = 2, PACK_ELIMIT = 3 };
 
 struct PackParams {
@@ -48,7 +59,8 @@ struct PackParams {
   int32_t* order;               // [dup * n_sent]
   int32_t* binned;              // [dup * n_sent]
   int64_t* tok_local;           // [dup * n_sent]
-  int64_t* part_npairs;         // [n_part]
+  SpanRec* span;                // [dup * n_sent] per binned position: the row's spans (bin_pairs)
+  int64_t* part_npairs;        // [n_part]
   int64_t* part_ntok;           // [n_part]
   int64_t* bin_count;           // [n_part * nbins]
   int64_t* bin_cursor;          // [n_part * nbins] scratch (nbins > 16)
@@ -119,7 +131,8 @@ struct MlmParams {
 struct MatParams {
   PackView V;
   const uint16_t* dense;        // the tokenizer's dense ids (sentence s at tokoff[s])
-  const int32_t* chunk_part;    // row spans: partition of row 64c, per 64-row chunk c (chunk_parts_kernel)
+  const SpanRec* span;          // row spans: the packer's row table, per binned position
+  const int32_t* chunk_part;   // row spans: partition of row 64c, per 64-row chunk c (chunk_parts_kernel)
   const int64_t* part_pb;       // row spans: dup * first sentence of partition p (its pair arrays' base)
   uint32_t cls_id, sep_id;
   // outputs, global final order (partition-major, bin-major, shuffled)

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void materialize_kernel(MatParams M) {
         const RowDesc x = row_desc(V, r);
         st[wv][lane] = x;
         st_off[wv][lane] = off;
-        store_row_meta(M, g, p, r, x, total, [&] { return off; });
+        store_row_meta(M, g, p, r.flags, x, total, [&] { return off; });
       }
       wave_sync();
       const int nr = (int)min((int64_t)64, np - c);
@@ -296,7 +296,7 @@ __global__ __launch_bounds__(256) void materialize2_kernel(MatParams M, int64_t 
     off = row_tok_off(V, p, w);
     x = row_desc(V, r);
     rend = off + x.nt;
-    store_row_meta(M, g, p, r, x, total, [&] { return off; });
+    store_row_meta(M, g, p, r.flags, x, total, [&] { return off; });
   }
   const int64_t G0 = __shfl(off, 0), G1 = __shfl(rend, nr - 1);
   W.roff[lane] = lane < nr ? (int32_t)(off - G0) : 0x7FFFFFFF;
@@ -311,9 +311,10 @@ __global__ __launch_bounds__(256) void materialize2_kernel(MatParams M, int64_t 
 // of consecutive sentences), so row g = [CLS] ids[src0, src0 + len0) [SEP]
 // ids[src1, src1 + len1) [SEP] is fully described by two offsets; the string
 // columns (lddl_render_strings, RENDER_SPAN) and the loaders read the ids
-// through them.  Wave per 64 rows, lane per row: the same metadata chain as
-// materialize2 (partition, binned record, pair record, segment starts) and
-// ~38 B written per row instead of the row's 2 B per token.
+// through them.  The packer left each row's SpanRec at its binned position
+// (pack_wave.hip bin_pairs), in file order within a partition, so this is a
+// stream: ~32 B read and ~38 B written per row, no load that depends on
+// another row-sized load.
 // Per partition p: part_pb[p] and the 64-row chunks whose first row is p's
 // (chunk_part), so a row-spans wave finds its partition with one load instead
 // of a binary search over pair_base (15 dependent loads per wave).
@@ -335,22 +336,16 @@ hipError_t launch_chunk_parts(const int64_t* pair_base, const int64_t* doc_sent_
   return hipGetLastError();
 }
 
-// (XCD-aware blocks, as materialize2: a partition's rows run on one XCD, so
-// its pair records and binned order are fetched into one L2, not all eight;
-// against blocks in plain order 3.35 vs 3.53 ms per launch,
-// profiles/r5_rowspan_xcd.txt)
-// RS_U consecutive 64-row chunks per wave, each metadata level loaded for all
-// of them before the next: a row's chain (partition -> bases -> binned
-// index -> pair record -> segment offsets) is ~6 dependent loads, and
-// RS_U chains in flight per wave instead of one (1 / 2 / 4 chunks: 3.32 /
-// 2.99 / 2.99 ms per launch, profiles/r6/rowspan_u/)
+// RS_U consecutive 64-row chunks per wave, lane per row: every chunk's
+// partition (the per-partition tables are a few KB, L2-resident), then every
+// chunk's table record and token offset are loaded before the first store
 constexpr int RS_U = 2;
 __global__ __launch_bounds__(256) void rowspan_kernel(MatParams M, int64_t total) {
   const PackView& V = M.V;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int64_t gbase = (xcd_block(blockIdx.x, gridDim.x) * 4 + wv) * 64 * RS_U;
+  const int64_t gbase = ((int64_t)blockIdx.x * 4 + wv) * 64 * RS_U;
   if (gbase >= total) return;
-  int64_t g[RS_U], p[RS_U];
+  int64_t g[RS_U], p[RS_U], at[RS_U];
   bool in[RS_U];
 #pragma unroll
   for (int u = 0; u < RS_U; ++u) {
@@ -358,31 +353,30 @@ __global__ __launch_bounds__(256) void rowspan_kernel(MatParams M, int64_t total
     in[u] = g[u] < total;
     p[u] = in[u] ? M.chunk_part[(gbase >> 6) + u] : 0;
   }
-  RowRef w[RS_U];  // (pb from chunk_parts_kernel's table: one load, not part_first_pair's two)
 #pragma unroll
   for (int u = 0; u < RS_U; ++u) {
     if (in[u]) p[u] = part_walk(V, p[u], g[u]);
-    w[u].i = in[u] ? g[u] - V.pair_base[p[u]] : 0;
-    w[u].pb = in[u] ? M.part_pb[p[u]] : 0;
+    at[u] = in[u] ? M.part_pb[p[u]] + (g[u] - V.pair_base[p[u]]) : 0;  // (a lane past the end reads record 0)
   }
+  SpanRec t[RS_U];
+  int64_t off[RS_U];
 #pragma unroll
-  for (int u = 0; u < RS_U; ++u) w[u].rec = in[u] ? row_rec(V, w[u].pb, w[u].i) : 0;
-  PairRec r[RS_U];
+  for (int u = 0; u < RS_U; ++u) t[u] = M.span[at[u]];
+  if (M.out_tok_off) {
 #pragma unroll
-  for (int u = 0; u < RS_U; ++u) r[u] = V.pairs[w[u].rec];
+    for (int u = 0; u < RS_U; ++u) off[u] = V.tok_base[p[u]] + V.tok_local[at[u]];
+  }
 #pragma unroll
   for (int u = 0; u < RS_U; ++u) {
     if (!in[u]) continue;
-    const RowDesc x = row_desc(V, r[u]);
-    M.out_src0[g[u]] = x.src0;
-    M.out_src1[g[u]] = x.src1;
-    store_row_meta(M, g[u], p[u], r[u], x, total, [&] { return row_tok_off(V, p[u], w[u]); });
+    M.out_src0[g[u]] = t[u].src0;
+    M.out_src1[g[u]] = t[u].src1;
+    store_row_meta(M, g[u], p[u], t[u].flags, row_desc(t[u]), total, [&] { return off[u]; });
   }
 }
 
 hipError_t launch_row_spans(const MatParams& M, int64_t total_pairs, hipStream_t s) {
-  int64_t nblk = (total_pairs + 256 * RS_U - 1) / (256 * RS_U);
-  if (nblk >= 64) nblk = (nblk + 7) & ~(int64_t)7;  // xcd_block: 8 equal ranges (extra blocks exit)
+  const int64_t nblk = (total_pairs + 256 * RS_U - 1) / (256 * RS_U);
   hipLaunchKernelGGL(rowspan_kernel, dim3((unsigned)nblk), dim3(256), 0, s, M, total_pairs);
   return hipGetLastError();
 }

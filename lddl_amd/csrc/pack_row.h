@@ -5,8 +5,9 @@
 // (materialize, materialize2, row spans, the two masked-LM kernels),
 // pack_wave.hip (bin_of) and render.hip (row_docs_kernel).  Every function is
 // one level of the dependent-load chain partition -> bases -> binned index ->
-// record -> segment starts, so a kernel that keeps several rows' chains in
-// flight (rowspan_kernel) calls them level by level.
+// record -> segment starts.  The wave packers resolve that chain once, while
+// a partition's records are hot, into a SpanRec per binned position
+// (span_rec): lddl_row_spans streams those.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,22 +85,39 @@ struct RowDesc {
   int32_t l0, b1, l1, nt;   // |A|, first position of B, |B|, row length
 };
 
-__device__ __forceinline__ RowDesc row_desc(const PackView& V, const PairRec& r) {
-  RowDesc x;
-  x.l0 = r.hi0 - r.lo0;
-  x.l1 = r.hi1 - r.lo1;
-  x.src0 = x.l0 > 0 ? V.fs_dense[r.fs0] + r.lo0 : 0;
-  x.src1 = x.l1 > 0 ? V.fs_dense[r.fs1] + r.lo1 : 0;
-  x.b1 = 1 + x.l0 + ((r.flags & 2) != 0);  // (bit 1: a [SEP] follows segment 0)
-  x.nt = r.num_tokens;
+// the two runs of record r, d0 / d1 = fs_dense[r.fs0] / fs_dense[r.fs1]: the
+// one place a record's windows become offsets into the dense ids
+__device__ __forceinline__ SpanRec span_rec(const PairRec& r, int64_t d0, int64_t d1) {
+  SpanRec x;
+  x.len0 = (uint16_t)(r.hi0 - r.lo0);
+  x.len1 = (uint16_t)(r.hi1 - r.lo1);
+  x.src0 = x.len0 > 0 ? d0 + r.lo0 : 0;
+  x.src1 = x.len1 > 0 ? d1 + r.lo1 : 0;
+  x.flags = r.flags;
+  x.num_tokens = r.num_tokens;
   return x;
+}
+
+__device__ __forceinline__ RowDesc row_desc(const SpanRec& t) {
+  RowDesc x;
+  x.l0 = t.len0;
+  x.l1 = t.len1;
+  x.src0 = t.src0;
+  x.src1 = t.src1;
+  x.b1 = 1 + x.l0 + ((t.flags & 2) != 0);  // (bit 1: a [SEP] follows segment 0)
+  x.nt = t.num_tokens;
+  return x;
+}
+
+__device__ __forceinline__ RowDesc row_desc(const PackView& V, const PairRec& r) {
+  return row_desc(span_rec(r, V.fs_dense[r.fs0], V.fs_dense[r.fs1]));
 }
 
 // the per-row outputs of materialize / row spans; out_tok_off is optional
 // (lddl_row_spans): tok_off() is asked for the row's offset only when it is
 // wanted, and the last row writes the total behind it
 template <class TokOff>
-__device__ __forceinline__ void store_row_meta(const MatParams& M, int64_t g, int64_t p, const PairRec& r,
+__device__ __forceinline__ void store_row_meta(const MatParams& M, int64_t g, int64_t p, uint32_t flags,
                                                const RowDesc& x, int64_t total, TokOff tok_off) {
   if (M.out_tok_off) {
     const int64_t off = tok_off();
@@ -108,7 +126,7 @@ __device__ __forceinline__ void store_row_meta(const MatParams& M, int64_t g, in
   }
   M.out_len0[g] = (uint16_t)x.l0;
   M.out_len1[g] = (uint16_t)x.l1;
-  M.out_flags[g] = (uint8_t)r.flags;
+  M.out_flags[g] = (uint8_t)flags;
   M.out_bin[g] = (uint8_t)bin_of(x.nt, M.V.bin_size, M.V.nbins);
   M.out_part[g] = p;
 }

@@ -609,7 +609,11 @@ __device__ __forceinline__ void shuffle_pairs(const PackParams& P, const PartOpe
 //            num_tokens still packed in
 //   offsets  one linear pass over binned: a wave scan of num_tokens per 64
 //            rows gives tok_local (MASK: a second one over mref >> 48 gives
-//            mloc), and the packed words are cut down to the record index
+//            mloc), and the packed words are cut down to the record index.
+//            The pass visits the rows in file order with their records still
+//            in this XCD's L2, so it also gathers each row's record and
+//            sentence starts and stores the row table lddl_row_spans streams
+//            (span[pb + i], 64 rows per coalesced store)
 // One bin is the offsets pass alone, over the order; more than 64 bins take
 // one filtering pass per bin.
 template <int MASK, bool LDSOK>
@@ -630,6 +634,7 @@ __device__ __forceinline__ void bin_pairs(const PackParams& P, const PartOpen& O
   const int nb = P.nbins;
   int32_t* binned = P.binned + pb;
   int64_t* tl = P.tok_local + pb;
+  SpanRec* span = P.span + pb;
   int64_t acc = 0, macc = 0;
   if (bins_by_lane(nb)) {
     const int cnt = lane < nb ? (int)P.bin_count[p * nb + lane] : 0;
@@ -652,14 +657,20 @@ __device__ __forceinline__ void bin_pairs(const PackParams& P, const PartOpen& O
       const bool in = kk < np;
       const int w = in ? binned[kk] : 0;
       const int rec = rec_of(w);
+      // the row's record and its two sentence starts (a lane past the end
+      // reads record 0's), all loaded before the step's first store
+      const PairRec r = out[rec];
+      const int64_t d0 = P.fs_dense[r.fs0], d1 = P.fs_dense[r.fs1];
+      int nmk = 0;
+      if constexpr (MASK) nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
       const int nt = in ? ntk_of(w) : 0;
       const int tinc = wave_incl_add(nt);
       if (in) {
         if (packed) binned[kk] = rec;
         tl[kk] = acc + tinc - nt;
+        span[kk] = span_rec(r, d0, d1);
       }
       if constexpr (MASK) {
-        const int nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
         const int minc = wave_incl_add(nmk);
         if (in) P.mloc[pb + kk] = macc + minc - nmk;
         macc += lane_get(minc, 63);
@@ -680,15 +691,24 @@ __device__ __forceinline__ void bin_pairs(const PackParams& P, const PartOpen& O
           nt = ntk_of(w);
           in = nb == 1 || bin_of(nt, P.bin_size, nb) == b;
         }
+        PairRec r{};
+        int64_t d0 = 0, d1 = 0;
+        int nmk = 0;
+        if (in) {  // (as above: the loads before the step's stores)
+          r = out[rec];
+          d0 = P.fs_dense[r.fs0];
+          d1 = P.fs_dense[r.fs1];
+          if constexpr (MASK) nmk = (int)((uint64_t)P.mref[pb + rec] >> 48);
+        }
         const uint64_t m = __ballot(in);
         const int before = bits_below(m);
         const int tinc = wave_incl_add(in ? nt : 0);
         if (in) {
           binned[pos + before] = rec;
           tl[pos + before] = acc + tinc - nt;
+          span[pos + before] = span_rec(r, d0, d1);
         }
         if constexpr (MASK) {
-          const int nmk = in ? (int)((uint64_t)P.mref[pb + rec] >> 48) : 0;
           const int minc = wave_incl_add(nmk);
           if (in) P.mloc[pb + pos + before] = macc + minc - nmk;
           macc += lane_get(minc, 63);

@@ -329,6 +329,36 @@ int lddl_mask_tokens(lddl_ctx *ctx, int64_t *d_inputs, const int64_t *d_special_
                      int64_t n_rows, int64_t seq_len, double mlm_probability, int64_t ignore_index, uint64_t seed,
                      uint64_t counter, void *stream);
 
+/* Whole-word dynamic masking (BERT-WWM): with on != 0, lddl_mask_tokens and
+ * mode 2 of every collate call of the ctx (lddl_collate_bert,
+ * lddl_collate_rows[_unpadded], lddl_collate_code_rows[_unpadded]) select
+ * words instead of tokens.  Off by default; modes 0 and 1 ignore it; a
+ * vocabulary without "##" entries is accepted (every token is then a word).
+ * The reference has no counterpart.  For one row, with id_j the unmasked id
+ * of column j, V the vocabulary size and special(j) what the call uses
+ * without the switch ([CLS], each [SEP] and the padding in the collates, the
+ * caller's special_tokens_mask in lddl_mask_tokens):
+ *   cont(id)   iff 0 <= id < V and vocabulary entry id begins with the two
+ *              bytes "##" (ids outside [0, V), which only lddl_mask_tokens can
+ *              meet, are no continuations)
+ *   start(j)   iff !special(j) and (j == 0 or special(j - 1) or !cont(id_j)):
+ *              a segment's first token starts a word even when it is a "##"
+ *              piece (_truncate_seq_pair can leave one there), and a word
+ *              never crosses a [SEP]
+ *   head(j)    for a non-special j: the largest h <= j with start(h)
+ *   selected   iff !special(j) and unit(sm(k + i(row, head(j)))) <
+ *              mlm_probability: lddl_mask_tokens' select draw taken at the
+ *              word's head column, k and i as there
+ *   a selected j has label id_j and its own second and third draws
+ *   (i(row, j) + 1, + 2) decide [MASK] / random id / kept, unchanged; an
+ *   unselected j keeps its id and has label ignore_index.
+ * row and column are what they are without the switch (on the padding-free
+ * calls the column is the token's position in its row).  A row in which every
+ * token heads its own word is masked bit for bit as without the switch, and
+ * a token is selected with probability mlm_probability either way.
+ * tests/wwm_model.py is this in numpy. */
+int lddl_set_whole_word_mask(lddl_ctx *ctx, int on);
+
 /* ---- collate straight from a pack result ---------------------------------
  * The same lddl/torch/bert.py:69-153 `_to_encoded_inputs` (+ :156-196
  * `_mask_tokens`) for rows that never became parquet: batch row r is row

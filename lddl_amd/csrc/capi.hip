@@ -34,6 +34,7 @@ static void free_ctx(lddl_ctx* c) {
   (void)hipFree(c->d_voff);
   (void)hipFree(c->d_rpool);
   (void)hipFree(c->d_rinfo);
+  (void)hipFree(c->d_cont);
   (void)hipFree(c->d_vt);
   (void)hipFree(c->d_vbloom);
   (void)hipFree(c->d_ovf);
@@ -91,6 +92,10 @@ static int load_vocab(lddl_ctx* c, const char* path) {
   if ((rc = upload(&c->d_voff, V.voff.data(), V.voff.size() * 4))) return rc;
   if ((rc = upload(&c->d_rpool, V.rpool.data(), V.rpool.size()))) return rc;
   if ((rc = upload(&c->d_rinfo, V.rinfo.data(), V.rinfo.size() * 4))) return rc;
+  std::vector<uint32_t> cont((V.vocab.size() + 31) / 32, 0u);
+  for (size_t i = 0; i < V.vocab.size(); ++i)
+    if (V.vocab[i].compare(0, 2, "##") == 0) cont[i >> 5] |= 1u << (i & 31);
+  if ((rc = upload(&c->d_cont, cont.data(), cont.size() * 4))) return rc;
   c->vocab = std::move(V.vocab);
   return 0;
 }
@@ -163,6 +168,12 @@ extern "C" int lddl_vocab_token(const lddl_ctx* c, int32_t id, char* buf, int64_
 extern "C" int lddl_set_special_flags(lddl_ctx* c, int on) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   c->spec_flags = on != 0;
+  return 0;
+}
+
+extern "C" int lddl_set_whole_word_mask(lddl_ctx* c, int on) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  c->whole_word = on != 0;
   return 0;
 }
 

@@ -98,6 +98,7 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
   P.mlm_probability = mlm_probability;
   P.seed = seed;
   P.counter = counter;
+  P.cont = c->whole_word ? c->d_cont : nullptr;  // picks the whole-word instantiation of mode 2
   P.input_ids = d_input_ids;
   P.token_type_ids = d_token_type_ids;
   P.attention_mask = d_attention_mask;
@@ -144,6 +145,7 @@ extern "C" int lddl_mask_tokens(lddl_ctx* c, int64_t* d_inputs, const int64_t* d
   M.mlm_probability = mlm_probability;
   M.seed = seed;
   M.counter = counter;
+  M.cont = c->whole_word ? c->d_cont : nullptr;  // picks the wave-per-row kernel
   HIP_TRY(launch_mask_tokens(M, c->n_cu, (hipStream_t)stream));
   return 0;
 }
@@ -280,6 +282,7 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
   P.mlm_probability = mlm_probability;
   P.seed = seed;
   P.counter = counter;
+  P.cont = c->whole_word ? c->d_cont : nullptr;  // picks the whole-word instantiation of mode 2
   P.input_ids = d_input_ids;
   P.token_type_ids = d_token_type_ids;
   P.attention_mask = d_attention_mask;

@@ -179,6 +179,8 @@ struct lddl_ctx {
   uint32_t* d_voff = nullptr;
   uint8_t* d_rpool = nullptr;    // full vocab strings (incl. "##"), 4-aligned: rendering
   uint32_t* d_rinfo = nullptr;   // [V] offset << 8 | length into d_rpool
+  uint32_t* d_cont = nullptr;    // [(V + 31) / 32] bit id: entry id begins with "##" (whole-word masking)
+  bool whole_word = false;       // lddl_set_whole_word_mask
   uint32_t maxb[2] = {0, 0};
   uint4* d_vt = nullptr;         // v4 bucketed vocab table
   uint32_t vt_mask = 0;

@@ -43,6 +43,7 @@ struct CollateParams {
   int64_t ignore_index;
   double mlm_probability;
   uint64_t seed, counter;
+  const uint32_t* cont;      // whole-word masking (mode 2 with lddl_set_whole_word_mask on): bit id = entry id begins with "##"; else NULL
   int64_t* input_ids;        // [n_rows, seq_len]
   int64_t* token_type_ids;
   int64_t* attention_mask;
@@ -61,6 +62,7 @@ struct MaskParams {
   int64_t ignore_index;
   double mlm_probability;
   uint64_t seed, counter;
+  const uint32_t* cont;       // whole-word masking: as CollateParams::cont, over n_random entries; else NULL
 };
 
 // lddl_collate_rows_seq_len / lddl_collate_rows: batch row r is row
@@ -86,6 +88,7 @@ struct CollateRowsParams {
   int64_t ignore_index;
   double mlm_probability;
   uint64_t seed, counter;
+  const uint32_t* cont;      // whole-word masking: as CollateParams::cont, over n_random entries; else NULL
   int64_t* input_ids;        // [n_rows, seq_len]
   int64_t* token_type_ids;
   int64_t* attention_mask;

@@ -26,21 +26,77 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
 
 __device__ __forceinline__ double unit53(uint64_t h) { return (double)(h >> 11) * (1.0 / 9007199254740992.0); }
 
-// _mask_tokens for one column: returns the (possibly replaced) input id and
-// sets label
-__device__ __forceinline__ int64_t mask_one(int64_t id, bool special, int64_t row, int32_t col, uint64_t seed,
-                                            uint64_t counter, double p, int32_t mask_id, int32_t n_random,
-                                            int64_t ignore, int64_t& label) {
-  const uint64_t k = splitmix64(seed ^ splitmix64(counter));
-  const uint64_t idx = ((uint64_t)row << 20 | (uint64_t)col) * 3ull;
+// the three draws of (row, col) are the hashes of k + idx, + 1 and + 2
+__device__ __forceinline__ uint64_t mask_key(uint64_t seed, uint64_t counter) {
+  return splitmix64(seed ^ splitmix64(counter));
+}
+__device__ __forceinline__ uint64_t mask_idx(int64_t row, int32_t col) {
+  return ((uint64_t)row << 20 | (uint64_t)col) * 3ull;
+}
+
+// _mask_tokens for one column whose select draw is taken at column sel of its
+// row and whose replacement draws are its own: returns the (possibly replaced)
+// input id and sets label
+__device__ __forceinline__ int64_t mask_one_at(int64_t id, bool special, int64_t row, int32_t col, int32_t sel,
+                                               uint64_t seed, uint64_t counter, double p, int32_t mask_id,
+                                               int32_t n_random, int64_t ignore, int64_t& label) {
+  const uint64_t k = mask_key(seed, counter);
   label = ignore;
-  if (special || !(unit53(splitmix64(k + idx)) < p)) return id;
+  if (special || !(unit53(splitmix64(k + mask_idx(row, sel))) < p)) return id;
   label = id;
+  const uint64_t idx = mask_idx(row, col);
   const uint64_t h = splitmix64(k + idx + 1);
   if (unit53(h) < 0.8) return mask_id;
   const uint64_t g = splitmix64(k + idx + 2);
   if (unit53(g) < 0.5) return (int64_t)(((g & 0xFFFFFFFFull) * (uint64_t)n_random) >> 32);
   return id;
+}
+
+// _mask_tokens for one column: every column selects for itself
+__device__ __forceinline__ int64_t mask_one(int64_t id, bool special, int64_t row, int32_t col, uint64_t seed,
+                                            uint64_t counter, double p, int32_t mask_id, int32_t n_random,
+                                            int64_t ignore, int64_t& label) {
+  return mask_one_at(id, special, row, col, col, seed, counter, p, mask_id, n_random, ignore, label);
+}
+
+// ------------------------------------------------------ whole-word masking --
+// cont(id): vocabulary entry id begins with "##" (bit id of the ctx's table;
+// an id outside [0, n_vocab) is no continuation)
+__device__ __forceinline__ bool word_cont(const uint32_t* bits, int32_t n_vocab, int64_t id) {
+  return (uint64_t)id < (uint64_t)n_vocab && ((bits[id >> 5] >> (id & 31)) & 1u);
+}
+
+// The head of every column of one step of a row: the last column at or before
+// it where a word starts.  A step is W * 64 columns, lane l owns columns
+// base + W * l + k (k < W) and says in st[k] whether a word starts there
+// (false on a column that is not the row's).  head[k] is the highest start at
+// or below the lane's column k, from the ballots of the step; without one,
+// carry: the last start of the row's earlier steps (-1 before the first; the
+// caller sets it so for every row).  carry is wave-uniform and moves on to the
+// step's last start.  Registers and scalars only.  Every lane of the wave
+// calls it.
+template <int W>
+__device__ __forceinline__ void word_heads(int32_t base, const bool (&st)[W], int32_t& carry, int32_t (&head)[W]) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t upto = (2ull << lane) - 1ull;  // the lanes at or below this one
+  uint64_t m[W];
+#pragma unroll
+  for (int t = 0; t < W; ++t) m[t] = __ballot(st[t]);
+  int32_t last = carry;
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    head[k] = carry;
+#pragma unroll
+    for (int t = 0; t < W; ++t) {
+      // sub-column t of a lane is at or before sub-column k of this one: the lanes below, and this one when t <= k
+      const uint64_t b = m[t] & (t <= k ? upto : upto >> 1);
+      if (b) head[k] = max(head[k], base + W * (63 - __clzll((long long)b)) + t);
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < W; ++t)
+    if (m[t]) last = max(last, base + W * (63 - __clzll((long long)m[t])) + t);
+  carry = last;
 }
 
 static constexpr uint32_t kEmpty = 0xFFFFFFFFu;

@@ -145,6 +145,38 @@ __device__ __forceinline__ RowColumn row_column(const CollateRowsParams& P, cons
   return o;
 }
 
+// Whole-word masking (mode 2, P.cont set): a column in two halves, with
+// word_heads (collate_dev.h) over the start flags of the step between them.
+struct WordColumn {
+  int64_t id;    // the unmasked id (0 where !valid or pad)
+  bool special;  // never selected: a special token, a pad column, or not a column of the row
+  bool start;    // a word starts here
+};
+
+// valid: j is a column of the batch row (the wide paths compute a neighbour
+// that is not); pad as in row_column
+__device__ __forceinline__ WordColumn word_column(const CollateRowsParams& P, const OpenRow& R, int32_t j, bool valid,
+                                                  bool pad) {
+  WordColumn c;
+  c.special = !valid || pad || R.L.special(j);
+  c.id = 0;
+  if (valid && !pad)
+    c.id = R.L.base_id(j, P.cls, P.sep, [&](int32_t k) { return (int32_t)(k <= R.L.a ? R.s0[k] : R.s1[k]); });
+  // j - 1 is special exactly where j begins a segment: no column is in front of [CLS]
+  c.start = !c.special && (R.L.special(j - 1) || !word_cont(P.cont, P.n_random, c.id));
+  return c;
+}
+
+// row_column<COLLATE_DYNAMIC> of a column whose word starts at column head
+__device__ __forceinline__ RowColumn row_column_word(const CollateRowsParams& P, const OpenRow& R, int64_t r, int32_t j,
+                                                     const WordColumn& c, int32_t head) {
+  RowColumn o;
+  o.id = mask_one_at(c.id, c.special, r, j, head, P.seed, P.counter, P.mlm_probability, P.mask_id, P.n_random,
+                     P.ignore_index, o.lab);
+  o.tt = R.L.token_type(j);
+  return o;
+}
+
 // ------------------------------------------------ the chunked offsets scan --
 // An exclusive scan of N per-row quantities over any number of rows, in two
 // levels.  Level one is each caller's own: chunk c's sums of its kChunk rows

@@ -104,9 +104,13 @@ __global__ __launch_bounds__(256) void collate_cu_scan_kernel(CollateUnpaddedPar
 
 }  // namespace
 
-template <int MODE, bool CODE>
+// WWM (mode 2 only): whole-word masking, as in collate_rows_kernel.  A step of
+// the wide path is the 128 tokens of 64 aligned pairs, the first of them -1
+// (not a token of the row) when the row starts at an odd offset.
+template <int MODE, bool CODE, bool WWM = false>
 __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedParams P) {
   static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
+  static_assert(!WWM || MODE == COLLATE_DYNAMIC, "whole-word masking is dynamic masking");
   // mode 1 only: per wave, label | token << 16 of every masked token
   __shared__ uint32_t s_mlm[MODE == COLLATE_STATIC ? 4 : 1][MODE == COLLATE_STATIC ? COLLATE_MAX_LEN : 1];
   const CollateRowsParams& R = P.R;
@@ -138,7 +142,51 @@ __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedPa
     int64_t* o_tt = R.token_type_ids + c0;
     int64_t* o_pos = P.position_ids + c0;
     int64_t* o_lab = R.labels + c0;
-    if (wide) {
+    if constexpr (WWM) {
+      int32_t carry = -1;
+      if (wide) {
+        const int32_t head = (int32_t)(c0 & 1);
+        const int32_t nq = (head + n + 1) >> 1;
+        for (int32_t qb = 0; qb < nq; qb += 64) {
+          const int32_t q = qb + lane;
+          const int32_t j0 = 2 * q - head, j1 = j0 + 1;
+          const bool v0 = q < nq && j0 >= 0, v1 = q < nq && j1 < n;
+          const WordColumn w0 = word_column(R, S, j0, v0, false);
+          const WordColumn w1 = word_column(R, S, j1, v1, false);
+          int32_t wh[2];
+          word_heads<2>(2 * qb - head, {w0.start, w1.start}, carry, wh);
+          const RowColumn t0 = row_column_word(R, S, r, j0, w0, wh[0]);
+          const RowColumn t1 = row_column_word(R, S, r, j1, w1, wh[1]);
+          if (v0 && v1) {
+            *reinterpret_cast<longlong2*>(o_ids + j0) = make_longlong2(t0.id, t1.id);
+            *reinterpret_cast<longlong2*>(o_tt + j0) = make_longlong2(t0.tt, t1.tt);
+            *reinterpret_cast<longlong2*>(o_pos + j0) = make_longlong2(j0, j1);
+            *reinterpret_cast<longlong2*>(o_lab + j0) = make_longlong2(t0.lab, t1.lab);
+          } else if (v0 || v1) {
+            const RowColumn t = v0 ? t0 : t1;
+            const int32_t k = v0 ? j0 : j1;
+            o_ids[k] = t.id;
+            o_tt[k] = t.tt;
+            o_pos[k] = k;
+            o_lab[k] = t.lab;
+          }
+        }
+      } else {
+        for (int32_t base = 0; base < n; base += 64) {
+          const int32_t j = base + lane;
+          const WordColumn w0 = word_column(R, S, j, j < n, false);
+          int32_t wh[1];
+          word_heads<1>(base, {w0.start}, carry, wh);
+          if (j < n) {
+            const RowColumn t = row_column_word(R, S, r, j, w0, wh[0]);
+            o_ids[j] = t.id;
+            o_tt[j] = t.tt;
+            o_pos[j] = j;
+            o_lab[j] = t.lab;
+          }
+        }
+      }
+    } else if (wide) {
       // pair q holds tokens 2q - head and 2q - head + 1: 16-B aligned in the
       // stream.  The first pair of an odd start and the last of an odd end have
       // one token of this row (n >= 2: never the same pair, never neither).
@@ -193,7 +241,10 @@ hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, 
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.R.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.R.n_rows, n_cu)), block(256);
-  if (code) {
+  if (mode == COLLATE_DYNAMIC && P.R.cont) {
+    if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, true>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, true>), grid, block, 0, s, P);
+  } else if (code) {
     dispatch_code_mode(mode, [&](auto m) {
       hipLaunchKernelGGL((collate_unpadded_kernel<decltype(m)::value, true>), grid, block, 0, s, P);
     });

@@ -228,10 +228,20 @@ class _RowCollate:
   VOCAB = _lib.VOCAB_BERT
 
   def __init__(self, vocab_file=None, device=None, sequence_length_alignment=8, ignore_index=-1,
-               mlm_probability=0.15, base_seed=12345, tokenizer=None):
+               mlm_probability=0.15, base_seed=12345, tokenizer=None, whole_word_mask=False):
+    """whole_word_mask: dynamic masking (mode 2 and ``mask_tokens``) selects
+    words, not tokens: a piece and the ``##`` pieces after it are masked
+    together (lddl_set_whole_word_mask; include/lddl_amd.h defines it).  The
+    switch lives on the tokenizer's ctx and is set here, on or off: with
+    ``tokenizer=`` a shared ctx, every collate over that ctx follows the one
+    constructed last."""
     assert isinstance(sequence_length_alignment, int) and sequence_length_alignment >= 1
     assert isinstance(mlm_probability, (int, float)) and 0 <= mlm_probability <= 1
     self.tok = tokenizer if tokenizer is not None else Tokenizer(vocab_file or self.VOCAB, device)
+    self.whole_word_mask = bool(whole_word_mask)
+    L = _lib.lib()
+    if self.whole_word_mask or hasattr(L, 'lddl_set_whole_word_mask'):  # (an A/B library of an older revision lacks it)
+      _lib.check(L.lddl_set_whole_word_mask(self.tok.handle, 1 if self.whole_word_mask else 0))
     self.device = self.tok.device
     self.sequence_length_alignment = sequence_length_alignment
     self.ignore_index = int(ignore_index)

@@ -90,6 +90,7 @@ def main():
   ap.add_argument('--reps', type=int, default=30)
   ap.add_argument('--warmup', type=int, default=5)
   ap.add_argument('--sizes', type=int, nargs='+', default=[256, 8192])
+  ap.add_argument('--whole-word', action='store_true', help='whole-word masking on (lddl_set_whole_word_mask): both routes')
   ap.add_argument('--out')
   a = ap.parse_args()
   assert torch.cuda.is_available(), 'needs a GPU'
@@ -100,13 +101,13 @@ def main():
   sh = pipeline.upload(c, pipeline.partition_by_bytes(c, 4), dev)
   res = pk.run(sh, target_seq_length=512, bin_size=64, duplicate_factor=2, seed=1, spans=True)
   torch.cuda.synchronize()
-  col = BertCollate(tokenizer=pk.tok, sequence_length_alignment=8, base_seed=7)
+  col = BertCollate(tokenizer=pk.tok, sequence_length_alignment=8, base_seed=7, whole_word_mask=a.whole_word)
   L = _lib.lib()
   P = ctypes.c_void_p
   p = lambda t: P(t.data_ptr())  # noqa: E731
   h = pk.tok.handle
   report = {'gpu': torch.cuda.get_device_name(0), 'n_pairs': res.n_pairs, 'corpus_mb': a.mb, 'seq': 512, 'bin': 64,
-            'batches': {}}
+            'whole_word': a.whole_word, 'batches': {}}
   for n in a.sizes:
     assert res.n_pairs >= n, 'corpus too small: %d rows' % res.n_pairs
     idx = torch.from_numpy(np.random.default_rng(n).permutation(res.n_pairs)[:n]).to(dev)

@@ -60,6 +60,7 @@ def main():
   ap.add_argument('--reps', type=int, default=30)
   ap.add_argument('--warmup', type=int, default=5)
   ap.add_argument('--sizes', type=int, nargs='+', default=[256, 8192])
+  ap.add_argument('--whole-word', action='store_true', help='whole-word masking on (lddl_set_whole_word_mask): both calls')
   ap.add_argument('--out')
   a = ap.parse_args()
   assert torch.cuda.is_available(), 'needs a GPU'
@@ -75,8 +76,10 @@ def main():
   p = lambda t: P(t.data_ptr())  # noqa: E731
   h = pk.tok.handle
   st = P(torch.cuda.current_stream().cuda_stream)
+  if a.whole_word:
+    _lib.check(L.lddl_set_whole_word_mask(h, 1))
   report = {'gpu': torch.cuda.get_device_name(0), 'n_pairs': res.n_pairs, 'corpus_mb': a.mb, 'seq': 512, 'bin': 64,
-            'mode': 2, 'batches': {}}
+            'mode': 2, 'whole_word': a.whole_word, 'batches': {}}
 
   def measure(idx):
     n = idx.numel()

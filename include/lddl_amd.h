@@ -534,6 +534,46 @@ int lddl_collate_code_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const 
                                     int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
                                     int64_t *d_labels, void *stream);
 
+/* ---- compact MLM targets ----------------------------------------------------
+ * The masked positions of a batch and their labels, in order: what a trainer
+ * gathers the hidden states at before the LM head, so that the vocabulary
+ * projection and its loss run over the ~15 % of the tokens that are selected.
+ * The static shards carry these lists per row (masked_lm_positions /
+ * masked_lm_labels, scattered by bert.py:113-116); with dynamic masking they
+ * never exist.  d_labels is the int64 [total] labels of any collate call of
+ * this header or of lddl_mask_tokens; its rows are given by one of
+ *   padded   d_cu_seqlens NULL: row r is [r * seq_len, (r + 1) * seq_len),
+ *            total = n_rows * seq_len;
+ *   offsets  d_cu_seqlens int32 [n_rows + 1] on the device: row r is
+ *            [cu[r], cu[r + 1]) inside [0, total); seq_len is not read; an empty
+ *            row (cu[r] == cu[r + 1]) is legal, and tokens of d_labels that lie
+ *            in no row are ignored.
+ * With F the ascending list of the flat indices t that lie inside a row and
+ * have d_labels[t] != ignore_index, and M its length:
+ *   d_positions[k] = F[k], d_target_labels[k] = d_labels[F[k]]   for k < M
+ *   d_positions[k] = 0,    d_target_labels[k] = ignore_index     for M <= k < capacity
+ *   d_offsets[r] = the selected tokens of the rows before r, d_offsets[n_rows] = M
+ * d_positions and d_target_labels are int64 [capacity], d_offsets int32
+ * [n_rows + 1]; labels pass through as 64-bit values.  The padded tail is
+ * harmless to a loss that honours ignore_index and gives fixed shapes.  The
+ * order is fixed: no result depends on the arrival order of an atomic.
+ * Synchronises the stream; *out_count = M on every return that got as far as
+ * counting, a device error included (it is left alone before that).
+ * Errors, first one wins, none faults: LDDL_EINVAL (a NULL ctx, output or
+ * out_count, NULL d_labels with total > 0; n_rows <= 0; ignore_index >= 0, which
+ * could be a label; total or capacity < 0; padded with seq_len < 1 or total !=
+ * n_rows * seq_len), LDDL_ECAPACITY (total or n_rows >= 2^31: d_offsets is
+ * int32), then from the device LDDL_EINVAL (a row with cu[r] < 0,
+ * cu[r + 1] < cu[r] or cu[r + 1] > total: d_cu_seqlens is checked, not trusted;
+ * such a row counts 0 and is never read through, and the three outputs are
+ * unspecified), LDDL_ECAPACITY (M > capacity: the three outputs are
+ * unspecified but never written out of bounds, and *out_count holds M, so the
+ * caller can resize). */
+int lddl_mlm_targets(lddl_ctx *ctx, const int64_t *d_labels, int64_t n_rows, int64_t seq_len,
+                     const int32_t *d_cu_seqlens, int64_t total, int64_t ignore_index, int64_t capacity,
+                     int64_t *d_positions, int64_t *d_target_labels, int32_t *d_offsets, int64_t *out_count,
+                     void *stream);
+
 /* ---- a row table from the shards on disk ----------------------------------
  * The bridge from parquet shards to lddl_collate_rows[_unpadded]: the string
  * columns of a shard (A, B, is_random_next and, with static masking,

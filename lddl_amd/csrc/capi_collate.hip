@@ -1,5 +1,5 @@
 // C-ABI, host side of the training-time collate (kernels: collate.hip,
-// collate_rows.hip, collate_unpadded.hip, rows_from_strings.hip).
+// collate_rows.hip, collate_unpadded.hip, rows_from_strings.hip, mlm_targets.hip).
 #include "capi_ctx.h"
 
 static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
@@ -419,6 +419,60 @@ extern "C" int lddl_collate_code_rows_unpadded(lddl_ctx* c, const uint16_t* d_id
   return collate_rows_common(c, 1, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, nullptr,
                              nullptr, nullptr, nullptr, 0, d_cu_seqlens, total, mode, ignore_index, mlm_probability, seed,
                              counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids, d_labels, nullptr, stream);
+}
+
+// ------------------------------------------------------ compact MLM targets --
+extern "C" int lddl_mlm_targets(lddl_ctx* c, const int64_t* d_labels, int64_t n_rows, int64_t seq_len,
+                                const int32_t* d_cu_seqlens, int64_t total, int64_t ignore_index, int64_t capacity,
+                                int64_t* d_positions, int64_t* d_target_labels, int32_t* d_offsets, int64_t* out_count,
+                                void* stream) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (!d_positions || !d_target_labels || !d_offsets || !out_count) return set_err(LDDL_EINVAL, "null output pointer");
+  if (n_rows <= 0) return set_err(LDDL_EINVAL, "n_rows %lld: a batch has one row at least", (long long)n_rows);
+  if (ignore_index >= 0)
+    return set_err(LDDL_EINVAL, "ignore_index %lld could be a label: it must be negative", (long long)ignore_index);
+  if (total < 0 || capacity < 0) return set_err(LDDL_EINVAL, "negative total / capacity");
+  if (total > 0 && !d_labels) return set_err(LDDL_EINVAL, "null labels");
+  // total / n_rows == seq_len without a product that could overflow
+  if (!d_cu_seqlens && (seq_len < 1 || total % n_rows != 0 || total / n_rows != seq_len))
+    return set_err(LDDL_EINVAL, "a padded batch of %lld rows of %lld columns does not hold %lld labels", (long long)n_rows,
+                   (long long)seq_len, (long long)total);
+  if (total > INT32_MAX || n_rows > INT32_MAX)
+    return set_err(LDDL_ECAPACITY, "total %lld / n_rows %lld: offsets are int32", (long long)total, (long long)n_rows);
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t st = (hipStream_t)stream;
+  MlmTargetsParams P{};
+  P.labels = d_labels;
+  P.cu_seqlens = d_cu_seqlens;
+  P.n_rows = n_rows;
+  P.seq_len = seq_len;
+  P.total = total;
+  P.ignore_index = ignore_index;
+  P.capacity = capacity;
+  P.positions = d_positions;
+  P.target_labels = d_target_labels;
+  P.offsets = d_offsets;
+  P.n_chunks = collate_chunks(n_rows);
+  // one buffer, one memset: M, the error word (the layout of HW_CU_TOTAL, HW_MAX_LEN), then the chunk sums
+  unsigned long long* words;
+  int rc;
+  if ((rc = ws_get(c, CW_SHARED_BSUM, (size_t)P.n_chunks + 2, &words))) return rc;
+  P.count_out = (int64_t*)words;
+  P.err = (uint32_t*)(words + 1);
+  P.chunk_sum = words + 2;
+  HIP_TRY(hipMemsetAsync(words, 0, ((size_t)P.n_chunks + 2) * sizeof(*words), st));
+  HIP_TRY(launch_mlm_targets(P, c->n_cu, st));
+  HIP_TRY(fetch_word(c, HW_CU_TOTAL, words, 16, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const int64_t count = c->h_tot[HW_CU_TOTAL];
+  const uint32_t e = (uint32_t)(c->h_tot[HW_MAX_LEN] & 0xFFFFFFFF);
+  *out_count = count;
+  if (e)
+    return set_err(LDDL_EINVAL, "row %llu: cu_seqlens do not hold a row within [0, total %lld)", (unsigned long long)(e >> 4),
+                   (long long)total);
+  if (count > capacity)
+    return set_err(LDDL_ECAPACITY, "%lld masked positions, capacity %lld", (long long)count, (long long)capacity);
+  return 0;
 }
 
 // ------------------------------------------- a row table from a shard's strings --

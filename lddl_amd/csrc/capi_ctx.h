@@ -92,7 +92,8 @@ enum CtxWs {
   CW_ENT,          // tokenize: the segment's entry / staging buffer
   CW_SHARED_ROWS,  // tokenize: rec, the record slots; lddl_render_strings / _npy / _masked: lens, bytes per row
   CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan;
-                   // lddl_collate_rows_cu_seqlens / lddl_rows_from_strings_len: chunk sums of their scans
+                   // lddl_collate_rows_cu_seqlens / lddl_rows_from_strings_len: chunk sums of their scans;
+                   // lddl_mlm_targets: M, its error word, then the chunk sums of its scan (one memset)
   CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len;
                    // lddl_collate_rows_cu_seqlens: total, max_len; lddl_rows_from_strings_len: its three totals
                    // the lddl_bart_* calls use the three too: ROWS = chunks per document (plan_len) / bytes per chunk
@@ -133,7 +134,8 @@ enum HostWord {
   HW_NMASK,         // lddl_pack_bert (masking): the masked entries; lddl_rows_from_strings_len: the same of the table
   HW_MARENA_USED,   // lddl_pack_bert (masking): the arena entries the bump allocator handed out
   HW_NDENSE,        // lddl_pack_bert / _codebert: the tokenizer's dense ids
-  HW_CU_TOTAL = HW_NDENSE,  // the same word; lddl_collate_rows_cu_seqlens: the batch's tokens (one 16-byte copy with HW_MAX_LEN)
+  HW_CU_TOTAL = HW_NDENSE,  // the same word; lddl_collate_rows_cu_seqlens: the batch's tokens (one 16-byte copy with HW_MAX_LEN);
+                            // lddl_mlm_targets: M, with its error word in HW_MAX_LEN by the same copy
   HW_MAX_LEN,       // lddl_collate_seq_len / lddl_collate_rows_seq_len / lddl_collate_rows_cu_seqlens: the longest row (int32)
   HW_RENDER_BYTES = HW_MAX_LEN,  // the same word; lddl_render_strings / _npy / _masked: the bytes of the rendered column
   HW_ERR,           // lddl_bin, lddl_render_npy, lddl_collate_bert, lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded],

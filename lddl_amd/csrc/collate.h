@@ -144,6 +144,25 @@ struct RowsFromStringsParams {
   uint32_t* err;          // [1] as CollateParams::err
 };
 
+// lddl_mlm_targets (mlm_targets.hip): the ordered compaction of a labels
+// tensor.  Row r is [r * seq_len, (r + 1) * seq_len) (cu_seqlens NULL; the
+// host has checked total = n_rows * seq_len) or [cu_seqlens[r],
+// cu_seqlens[r + 1]) within [0, total), checked on the device.
+struct MlmTargetsParams {
+  const int64_t* labels;      // [total]
+  const int32_t* cu_seqlens;  // [n_rows + 1] or NULL
+  int64_t n_rows, seq_len, total;
+  int64_t ignore_index;       // < 0
+  int64_t capacity;           // entries of positions / target_labels that may be written
+  int64_t* positions;         // [capacity]
+  int64_t* target_labels;     // [capacity]
+  int32_t* offsets;           // [n_rows + 1]: the count pass leaves row r's count in [r + 1], the scan sums in place
+  unsigned long long* chunk_sum;  // [n_chunks] selected tokens of each chunk of rows (zeroed by the host)
+  int64_t* count_out;         // [1] M
+  uint32_t* err;              // [1] as CollateParams::err
+  int64_t n_chunks;           // collate_chunks(n_rows)
+};
+
 // error codes in CollateParams::err / CollateRowsParams::err (low 4 bits)
 enum : uint32_t {
   CERR_LONG = 1,
@@ -177,5 +196,6 @@ hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_rows_from_strings(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);
+hipError_t launch_mlm_targets(const MlmTargetsParams& P, int n_cu, hipStream_t s);
 
 }  // namespace lddl

@@ -228,15 +228,29 @@ class _RowCollate:
   VOCAB = _lib.VOCAB_BERT
 
   def __init__(self, vocab_file=None, device=None, sequence_length_alignment=8, ignore_index=-1,
-               mlm_probability=0.15, base_seed=12345, tokenizer=None, whole_word_mask=False):
+               mlm_probability=0.15, base_seed=12345, tokenizer=None, whole_word_mask=False, compact_mlm=False):
     """whole_word_mask: dynamic masking (mode 2 and ``mask_tokens``) selects
     words, not tokens: a piece and the ``##`` pieces after it are masked
     together (lddl_set_whole_word_mask; include/lddl_amd.h defines it).  The
     switch lives on the tokenizer's ctx and is set here, on or off: with
     ``tokenizer=`` a shared ctx, every collate over that ctx follows the one
-    constructed last."""
+    constructed last.
+
+    compact_mlm: every batch with ``labels`` (modes 1 and 2) also carries the
+    compact targets of ``mlm_targets`` over those labels, as
+    ``masked_lm_positions``, ``masked_lm_labels`` and ``masked_lm_offsets``:
+    True for exact-size tensors, an int K for tensors of exactly K entries
+    (a batch with more masked tokens raises).  ``ignore_index`` must then be
+    negative.  Everything else in the batch, and the batch counter, are as
+    without it."""
     assert isinstance(sequence_length_alignment, int) and sequence_length_alignment >= 1
     assert isinstance(mlm_probability, (int, float)) and 0 <= mlm_probability <= 1
+    if not isinstance(compact_mlm, bool):
+      if not isinstance(compact_mlm, int) or compact_mlm < 0:
+        raise ValueError('compact_mlm %r: False, True or a capacity >= 0' % (compact_mlm,))
+    if compact_mlm is not False and int(ignore_index) >= 0:  # (before the ctx is made: nothing here needs a GPU)
+      raise ValueError('compact_mlm needs a negative ignore_index: %d could be a label' % int(ignore_index))
+    self.compact_mlm = compact_mlm
     self.tok = tokenizer if tokenizer is not None else Tokenizer(vocab_file or self.VOCAB, device)
     self.whole_word_mask = bool(whole_word_mask)
     L = _lib.lib()
@@ -336,7 +350,7 @@ class _RowCollate:
       batch['next_sentence_labels'] = nsl
     if unpadded:
       batch['cu_seqlens'], batch['max_seqlen'] = cu, int(longest.value)
-    return batch
+    return self._with_targets(batch, cu if unpadded else None)
 
   def _load_table(self, cols, per_row, static, bins, part, nbins):
     """load_rows of both classes over staged columns: the length call, the
@@ -420,11 +434,53 @@ class _RowCollate:
                                            _stream()))
     return inputs, labels
 
+  def mlm_targets(self, labels, cu_seqlens=None, capacity=None):
+    """The masked positions of a batch and their labels, in order
+    (lddl_mlm_targets; include/lddl_amd.h defines it): what a trainer gathers
+    the hidden states at before the LM head.  labels: int64 CUDA, ``[n, S]``
+    of a padded batch, or ``[T]`` with the int32 ``cu_seqlens`` ``[n + 1]`` of
+    a padding-free one -- the ``labels`` of any collate here or of
+    ``mask_tokens``.  Returns (positions, target_labels, offsets): the
+    ascending flat indices into ``labels.view(-1)`` that lie in a row and
+    differ from ``ignore_index``, the labels there (both int64), and int32
+    ``[n + 1]`` offsets of each row's share, ``offsets[n]`` = their number M.
+    capacity None: tensors of M entries (views of ``labels.numel()``
+    allocated).  capacity K: tensors of exactly K entries, (0, ignore_index)
+    behind the first M: fixed shapes, harmless to a loss that honours
+    ``ignore_index``; M > K raises."""
+    assert labels.dtype == torch.int64 and labels.is_cuda and labels.is_contiguous()
+    if cu_seqlens is None:
+      assert labels.dim() == 2
+      n, S = labels.shape
+    else:
+      assert labels.dim() == 1 and cu_seqlens.dtype == torch.int32 and cu_seqlens.is_cuda and cu_seqlens.is_contiguous()
+      n, S = cu_seqlens.numel() - 1, 0
+    total = labels.numel()
+    cap = total if capacity is None else int(capacity)
+    pos = torch.empty(max(cap, 1), dtype=torch.int64, device=labels.device)
+    lab = torch.empty(max(cap, 1), dtype=torch.int64, device=labels.device)
+    off = torch.empty(max(n, 0) + 1, dtype=torch.int32, device=labels.device)
+    count = ctypes.c_int64()
+    _check(_lib.lib().lddl_mlm_targets(self.tok.handle, _ptr(labels), n, S, _ptr(cu_seqlens), total, self.ignore_index,
+                                       cap, _ptr(pos), _ptr(lab), _ptr(off), ctypes.byref(count), _stream()))
+    m = int(count.value) if capacity is None else cap
+    return pos[:m], lab[:m], off
+
+  def _with_targets(self, batch, cu_seqlens=None):
+    """the batch of a collate, with the compact targets of its labels when compact_mlm asks for them"""
+    if self.compact_mlm is not False and 'labels' in batch:
+      capacity = None if self.compact_mlm is True else self.compact_mlm
+      pos, lab, off = self.mlm_targets(batch['labels'], cu_seqlens, capacity)
+      batch['masked_lm_positions'], batch['masked_lm_labels'], batch['masked_lm_offsets'] = pos, lab, off
+    return batch
+
 
 class BertCollate(_RowCollate):
   """``collate(batch) -> dict`` with the keys of bert.py:129-152 plus
   ``labels`` (masked): input_ids, token_type_ids, attention_mask, labels,
-  next_sentence_labels -- int64 tensors on the GPU.
+  next_sentence_labels -- int64 tensors on the GPU.  With ``compact_mlm``
+  also masked_lm_positions, masked_lm_labels and masked_lm_offsets
+  (``mlm_targets`` over those labels), here and in every ``collate_rows*``.
 
   batch: a list of samples as the reference's DataLoader hands to its
   collate_fn (tuples of 3 or 5 fields), or a pyarrow RecordBatch / Table of
@@ -459,8 +515,9 @@ class BertCollate(_RowCollate):
       self.counter += 1
     _check(rc)
     del dev, host  # the stream was synchronised by the call
-    return {'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2], 'next_sentence_labels': nsl,
-            'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
+    return self._with_targets({'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2],
+                               'next_sentence_labels': nsl,
+                               'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]})
 
   # ---- entry points ---------------------------------------------------------
   def __call__(self, batch):

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from .tokenizer import _ptr, _stream
+from .writer import EncodeSink, FilePlan, render_call
 
 SCHEMA = pa.schema([('sentences', pa.string())])  # pretrain.py:144-146
 
@@ -58,20 +59,9 @@ class BartResult:
     numpy arrays, or device tensors with host=False"""
     n = self.n_chunks - c0 if n is None else n
     sh = self.shards
-    dev = sh.data.device
-    off = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    nb = ctypes.c_int64(0)
-    s = _stream(stream)
     args = (_handle(self.ctx), _ptr(sh.data), sh.nbytes, _ptr(sh.sent_off), sh.n_sent, _ptr(self.chunk_sent0),
-            _ptr(self.chunk_nsent), _ptr(self.chunk_off), self.n_chunks, c0, n, _ptr(off))
-    L = _lib.lib()
-    _lib.check(L.lddl_bart_render(*args, None, 0, ctypes.byref(nb), s))
-    data = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
-    _lib.check(L.lddl_bart_render(*args, _ptr(data), nb.value, ctypes.byref(nb), s))
-    if not host:
-      return off, data[:nb.value]
-    from .writer import _host
-    return _host(off, stream), _host(data[:nb.value], stream)
+            _ptr(self.chunk_nsent), _ptr(self.chunk_off), self.n_chunks, c0, n)
+    return render_call(_lib.lib().lddl_bart_render, args, n, sh.data.device, stream, host)
 
 
 def aggregate(corpus_on_device, part_doc_off=None, target_seq_length=128, tokenizer_or_ctx=None, stream=None):
@@ -110,7 +100,6 @@ def aggregate(corpus_on_device, part_doc_off=None, target_seq_length=128, tokeni
 
 def _plan(result, max_parts, part_base):
   """writer.FilePlan of a BartResult: a partition is one file of its chunks"""
-  from .writer import FilePlan
   return FilePlan(np.diff(result.part_chunk_off)[:, None], False, max_parts, part_base)
 
 
@@ -123,23 +112,14 @@ def write_bart_shards(result, out_dir, part_base=0, compression='snappy', batch_
   thread pool takes the encodes and their futures go to `pending` (an
   executor without that list is a ValueError); without one the files are
   written before the call returns.  Returns the files."""
-  import pyarrow.parquet as pq
-  from . import writer
-  sink = writer.EncodeSink(executor, pending)
+  sink = EncodeSink(executor, pending)
   os.makedirs(out_dir, exist_ok=True)
   plan = _plan(result, max_parts, part_base)
   files = []
   for f, g, c0, c1 in plan.batches(batch_rows):
-    n = c1 - c0
     flist = plan.files(f, g, out_dir, 'parquet')
-    off, data = result.render(c0, n, stream, host=not sink.proc)
-    if sink.proc:
-      sink.futs.extend(executor.submit_batch(n, [('sentences', 'str', off, data)], SCHEMA, flist, compression, [],
-                                             stream))
-    else:
-      for path, lo, hi in flist:
-        t = pa.Table.from_arrays([writer._arrow(pa.string(), off, data, lo, hi)], schema=SCHEMA)
-        sink.futs.append(sink.pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=False))
+    specs = [('sentences', 'str') + tuple(result.render(c0, c1 - c0, stream, host=sink.host))]
+    sink.submit_batch(c1 - c0, specs, SCHEMA, flist, compression, [], stream)  # (no dictionary pages)
     files.extend(f_[0] for f_ in flist)
   sink.close()
   return files

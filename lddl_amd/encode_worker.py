@@ -16,10 +16,12 @@ import numpy as np
 import pyarrow as pa
 import pyarrow.parquet as pq
 
+from .arrow_cols import fixed_column, var_column
+
 _MAPS = {}  # slot path -> (mmap, size)
 
 _FIXED = {'bool': np.bool_, 'u16': np.uint16, 'i64': np.int64}
-_ARROW = {'u16': pa.uint16(), 'i64': pa.int64()}
+_VAR = {'str': pa.string(), 'bin': pa.binary()}
 
 
 def _map(path, size):
@@ -40,24 +42,15 @@ def _map(path, size):
   return m[0]
 
 
-def _var_column(typ, mm, off_pos, n, data_pos, lo, hi):
-  """rows [lo, hi) of an (int64 offsets from 0, bytes) column, offsets
-  rebased to the file's first row"""
-  off = np.frombuffer(mm, dtype=np.int64, count=n + 1, offset=off_pos)
-  o = off[lo:hi + 1] - off[lo]
-  nb = int(o[-1])
-  data = pa.py_buffer(memoryview(mm)[data_pos + int(off[lo]):data_pos + int(off[lo]) + nb])
-  if nb < 2**31:
-    return pa.Array.from_buffers(typ, hi - lo, [None, pa.py_buffer(o.astype(np.int32)), data])
-  big = pa.large_string() if typ == pa.string() else pa.large_binary()
-  return pa.Array.from_buffers(big, hi - lo, [None, pa.py_buffer(np.ascontiguousarray(o)), data]).cast(typ)
-
-
-def _fixed_column(kind, mm, pos, n, lo, hi):
-  x = np.frombuffer(mm, dtype=_FIXED[kind], count=n, offset=pos)[lo:hi]
-  if kind == 'bool':
-    return pa.Array.from_buffers(pa.bool_(), hi - lo, [None, pa.py_buffer(np.packbits(x, bitorder='little'))])
-  return pa.Array.from_buffers(_ARROW[kind], hi - lo, [None, pa.py_buffer(np.ascontiguousarray(x))])
+def write_file(path, lo, hi, cols, schema, compression, dict_cols):
+  """Rows [lo, hi) of a batch as one parquet file.  cols: (kind, a, b) per
+  schema column in order: 'str' / 'bin' with a = int64 offsets [n + 1] and
+  b = the bytes (numpy, or a memoryview of the slot mapping), or 'bool' /
+  'u16' / 'i64' with a = the values [n].  The encodes of a thread pool and of
+  the worker processes both end here.  Returns the bytes written."""
+  arrs = [var_column(_VAR[kind], a, b, lo, hi) if kind in _VAR else fixed_column(a[lo:hi]) for kind, a, b in cols]
+  pq.write_table(pa.Table.from_arrays(arrs, schema=schema), path, compression=compression, use_dictionary=dict_cols)
+  return os.path.getsize(path)
 
 
 def encode(slot, size, n, cols, schema, files, compression, dict_cols):
@@ -65,16 +58,7 @@ def encode(slot, size, n, cols, schema, files, compression, dict_cols):
   'str' / 'bin' (offsets at pos, bytes at data_pos) or 'bool' / 'u16' / 'i64';
   files: (path, lo, hi) row ranges of the batch.  Returns the bytes written."""
   mm = _map(slot, size)
-  total = 0
-  for path, lo, hi in files:
-    arrs = []
-    for name, kind, pos, dpos in cols:
-      if kind in ('str', 'bin'):
-        arrs.append(_var_column(pa.string() if kind == 'str' else pa.binary(), mm, pos, n, dpos, lo, hi))
-      else:
-        arrs.append(_fixed_column(kind, mm, pos, n, lo, hi))
-    t = pa.Table.from_arrays(arrs, schema=schema)
-    pq.write_table(t, path, compression=compression, use_dictionary=dict_cols)
-    del t, arrs
-    total += os.path.getsize(path)
-  return total
+  view = [(kind, np.frombuffer(mm, dtype=np.int64, count=n + 1, offset=pos), memoryview(mm)[dpos:]) if kind in _VAR
+          else (kind, np.frombuffer(mm, dtype=_FIXED[kind], count=n, offset=pos), None)
+          for _, kind, pos, dpos in cols]
+  return sum(write_file(path, lo, hi, view, schema, compression, dict_cols) for path, lo, hi in files)

@@ -52,19 +52,9 @@ def _column(values, encode):
 
 
 def _arrow_column(arr):
-  """pa.StringArray / BinaryArray (or a ChunkedArray) -> (uint8 bytes, int64
-  offsets), zero-copy on the bytes"""
-  import pyarrow as pa
-  if isinstance(arr, pa.ChunkedArray):
-    arr = arr.combine_chunks()
-  if pa.types.is_large_string(arr.type) or pa.types.is_large_binary(arr.type):
-    odt = np.int64
-  else:
-    odt = np.int32
-  bufs = arr.buffers()
-  off = np.frombuffer(bufs[1], dtype=odt)[arr.offset:arr.offset + len(arr) + 1].astype(np.int64)
-  data = np.frombuffer(bufs[2], dtype=np.uint8) if bufs[2] is not None else np.zeros(0, np.uint8)
-  return data, off
+  """arrow_cols.var_buffers (pyarrow is imported with the first Arrow input)"""
+  from .arrow_cols import var_buffers
+  return var_buffers(arr)
 
 
 def _merge_columns(parts):

@@ -28,10 +28,10 @@ import time
 
 import numpy as np
 import pyarrow as pa
-import pyarrow.parquet as pq
 import torch
 
-from . import _lib
+from . import _lib, encode_worker
+from .arrow_cols import fixed_column, var_buffers, var_column
 from .tokenizer import _ptr, _stream
 
 SEG0, SEG1, ROW, SPAN = 0, 1, 2, 3
@@ -65,43 +65,42 @@ def _host(t, stream=None):
   return h.numpy()
 
 
+def render_call(fn, args, n_rows, device, stream=None, host=True):
+  """One rendered column of n_rows rows: the C render entry point `fn` called
+  twice, for the size (NULL bytes) and for the fill.  args: fn's arguments up
+  to the offsets pointer, which is made here and follows them.  Returns
+  (offsets int64[n_rows + 1] from 0, bytes uint8): numpy arrays on the host,
+  or with host=False device tensors (the process encoder copies them into its
+  shared slot)."""
+  off = torch.empty(n_rows + 1, dtype=torch.int64, device=device)
+  nb = ctypes.c_int64(0)
+  s = _stream(stream)
+  _lib.check(fn(*args, _ptr(off), None, 0, ctypes.byref(nb), s))
+  data = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=device)
+  _lib.check(fn(*args, _ptr(off), _ptr(data), nb.value, ctypes.byref(nb), s))
+  if not host:
+    return off, data[:nb.value]
+  return _host(off, stream), _host(data[:nb.value], stream)
+
+
 def render(packer, tokens, row_off, row0, n_rows, segment, len0=None, len1=None, flags=None, codebert=False,
            stream=None, host=True):
   """One string column of rows [row0, row0 + n_rows) on the GPU.
 
   Returns (offsets int64[n_rows + 1] starting at 0, bytes uint8) on the host.
   """
-  L = _lib.lib()
-  dev = packer.device
-  off = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-  nb = ctypes.c_int64(0)
-  s = _stream(stream)
   args = (packer.tok.handle, _ptr(tokens), _ptr(row_off), _ptr(len0), _ptr(len1), _ptr(flags), row0, n_rows,
-          segment, 1 if codebert else 0, _ptr(off))
-  _lib.check(L.lddl_render_strings(*args, None, 0, ctypes.byref(nb), s))
-  data = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
-  _lib.check(L.lddl_render_strings(*args, _ptr(data), nb.value, ctypes.byref(nb), s))
-  if not host:  # (device tensors: the process encoder copies them into its shared slot)
-    return off, data[:nb.value]
-  return _host(off, stream), _host(data[:nb.value], stream)
+          segment, 1 if codebert else 0)
+  return render_call(_lib.lib().lddl_render_strings, args, n_rows, packer.device, stream, host)
 
 
 def render_masked(packer, res, row0, n_rows, segment, stream=None, host=True):
   """A (segment 0) / B (1) of span rows with the static masking applied
   (lddl_render_masked): (offsets, bytes) on the host as render()"""
-  L = _lib.lib()
-  off = torch.empty(n_rows + 1, dtype=torch.int64, device=packer.device)
-  nb = ctypes.c_int64(0)
-  s = _stream(stream)
   src, ln = (res.src0, res.len0) if segment == 0 else (res.src1, res.len1)
   args = (packer.tok.handle, _ptr(res.ids), _ptr(src), _ptr(ln), _ptr(res.len0), segment, _ptr(res.mlm_off),
-          _ptr(res.mlm_pos), _ptr(res.mlm_token), row0, n_rows, _ptr(off))
-  _lib.check(L.lddl_render_masked(*args, None, 0, ctypes.byref(nb), s))
-  data = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=packer.device)
-  _lib.check(L.lddl_render_masked(*args, _ptr(data), nb.value, ctypes.byref(nb), s))
-  if not host:
-    return off, data[:nb.value]
-  return _host(off, stream), _host(data[:nb.value], stream)
+          _ptr(res.mlm_pos), _ptr(res.mlm_token), row0, n_rows)
+  return render_call(_lib.lib().lddl_render_masked, args, n_rows, packer.device, stream, host)
 
 
 def seg_columns(packer, res, r0, n, codebert=False, stream=None, host=True):
@@ -157,17 +156,8 @@ def render_npy(packer, res, row0, n_rows, stream=None, host=True):
   if t is None:
     return None
   hdr, hlen, kmax = t
-  L = _lib.lib()
-  off = torch.empty(n_rows + 1, dtype=torch.int64, device=packer.device)
-  nb = ctypes.c_int64(0)
-  s = _stream(stream)
-  args = (packer.tok.handle, _ptr(res.mlm_off), _ptr(res.mlm_pos), row0, n_rows, _ptr(hdr), hlen, kmax, _ptr(off))
-  _lib.check(L.lddl_render_npy(*args, None, 0, ctypes.byref(nb), s))
-  data = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=packer.device)
-  _lib.check(L.lddl_render_npy(*args, _ptr(data), nb.value, ctypes.byref(nb), s))
-  if not host:
-    return off, data[:nb.value]
-  return _host(off, stream), _host(data[:nb.value], stream)
+  args = (packer.tok.handle, _ptr(res.mlm_off), _ptr(res.mlm_pos), row0, n_rows, _ptr(hdr), hlen, kmax)
+  return render_call(_lib.lib().lddl_render_npy, args, n_rows, packer.device, stream, host)
 
 
 def _npy_header(k):
@@ -222,18 +212,7 @@ def _npy_positions_u16(k, inv, hdr, mlm_pos):
   return off16 * 2, data.view(np.uint8)
 
 
-# Arrow arrays straight from buffers: pa.array() on numpy arrays or Python
-# lists imports pandas on its first call (~0.4-0.5 s per process)
-_NP_TYPES = {np.dtype(np.uint16): pa.uint16(), np.dtype(np.int64): pa.int64(), np.dtype(np.int32): pa.int32()}
-
-
-def np_array(x):
-  """Arrow array of a 1-D numpy array (bool, uint16, int32 or int64), no copy
-  except bools (bit-packed)"""
-  x = np.ascontiguousarray(x)
-  if x.dtype == np.bool_:
-    return pa.Array.from_buffers(pa.bool_(), len(x), [None, pa.py_buffer(np.packbits(x, bitorder='little'))])
-  return pa.Array.from_buffers(_NP_TYPES[x.dtype], len(x), [None, pa.py_buffer(x)])
+np_array = fixed_column  # Arrow array of a 1-D numpy array (bool, uint16, int32 or int64)
 
 
 def str_array(strs):
@@ -241,47 +220,10 @@ def str_array(strs):
   b = [s.encode('utf-8') for s in strs]
   off = np.zeros(len(b) + 1, dtype=np.int64)
   np.cumsum(np.fromiter(map(len, b), dtype=np.int64, count=len(b)), out=off[1:])
-  return _arrow(pa.string(), off, np.frombuffer(b''.join(b), dtype=np.uint8), 0, len(b))
-
-
-OFF32_LIMIT = 2**31
-
-
-def _arrow_rows(typ, off, data, n):
-  """all n rows of a (int64 offsets from 0, bytes) column: 32-bit offsets, or
-  the large type when the bytes pass 2 GiB (files slice and cast it)"""
-  if off[n] < OFF32_LIMIT:
-    return pa.Array.from_buffers(typ, n, [None, pa.py_buffer(off[:n + 1].astype(np.int32)), pa.py_buffer(data)])
-  big = pa.large_string() if typ == pa.string() else pa.large_binary()
-  return pa.Array.from_buffers(big, n, [None, pa.py_buffer(np.ascontiguousarray(off[:n + 1])), pa.py_buffer(data)])
-
-
-def _arrow(typ, off, data, lo, hi):
-  """rows [lo, hi) of a (int64 offsets, bytes) column as an Arrow array"""
-  o = off[lo:hi + 1] - off[lo]
-  d = data[off[lo]:off[hi]]
-  if o[-1] < 2**31:
-    return pa.Array.from_buffers(typ, hi - lo, [None, pa.py_buffer(o.astype(np.int32)), pa.py_buffer(d)])
-  big = pa.large_string() if typ == pa.string() else pa.large_binary()
-  return pa.Array.from_buffers(big, hi - lo, [None, pa.py_buffer(o), pa.py_buffer(d)]).cast(typ)
-
-
-def file_table(sch, cols, raw, lo, hi, batch=None):
-  """rows [lo, hi) of a writer batch as one file's table.  batch: the batch's
-  table when every column fits its schema type (a zero-copy slice of it);
-  otherwise (a string column's batch bytes pass 2 GiB: large_string) each
-  string column is rebuilt from raw[name] = (type, int64 offsets, bytes)
-  with offsets rebased to the file's first row -- a slice of the large
-  column keeps absolute offsets, which a cast back to string rejects past
-  2^31 (the file's own bytes fit)"""
-  if batch is not None:
-    return batch.slice(lo, hi - lo)
-  arrs = [_arrow(*raw[nm], lo, hi) if nm in raw else cols[nm].slice(lo, hi - lo) for nm in sch.names]
-  return pa.Table.from_arrays(arrs, schema=sch)
+  return var_column(pa.string(), off, np.frombuffer(b''.join(b), dtype=np.uint8), 0, len(b))
 
 
 def _worker_init():
-  from . import encode_worker  # noqa: F401  (imported before the first batch)
   n = int(os.environ.get('LDDL_WORKER_NICE', '5'))  # (niced as the CLI's split workers)
   if n > 0:
     try:
@@ -439,13 +381,11 @@ class ProcessEncoder:
     if dev:
       st.synchronize()
     self.copy_s += time.perf_counter() - t0
-    from . import encode_worker
     # tasks of about equal rows, at least one file each, ~2 per worker
     ntask = max(1, min(len(files), 2 * self.workers))
     bounds = np.searchsorted(np.array([f_[2] for f_ in files]), np.linspace(0, n, ntask + 1)[1:-1], side='left')
     cuts = [0] + sorted(set(int(x) + 1 for x in bounds if 0 <= x < len(files) - 1)) + [len(files)]
-    cols = [(name, kind, p0, p1) for name, kind, p0, p1 in lay]
-    futs = [self.ex.submit(encode_worker.encode, sl['path'], sl['size'], n, cols, sch, files[a:b], compression,
+    futs = [self.ex.submit(encode_worker.encode, sl['path'], sl['size'], n, lay, sch, files[a:b], compression,
                            dict_cols) for a, b in zip(cuts[:-1], cuts[1:]) if b > a]
     sl['futs'] = list(futs)
     return futs
@@ -475,15 +415,8 @@ class ProcessEncoder:
 
 def _host_var(arr, r0, n):
   """rows [r0, r0 + n) of an Arrow string array as (int64 offsets from 0, bytes)"""
-  a = arr.slice(r0, n)
-  wide = a.type in (pa.large_string(), pa.large_binary())
-  off = np.frombuffer(a.buffers()[1], dtype=np.int64 if wide else np.int32, count=a.offset + n + 1)[a.offset:]
-  off = off.astype(np.int64)
-  buf = a.buffers()[2]
-  # (Arrow may leave the data buffer out when every string of the slice is empty)
-  data = np.frombuffer(buf, dtype=np.uint8, count=int(off[-1]))[int(off[0]):] if n and buf is not None and off[-1] \
-      else np.zeros(0, np.uint8)
-  return off - off[0], data
+  data, off = var_buffers(arr.slice(r0, n))
+  return off - off[0], data[int(off[0]):int(off[-1])]
 
 
 FILE_NAMES = {'parquet': ('part.%d.parquet', 'part.%d.parquet_%d'), 'txt': ('%d.txt', '%d_%d.txt')}
@@ -553,7 +486,9 @@ def mlm_positions(packer, res, r0, r1, n_rows, cache, stream=None, host=True):
 class EncodeSink:
   """Where a writer's parquet encodes go: a thread pool of its own, whose
   files close() waits for, or the caller's executor (a ProcessEncoder or a
-  thread pool), where close() hands the open futures to the caller's list."""
+  thread pool), where close() hands the open futures to the caller's list.
+  `host`: whether the batches' columns are wanted on the host (threads) or
+  as device tensors (a ProcessEncoder copies them into its shared slot)."""
 
   @staticmethod
   def check(executor, pending):
@@ -564,9 +499,28 @@ class EncodeSink:
     self.check(executor, pending)
     self.own, self.pending = executor is None, pending
     self.proc = isinstance(executor, ProcessEncoder)
+    self.host = not self.proc
     self.workers = executor.workers if self.proc else encode_workers()
     self.pool = concurrent.futures.ThreadPoolExecutor(self.workers) if self.own else executor
     self.futs = []
+
+  def submit_batch(self, n, specs, sch, files, compression, dict_cols, stream=None):
+    """The files of one batch, as ProcessEncoder.submit_batch takes them (with
+    threads the specs' columns are host arrays, and a file is one task).
+    Returns the seconds spent waiting for older files: threads hold at most
+    4 * workers open futures, so that rendering does not run far ahead of the
+    encodes (the parquet encoder releases the GIL: files encode in parallel
+    on the host cores while the next batch renders on the GPU)."""
+    if self.proc:
+      self.futs.extend(self.pool.submit_batch(n, specs, sch, files, compression, dict_cols, stream))
+      return 0.0
+    cols = [spec[1:] for spec in specs]
+    self.futs.extend(self.pool.submit(encode_worker.write_file, path, lo, hi, cols, sch, compression, dict_cols)
+                     for path, lo, hi in files)
+    t = time.perf_counter()
+    while len(self.futs) > 4 * self.workers:
+      self.futs.pop(0).result()
+    return time.perf_counter() - t
 
   def close(self):
     if self.own:
@@ -609,9 +563,9 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
   # per row and the encoder would build and then discard a dictionary for them
   dict_cols = [n_ for n_ in sch.names if n_ not in DENSE_COLS]
   n_rows = plan.n_rows  # rows of the files written
-  num_tokens = np.diff(res.tok_off[:n_rows + 1].cpu().numpy()).astype(np.uint16)
-  flags = res.flags[:n_rows].cpu().numpy()
-  bins = res.bins[:n_rows].cpu().numpy().astype(np.int64)
+  fixed = {'is_random_next': ('bool', (res.flags[:n_rows].cpu().numpy() & 1).astype(bool)),
+           'num_tokens': ('u16', np.diff(res.tok_off[:n_rows + 1].cpu().numpy()).astype(np.uint16)),
+           'bin_id': ('i64', res.bins[:n_rows].cpu().numpy().astype(np.int64))}
   if codebert:
     if doc_ids is None:
       raise ValueError('CodeBERT shards need doc_ids (the id column)')
@@ -630,51 +584,21 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
     flist = plan.files(f, g, out_dir, 'parquet')
     files.extend(f_[0] for f_ in flist)
     t0 = time.perf_counter()
-    host = not sink.proc  # (ProcessEncoder: the columns stay device tensors, which it copies into its shared slot)
-    var = dict(zip((seg0, seg1), seg_columns(packer, res, r0, n, codebert, stream, host=host)))
+    var = dict(zip((seg0, seg1), seg_columns(packer, res, r0, n, codebert, stream, host=sink.host)))
     if masking:
-      var['masked_lm_labels'] = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream, host=host)
-      var['masked_lm_positions'] = mlm_positions(packer, res, r0, r1, n_rows, host_mlm, stream, host=host)
-    if sink.proc:
-      if codebert:
-        var['id'] = _host_var(ids_col, r0, n)
-      fixed = {'is_random_next': ('bool', (flags[r0:r1] & 1).astype(bool)), 'num_tokens': ('u16', num_tokens[r0:r1]),
-               'bin_id': ('i64', bins[r0:r1])}
-      specs = [(nm, 'bin' if nm == 'masked_lm_positions' else 'str') + tuple(var[nm]) if nm in var else
-               (nm, fixed[nm][0], fixed[nm][1], None) for nm in sch.names]
-      t1 = time.perf_counter()
-      st['render_s'] += t1 - t0
-      st['batches'] += 1
-      sink.futs.extend(executor.submit_batch(n, specs, sch, flist, compression, dict_cols, stream))
-      st['table_s'] += time.perf_counter() - t1
-      continue
-    t1 = time.perf_counter()
-    st['render_s'] += t1 - t0
-    st['batches'] += 1
-    # one table over the batch's rows; a file is a zero-copy slice of it
-    raw = {nm: (sch.field(nm).type,) + tuple(c) for nm, c in var.items()}
-    cols = {'num_tokens': np_array(num_tokens[r0:r1])}
+      var['masked_lm_labels'] = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream, host=sink.host)
+      var['masked_lm_positions'] = mlm_positions(packer, res, r0, r1, n_rows, host_mlm, stream, host=sink.host)
     if codebert:
-      cols['id'] = ids_col.slice(r0, n)
-    else:
-      cols['is_random_next'] = np_array((flags[r0:r1] & 1).astype(bool))
-    if binned:
-      cols['bin_id'] = np_array(bins[r0:r1])
-    for nm, (typ, off, data) in raw.items():
-      cols[nm] = _arrow_rows(typ, off, data, n)
-    arrs = [cols[name] for name in sch.names]
-    large = any(a.type != fd.type for a, fd in zip(arrs, sch))
-    tb = None if large else pa.Table.from_arrays(arrs, names=sch.names)
-    for path, lo, hi in flist:
-      t = file_table(sch, cols, raw, lo, hi, tb)
-      sink.futs.append(sink.pool.submit(pq.write_table, t, path, compression=compression, use_dictionary=dict_cols))
+      var['id'] = _host_var(ids_col, r0, n)
+    specs = [(nm, 'bin' if nm == 'masked_lm_positions' else 'str') + tuple(var[nm]) if nm in var else
+             (nm, fixed[nm][0], fixed[nm][1][r0:r1], None) for nm in sch.names]
+    t1 = time.perf_counter()
+    wait = sink.submit_batch(n, specs, sch, flist, compression, dict_cols, stream)
     t2 = time.perf_counter()
-    st['table_s'] += t2 - t1
-    # the parquet encoder releases the GIL: files of a batch encode in
-    # parallel on the host cores while the next batch renders on the GPU
-    while len(sink.futs) > 4 * sink.workers:
-      sink.futs.pop(0).result()
-    st['backpressure_s'] += time.perf_counter() - t2
+    st['render_s'] += t1 - t0
+    st['table_s'] += t2 - t1 - wait
+    st['backpressure_s'] += wait
+    st['batches'] += 1
   t3 = time.perf_counter()
   sink.close()
   st['drain_s'] = time.perf_counter() - t3
@@ -720,32 +644,29 @@ def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False
     if isinstance(doc_ids, pa.Array):
       doc_ids = doc_ids.to_pylist()
     docs = row_docs(packer, res, n_rows, stream)
-  if masking and not codebert:
+  masking = masking and not codebert
+  if masking:
     moff_all = res.mlm_off[:n_rows + 1].cpu().numpy()
     mpos_all = res.mlm_pos[:int(moff_all[-1])].cpu().numpy().view(np.uint16)
   files = []
   for f, g, r0, r1 in plan.batches(batch_rows):
     n = r1 - r0
     (o0, d0), (o1, d1) = seg_columns(packer, res, r0, n, codebert, stream)
-    if masking and not codebert:
-      ol, dl = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream)
     b0, b1 = d0.tobytes(), d1.tobytes()
-    bl = dl.tobytes() if masking and not codebert else b''
+    if masking:
+      ol, dl = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream)
+      bl = dl.tobytes()
     for path, lo, hi in plan.files(f, g, out_dir, 'txt'):
       lines = []
       for i in range(lo, hi):
         r = r0 + i
-        a, bb = b0[o0[i]:o0[i + 1]].decode(), b1[o1[i]:o1[i + 1]].decode()
-        if codebert:
-          lines.append('{} [CLS] {} [SEP] {} [SEP] - {}'.format(doc_ids[docs[r]], a, bb, int(num_tokens[r])))
-        elif masking:
+        head = doc_ids[docs[r]] if codebert else 'is_random_next: {} -'.format(bool(flags[r] & 1))
+        mlm = ''
+        if masking:
           pos = np.array(mpos_all[moff_all[r] - moff_all[0]:moff_all[r + 1] - moff_all[0]], dtype=np.uint16)
-          lines.append('is_random_next: {} - [CLS] {} [SEP] {} [SEP] - masked_lm_positions: {} - '
-                       'masked_lm_labels: {} - {}'.format(bool(flags[r] & 1), a, bb, pos,
-                                                          bl[ol[i]:ol[i + 1]].decode(), int(num_tokens[r])))
-        else:
-          lines.append('is_random_next: {} - [CLS] {} [SEP] {} [SEP] - {}'.format(bool(flags[r] & 1), a, bb,
-                                                                                 int(num_tokens[r])))
+          mlm = 'masked_lm_positions: {} - masked_lm_labels: {} - '.format(pos, bl[ol[i]:ol[i + 1]].decode())
+        lines.append('{} [CLS] {} [SEP] {} [SEP] - {}{}'.format(head, b0[o0[i]:o0[i + 1]].decode(),
+                                                               b1[o1[i]:o1[i + 1]].decode(), mlm, int(num_tokens[r])))
       with open(path, 'w', encoding='utf-8', newline='') as fh:
         fh.write('\n'.join(lines))
       files.append(path)

@@ -349,42 +349,54 @@ def test_chunk_pieces_cover_the_chunk():
 
 
 def test_batch_columns_past_32bit_offsets(monkeypatch):
-  """a writer batch whose string bytes pass the 32-bit offset range is built
-  with the large type and each file's slice cast back to the schema's"""
+  """a column slice whose bytes pass the 32-bit offset range goes through the
+  large type and comes back as the schema's; below it, it never leaves it"""
   import pyarrow as pa
-  from lddl_amd import writer
+  from lddl_amd import arrow_cols
   off = np.array([0, 3, 3, 7, 9], np.int64)
   data = np.frombuffer(b'abcdefghi', np.uint8)
-  monkeypatch.setattr(writer, 'OFF32_LIMIT', 4)
-  a = writer._arrow_rows(pa.string(), off, data, 4)
-  assert a.type == pa.large_string()
-  t = pa.Table.from_arrays([a], names=['A']).slice(1, 2).cast(pa.schema([('A', pa.string())]))
-  assert t.schema.field('A').type == pa.string() and t.column('A').to_pylist() == ['', 'defg']
-  monkeypatch.setattr(writer, 'OFF32_LIMIT', 2**31)
-  assert writer._arrow_rows(pa.binary(), off, data, 4).type == pa.binary()
+  large = []  # the types that went through their large type
+
+  class Recording(dict):
+    def __getitem__(self, typ):
+      large.append(typ)
+      return dict.__getitem__(self, typ)
+  monkeypatch.setattr(arrow_cols, '_LARGE', Recording(arrow_cols._LARGE))
+  monkeypatch.setattr(arrow_cols, 'OFF32_LIMIT', 4)
+  a = arrow_cols.var_column(pa.string(), off, data, 0, 4)
+  assert large == [pa.string()] and a.type == pa.string() and a.to_pylist() == ['abc', '', 'defg', 'hi']
+  a = arrow_cols.var_column(pa.string(), off, data, 1, 3)  # (4 bytes: at the limit)
+  assert len(large) == 2 and a.type == pa.string() and a.to_pylist() == ['', 'defg']
+  assert arrow_cols.var_column(pa.string(), off, data, 0, 2).to_pylist() == ['abc', ''] and len(large) == 2
+  monkeypatch.setattr(arrow_cols, 'OFF32_LIMIT', 2**31)
+  assert arrow_cols.var_column(pa.binary(), off, data, 0, 4).type == pa.binary() and len(large) == 2
 
 
-def test_file_table_rebases_offsets_past_2gib():
+def test_file_table_rebases_offsets_past_2gib(tmp_path):
   """a writer batch whose string bytes really pass 2^31: the file
-  after the 2 GiB row is rebuilt with offsets rebased to its first row, not
-  sliced from the batch's large_string column (Arrow keeps a slice's absolute
-  offsets, and the cast back to string rejects them).  np.zeros leaves the
-  2 GiB buffer untouched: nothing reads its bytes."""
+  after the 2 GiB row is built with offsets rebased to its first row, not
+  sliced from a large_string column of the batch (Arrow keeps a slice's
+  absolute offsets, and the cast back to string rejects them).  np.zeros
+  leaves the 2 GiB buffer untouched: nothing reads its bytes."""
   import pyarrow as pa
-  from lddl_amd import writer
+  import pyarrow.parquet as pq
+  from lddl_amd import arrow_cols, encode_worker
   big = 2**31 + 5
   data = np.zeros(big + 3, np.uint8)
   data[big:] = np.frombuffer(b'xyz', np.uint8)
   off = np.array([0, big, big + 3], np.int64)
   sch = pa.schema([('A', pa.string()), ('num_tokens', pa.uint16())])
-  raw = {'A': (pa.string(), off, data)}
-  cols = {'A': writer._arrow_rows(pa.string(), off, data, 2), 'num_tokens': writer.np_array(np.array([7, 9], np.uint16))}
-  assert cols['A'].type == pa.large_string()
-  t = writer.file_table(sch, cols, raw, 1, 2)
+  a = arrow_cols.var_column(pa.string(), off, data, 1, 2)
+  assert a.type == pa.string() and a.to_pylist() == ['xyz']
+  path = str(tmp_path / 'f.parquet')
+  encode_worker.write_file(path, 1, 2, [('str', off, data), ('u16', np.array([7, 9], np.uint16), None)], sch, 'snappy',
+                           ['num_tokens'])
+  t = pq.read_table(path)
   assert t.schema == sch
   assert t.column('A').to_pylist() == ['xyz'] and t.column('num_tokens').to_pylist() == [9]
+  whole = pa.Array.from_buffers(pa.large_string(), 2, [None, pa.py_buffer(off), pa.py_buffer(data)])
   with pytest.raises(pa.ArrowInvalid):  # the old per-file slice + cast
-    pa.Table.from_arrays([cols['A']], names=['A']).slice(1, 1).cast(pa.schema([('A', pa.string())]))
+    pa.Table.from_arrays([whole], names=['A']).slice(1, 1).cast(pa.schema([('A', pa.string())]))
 
 
 # ---- the chunk plan, the worker scope and the split-ahead iterator ------------

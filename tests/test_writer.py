@@ -8,7 +8,7 @@ import numpy as np
 import pyarrow as pa
 import pytest
 
-from lddl_amd import writer
+from lddl_amd import arrow_cols, writer
 
 
 def _serialize(a):
@@ -27,7 +27,7 @@ def test_npy_positions_match_np_save():
   o, d = writer.npy_positions(off, pos)
   for r in range(len(k)):
     assert d[o[r]:o[r + 1]].tobytes() == _serialize(pos[off[r]:off[r + 1]].astype(np.uint16))
-  col = writer._arrow(pa.binary(), o, d, 10, 20)
+  col = arrow_cols.var_column(pa.binary(), o, d, 10, 20)
   assert col.to_pylist() == [_serialize(pos[off[r]:off[r + 1]]) for r in range(10, 20)]
 
 
@@ -48,8 +48,8 @@ def test_schemas():
 def test_arrow_slices_and_large_offsets():
   data = np.frombuffer(b'abcdefghij', dtype=np.uint8)
   off = np.array([0, 2, 2, 5, 10], dtype=np.int64)
-  assert writer._arrow(pa.string(), off, data, 1, 4).to_pylist() == ['', 'cde', 'fghij']
-  assert writer._arrow(pa.string(), off, data, 2, 2).to_pylist() == []
+  assert arrow_cols.var_column(pa.string(), off, data, 1, 4).to_pylist() == ['', 'cde', 'fghij']
+  assert arrow_cols.var_column(pa.string(), off, data, 2, 2).to_pylist() == []
 
 
 def test_process_encoder_writes_what_pyarrow_writes(tmp_path):
@@ -85,7 +85,7 @@ def test_process_encoder_writes_what_pyarrow_writes(tmp_path):
         for nm, fd in zip(sch.names, sch):
           if nm in cols:
             off, data = cols[nm]
-            arrs.append(writer._arrow(fd.type, off, data, lo, hi))
+            arrs.append(arrow_cols.var_column(fd.type, off, data, lo, hi))
           else:
             arrs.append(writer.np_array(fixed[nm][1][lo:hi]))
         exp = pa.Table.from_arrays(arrs, schema=sch)

@@ -75,6 +75,36 @@ def test_bert_parquet_golden(packer, tmp_path, k, binned, spans):
     assert got['masked_lm_labels'] == [_join(vocab, e['masked_lm_labels']) for e in exp]
 
 
+def test_write_shards_same_files_through_both_sinks(packer, tmp_path):
+  """one masked, binned golden pack through the writer's own thread pool and
+  through a ProcessEncoder (device columns, copied into its slots): the same
+  file names, schemas and rows, across several render batches"""
+  from lddl_amd import writer
+  case = BERT['cases'][24]
+  c = case['cfg']
+  sh, ids, ntok = shards_from_docs(case['docs'])
+  res = packer.pack(sh, ids, ntok, target_seq_length=c['max_seq'], short_seq_prob=c['ssp'], duplicate_factor=c['dup'],
+                    seed=case['seed'], bin_size=case['bin_size'], masking=True, spans=True)
+  kw = dict(bin_size=case['bin_size'], masking=True, part_base=3, batch_rows=97)
+  threads = writer.write_shards(packer, res, str(tmp_path / 'threads'), **kw)
+  enc, pending = writer.ProcessEncoder(workers=1, slots=2), []  # (one worker: each is a fork of the test process)
+  try:
+    procs = writer.write_shards(packer, res, str(tmp_path / 'procs'), executor=enc, pending=pending, **kw)
+    for fu in pending:
+      fu.result()
+  finally:
+    enc.close()
+  assert [os.path.basename(f) for f in threads] == [os.path.basename(f) for f in procs]
+  assert len(threads) == case['nbins'] and writer.LAST_STATS['batches'] > 1
+  rows = 0
+  for ft, fp in zip(threads, procs):
+    tt, tp = pq.read_table(ft), pq.read_table(fp)
+    assert tt.schema == tp.schema == writer.schema(False, True, True) and tt.equals(tp), ft
+    assert pq.read_metadata(ft).schema.equals(pq.read_metadata(fp).schema)
+    rows += tt.num_rows
+  assert rows == len(case['rows'])
+
+
 @pytest.mark.parametrize('spans', [False, True])
 @pytest.mark.parametrize('k', range(12))
 def test_codebert_parquet_golden(cpacker, tmp_path, k, spans):

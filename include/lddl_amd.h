@@ -153,6 +153,29 @@ int lddl_pack_codebert(lddl_ctx *ctx, lddl_pack *pack, const int32_t *d_ntok, co
                        double short_seq_prob, int32_t duplicate_factor, uint64_t seed, int32_t bin_size,
                        int64_t *out_totals, void *stream);
 
+/* MLM-only packing: single-segment rows without NSP, [CLS] s_i .. s_j [SEP]
+ * over consecutive sentences of one document (what RoBERTa-style recipes
+ * train on).  The reference has no such mode; the draw order reuses its
+ * seams: random.seed(seed + p) per partition; per kept document (>= 1
+ * non-empty sentence; corpus order, duplicate_factor passes) the
+ * short_seq_prob draw of create_pairs_from_document (pretrain.py:259-265:
+ * target = target_seq_length - 2, or randint(2, that) when random() <
+ * short_seq_prob); sentences accumulate until the chunk holds >= target tokens
+ * or the document ends; a chunk longer than target_seq_length - 2 loses one
+ * token per random() coin, front when < 0.5 else back (:161-179); then
+ * random.shuffle of the partition's rows (:401) and the stable binning of
+ * binning.py:63-93.  Arguments, checks and out_totals as lddl_pack_codebert
+ * without d_doc_nseg_doc (out_totals[3] = 0); every d_ntok count <= 32768.
+ * There is no error path.  A row is the CodeBERT packer's docstring-less
+ * row: len0 = 0, flags = 0, the tokens in segment 1, so lddl_materialize
+ * ([CLS] tokens [SEP]), lddl_row_spans, lddl_row_docs and the render calls
+ * read it unchanged; lddl_masked_lm[_spans] refuse it (dynamic masking in the
+ * collate calls covers these rows). */
+int lddl_pack_mlm(lddl_ctx *ctx, lddl_pack *pack, const int32_t *d_ntok, const int64_t *d_tok_off, const int64_t *d_sent_off,
+                  int64_t n_sent, const int64_t *d_doc_sent_off, int64_t n_doc, const int64_t *d_part_doc_off,
+                  int64_t n_part, int32_t target_seq_length, double short_seq_prob, int32_t duplicate_factor,
+                  uint64_t seed, int32_t bin_size, int64_t *out_totals, void *stream);
+
 /* d_ids: the dense ids lddl_tokenize wrote (and the pack call read).
  * Write the rows of `pack` in output order (partition-major,
  * bin-major, shuffled order within a bin = the reference's part.{p}.parquet_{b}

@@ -77,7 +77,10 @@ static int pack_debug_report(const PackParams& P, int64_t n_part, hipStream_t st
   return 0;
 }
 
-static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* d_ntok, const int64_t* d_tok_off,
+// which packer a pack call runs (pack_common)
+enum PackKind { PACK_BERT = 0, PACK_CODEBERT = 1, PACK_MLM = 2 };
+
+static int pack_common(lddl_ctx* c, lddl_pack* pk, PackKind kind, const int32_t* d_ntok, const int64_t* d_tok_off,
                        const int64_t* d_sent_off, int64_t n_sent,
                        const int64_t* d_doc_sent_off, const int32_t* d_doc_nseg_doc, int64_t n_doc,
                        const int64_t* d_part_doc_off, int64_t n_part, int32_t target_seq_length,
@@ -97,7 +100,7 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
   if (n_part < 1 || n_doc < 0 || n_sent < 0) return set_err(LDDL_EINVAL, "bad sizes");
   if (!d_ntok || !d_tok_off || !d_sent_off || !d_doc_sent_off || !d_part_doc_off || !out_totals)
     return set_err(LDDL_EINVAL, "null pointer");
-  if (codebert && !d_doc_nseg_doc) return set_err(LDDL_EINVAL, "codebert needs doc_nseg_doc");
+  if (kind == PACK_CODEBERT && !d_doc_nseg_doc) return set_err(LDDL_EINVAL, "codebert needs doc_nseg_doc");
   if (target_seq_length < 5 || target_seq_length > 32768)
     return set_err(LDDL_EINVAL, "target_seq_length %d not in [5, 32768]", target_seq_length);
   if (duplicate_factor < 1) return set_err(LDDL_EINVAL, "duplicate_factor %d < 1", duplicate_factor);
@@ -183,7 +186,7 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
     if (!spec_ok) HIP_TRY(launch_sent_special(d_ids, d_tok_off, d_ntok, n_sent, P.cls_id, P.sep_id, sent_spec, st));
     if (!k->mlm_cap) k->mlm_cap = (uint64_t)n_part * 4 * MLM_CHUNK + (uint64_t)duplicate_factor * n_sent * 4;
   }
-  if (!codebert) {
+  if (kind == PACK_BERT) {
     // Wave packer: one 64-lane workgroup per partition runs a serial chain, so
     // throughput is partitions in flight; measured on the bench workload the
     // per-partition arrays are best left in global memory (L2), keeping the
@@ -222,8 +225,10 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, int codebert, const int32_t* 
       HIP_TRY(hipMemsetAsync(c->d_pdbg, 0, pdbg_n * 8, st));
       P.dbg = c->d_pdbg;
     }
-    HIP_TRY(codebert ? launch_pack_codebert_wave(P, st) : launch_pack_bert_wave(P, st));
-    if (P.dbg && !codebert && (rc = pack_debug_report(P, n_part, st))) return rc;
+    HIP_TRY(kind == PACK_CODEBERT ? launch_pack_codebert_wave(P, st)
+            : kind == PACK_MLM    ? launch_pack_mlm_wave(P, st)
+                                  : launch_pack_bert_wave(P, st));
+    if (P.dbg && kind == PACK_BERT && (rc = pack_debug_report(P, n_part, st))) return rc;
     HIP_TRY(launch_scan_parts(P.part_npairs, P.part_ntok, n_part, pair_base, tok_base, P.part_err, err_any, st));
     HIP_TRY(fetch_word(c, HW_NPAIRS, pair_base + n_part, 8, st));
     HIP_TRY(fetch_word(c, HW_NTOK, tok_base + n_part, 8, st));
@@ -265,7 +270,7 @@ extern "C" int lddl_pack_bert(lddl_ctx* c, lddl_pack* pk, const uint16_t* d_ids,
                               double short_seq_prob, int32_t duplicate_factor, int32_t masking,
                               double masked_lm_ratio, uint64_t seed, int32_t bin_size, int64_t* out_totals,
                               void* stream) {
-  return pack_common(c, pk, 0, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, nullptr, n_doc, d_part_doc_off, n_part,
+  return pack_common(c, pk, PACK_BERT, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, nullptr, n_doc, d_part_doc_off, n_part,
                      target_seq_length, short_seq_prob, duplicate_factor, seed, bin_size, out_totals, stream, d_ids,
                      masking, masked_lm_ratio);
 }
@@ -276,7 +281,16 @@ extern "C" int lddl_pack_codebert(lddl_ctx* c, lddl_pack* pk, const int32_t* d_n
                                   const int64_t* d_part_doc_off, int64_t n_part, int32_t target_seq_length,
                                   double short_seq_prob, int32_t duplicate_factor, uint64_t seed, int32_t bin_size,
                                   int64_t* out_totals, void* stream) {
-  return pack_common(c, pk, 1, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, d_doc_nseg_doc, n_doc, d_part_doc_off,
+  return pack_common(c, pk, PACK_CODEBERT, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, d_doc_nseg_doc, n_doc, d_part_doc_off,
+                     n_part, target_seq_length, short_seq_prob, duplicate_factor, seed, bin_size, out_totals, stream);
+}
+
+extern "C" int lddl_pack_mlm(lddl_ctx* c, lddl_pack* pk, const int32_t* d_ntok, const int64_t* d_tok_off,
+                             const int64_t* d_sent_off, int64_t n_sent, const int64_t* d_doc_sent_off, int64_t n_doc,
+                             const int64_t* d_part_doc_off, int64_t n_part, int32_t target_seq_length,
+                             double short_seq_prob, int32_t duplicate_factor, uint64_t seed, int32_t bin_size,
+                             int64_t* out_totals, void* stream) {
+  return pack_common(c, pk, PACK_MLM, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, nullptr, n_doc, d_part_doc_off,
                      n_part, target_seq_length, short_seq_prob, duplicate_factor, seed, bin_size, out_totals, stream);
 }
 

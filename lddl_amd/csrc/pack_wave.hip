@@ -535,7 +535,7 @@ __device__ __forceinline__ int find_fill_reg(int dps, int dex, int tot, int k0, 
   return j;
 }
 
-// ---- what the two packers share around their generate loops --------------
+// ---- what the packers share around their generate loops ------------------
 // the partition a packer wave works on: ndoc documents from d0, nsent
 // sentences from s0, its pair arrays from pb
 struct PartOpen {
@@ -1404,6 +1404,37 @@ __device__ __forceinline__ void trunc_seq_wave(WaveRng& rng, PackWaveLds& L, int
   }
 }
 
+// The CodeBERT and MLM-only packers' sentence filter: kept_before[k] = #kept
+// (non-empty) sentences before sentence s0 + k of the partition (k <= nsent)
+// by a running wave scan, and fs_ntok / fs_base / fs_dense per kept slot.
+// Returns kept_before, its stores visible to the wave.
+__device__ __forceinline__ int32_t* filter_slots(const PackParams& P, const PartOpen& O, int64_t p, int lane) {
+  const int64_t s0 = O.s0;
+  const int64_t base = P.sent_off[0];
+  const int nsent = O.nsent;
+  int32_t* kept_before = P.kept + s0 + p;
+  int run = 0;
+  for (int k = 0; k < nsent; k += 64) {
+    const int kk = k + lane;
+    const int n = kk < nsent ? P.ntok[s0 + kk] : 0;
+    const int keep = (kk < nsent && n > 0) ? 1 : 0;
+    const int incl = wave_incl_add(keep);
+    if (kk < nsent) {
+      const int slot = run + incl - keep;
+      kept_before[kk] = slot;
+      if (keep) {
+        P.fs_ntok[s0 + slot] = (uint16_t)n;
+        P.fs_base[s0 + slot] = P.sent_off[s0 + kk] - base;
+        P.fs_dense[s0 + slot] = P.tokoff[s0 + kk];
+      }
+    }
+    run += lane_get(incl, 63);
+  }
+  if (lane == 0) kept_before[nsent] = run;
+  group_sync();
+  return kept_before;
+}
+
 __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
   __shared__ PackWaveLds L;
   const int lane = threadIdx.x;
@@ -1411,31 +1442,9 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
   if (p >= P.n_part) return;
   const PartOpen O = open_part(P, p);
   const int64_t d0 = O.d0, s0 = O.s0, pb = O.pb;
-  const int64_t base = P.sent_off[0];
-  const int nsent = O.nsent, ndoc = O.ndoc;
+  const int ndoc = O.ndoc;
   // ---- filter: kept segment slots (wave scan), kept documents ------------
-  int32_t* kept_before = P.kept + s0 + p;
-  {
-    int run = 0;
-    for (int k = 0; k < nsent; k += 64) {
-      const int kk = k + lane;
-      const int n = kk < nsent ? P.ntok[s0 + kk] : 0;
-      const int keep = (kk < nsent && n > 0) ? 1 : 0;
-      const int incl = wave_incl_add(keep);
-      if (kk < nsent) {
-        const int slot = run + incl - keep;
-        kept_before[kk] = slot;
-        if (keep) {
-          P.fs_ntok[s0 + slot] = (uint16_t)n;
-          P.fs_base[s0 + slot] = P.sent_off[s0 + kk] - base;
-          P.fs_dense[s0 + slot] = P.tokoff[s0 + kk];
-        }
-      }
-      run += lane_get(incl, 63);
-    }
-    if (lane == 0) kept_before[nsent] = run;
-  }
-  group_sync();
+  int32_t* kept_before = filter_slots(P, O, p, lane);
   // a document is kept when it has a kept code segment (len(CodePair) > 0,
   // pretrain_codebert.py:161); its first fd_nd kept slots are docstring
   int nd_docs = 0;
@@ -1539,6 +1548,100 @@ __global__ __launch_bounds__(64) void pack_codebert_wave_kernel(PackParams P) {
 
 hipError_t launch_pack_codebert_wave(const PackParams& P, hipStream_t s) {
   hipLaunchKernelGGL(pack_codebert_wave_kernel, dim3((unsigned)P.n_part), dim3(64), 0, s, P);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------- MLM-only ----
+// Single-segment rows without NSP: [CLS] s_i .. s_j [SEP], consecutive
+// sentences of one document (DESIGN.md "MLM-only rows" holds the row
+// definition).  The reference has no such mode; the draws are its building
+// blocks in its order: the short_seq_prob draw of create_pairs_from_document
+// (pretrain.py:259-265), one coin per excess token (:161-179), random.shuffle
+// of the partition's rows (:401), binning.py:63-93.  One wave per partition,
+// in the CodeBERT packer's shape: its filter, find_over for "accumulate
+// sentences until the chunk reaches the target", trunc_seq_wave, then the
+// shared shuffle and binning over global-memory arrays.  A row is the
+// CodeBERT packer's docstring-less record: n0 = 0, lo0 = hi0 = 0, flags = 0.
+// No error path: a kept sentence has >= 1 token and max_num >= 3, so a chunk
+// is never empty before or after truncation.
+// Capacities: a duplicate pass emits <= one row per kept sentence (every
+// chunk holds >= 1), so np <= dup * nsent, the partition's record slots.  A
+// chunk's length before truncation is < target + its last sentence's tokens
+// <= 32766 + 65535 (fs_ntok is u16): an int.  n1 <= target (k sentences hold
+// >= k tokens and the first k - 1 stay below target).  hi1 <= that length,
+// which fits u16 for sentences of <= 32768 tokens (lddl_amd.h); hi1 - lo1 <=
+// max_num, num_tokens <= max_seq <= 32768.
+__global__ __launch_bounds__(64) void pack_mlm_wave_kernel(PackParams P) {
+  __shared__ PackWaveLds L;
+  const int lane = threadIdx.x;
+  const int64_t p = blockIdx.x;
+  if (p >= P.n_part) return;
+  const PartOpen O = open_part(P, p);
+  const int64_t d0 = O.d0, s0 = O.s0, pb = O.pb;
+  const int ndoc = O.ndoc;
+  // ---- filter: kept sentence slots (wave scan), documents with >= 1 -------
+  int32_t* kept_before = filter_slots(P, O, p, lane);
+  int nd_docs = 0;
+  for (int k = 0; k < ndoc; k += 64) {
+    const int kk = k + lane;
+    int first = 0, cnt = 0;
+    if (kk < ndoc) {
+      const int a = (int)(P.doc_sent_off[d0 + kk] - s0), b = (int)(P.doc_sent_off[d0 + kk + 1] - s0);
+      first = kept_before[a];
+      cnt = kept_before[b] - first;
+    }
+    const int keep = (kk < ndoc && cnt > 0) ? 1 : 0;
+    const int incl = wave_incl_add(keep);
+    if (keep) {
+      const int di = nd_docs + incl - 1;
+      P.fd_first[d0 + di] = s0 + first;
+      P.fd_n[d0 + di] = cnt;
+    }
+    nd_docs += lane_get(incl, 63);
+  }
+  group_sync();
+  auto len_abs = [&](int64_t slot) -> int { return P.fs_ntok[slot]; };
+
+  WaveRng rng{L, lane, MT_N};
+  rng.load(P.mt_states + (int64_t)p * MT_N);
+  const int max_num = P.max_seq - 2;
+  PairRec* out = P.pairs + pb;
+  int np = 0;
+  for (int dup = 0; dup < P.dup; ++dup) {
+    for (int di = 0; di < nd_docs; ++di) {
+      const int64_t first = P.fd_first[d0 + di];
+      const int n = P.fd_n[d0 + di];
+      int target = max_num;
+      if (rng.random() < P.short_seq_prob) target = (int)rng.randint(2, max_num);
+      // chunks [cs, i]: flushed at the document's last sentence or once the
+      // chunk holds >= target tokens
+      int cs = 0;
+      while (cs < n) {
+        int cur;
+        const int i = find_over([&](int k) { return len_abs(first + k); }, cs, n, n - 1, 0, target - 1, lane, &cur);
+        int lo = 0, hi = cur;
+        trunc_seq_wave(rng, L, lane, lo, hi, max_num);
+        if (lane == 0) {
+          PairRec r;
+          r.fs0 = first; r.n0 = 0; r.lo0 = 0; r.hi0 = 0;
+          r.fs1 = first + cs; r.n1 = (uint16_t)(i - cs + 1); r.lo1 = (uint16_t)lo; r.hi1 = (uint16_t)hi;
+          r.flags = 0;
+          r.num_tokens = (uint16_t)((hi - lo) + 2);
+          out[np] = r;
+        }
+        ++np;
+        cs = i + 1;
+      }
+    }
+  }
+  if (lane == 0) P.part_err[p] = PACK_OK;
+  group_sync();
+  shuffle_pairs<false>(P, O, PackDyn{}, rng, p, np, lane);
+  bin_pairs<0, false>(P, O, PackDyn{}, p, np, lane);
+}
+
+hipError_t launch_pack_mlm_wave(const PackParams& P, hipStream_t s) {
+  hipLaunchKernelGGL(pack_mlm_wave_kernel, dim3((unsigned)P.n_part), dim3(64), 0, s, P);
   return hipGetLastError();
 }
 

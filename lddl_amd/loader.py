@@ -21,6 +21,10 @@ code / num_tokens, pretrain_codebert.py:425-433), for which the reference has
 no loader at all: ``collate_rows`` / ``collate_rows_unpadded`` over a CodeBERT
 pack result, ``load_rows`` / ``load_shards`` over CodeBERT shards.
 
+``MlmCollate`` is that surface over the BERT vocabulary for MLM-only rows
+(``Packer.pack(..., nsp=False)`` / ``preprocess --no-nsp``: ``[CLS] tokens
+[SEP]``, shards of A / num_tokens): no pair, no next_sentence_labels.
+
 Differences from the reference, by design:
 * dynamic masking draws from a counter-based hash of (seed, batch counter, row,
   column), not torch's CPU generator: the same distribution (mask rate
@@ -102,6 +106,24 @@ def _code_shard_columns(table):
   return cols, np.concatenate(nt).astype(np.uint16)
 
 
+def _mlm_shard_columns(table):
+  """MlmCollate.load_rows' input -> ([empty doc, A] as (bytes, offsets), num_tokens uint16)"""
+  table = list([table] if hasattr(table, 'schema') else table)
+  if not table:
+    raise ValueError('no rows')
+  for t in table:
+    names = t.schema.names if hasattr(t, 'schema') else ()
+    if 'A' not in names or 'num_tokens' not in names or 'B' in names:
+      raise ValueError('not an MLM-only shard (columns %s): A and num_tokens without B are needed; BertCollate loads '
+                       'BERT shards, CodeCollate CodeBERT shards' % (list(names),))
+  a = _merge_columns([_arrow_column(t.column('A')) for t in table])
+  nt = [np.asarray(t.column('num_tokens').to_numpy(zero_copy_only=False)) for t in table]
+  if any(len(x) and (x.min() < 0 or x.max() > 65535) for x in nt):
+    raise ValueError('num_tokens outside uint16')
+  nt = np.concatenate(nt).astype(np.uint16)
+  return [(np.zeros(0, np.uint8), np.zeros(len(nt) + 1, np.int64)), a], nt
+
+
 def _shard_columns(table):
   """load_rows' input -> ([A, B(, positions, labels)] as (bytes, offsets), is_random_next bytes, static)"""
   if hasattr(table, 'schema'):
@@ -116,7 +138,8 @@ def _shard_columns(table):
     return _sample_columns(table, static) + (static,)
   for t in table:
     if 'A' not in t.schema.names or 'B' not in t.schema.names:
-      raise ValueError('not a BERT shard (columns %s): CodeBERT shards are loaded by CodeCollate' % (t.schema.names,))
+      raise ValueError('not a BERT shard (columns %s): CodeBERT shards are loaded by CodeCollate, MLM-only shards '
+                       '(A without B) by MlmCollate' % (t.schema.names,))
   static = 'masked_lm_positions' in table[0].schema.names
   for t in table:
     if ('masked_lm_positions' in t.schema.names) != static or (static and 'masked_lm_labels' not in t.schema.names):
@@ -213,8 +236,9 @@ class _RowCollate:
   """What BertCollate and CodeCollate share: the constructor, the staging of
   string columns, the collate of row-table batches (padded and padding-free),
   the making of a row table and ``mask_tokens``.  CODE says which kind of row
-  the C calls are for."""
+  the C calls are for, KIND the PackResult.kind of the tables it loads."""
   CODE = False
+  KIND = 'bert'
   VOCAB = _lib.VOCAB_BERT
 
   def __init__(self, vocab_file=None, device=None, sequence_length_alignment=8, ignore_index=-1,
@@ -278,6 +302,8 @@ class _RowCollate:
 
   def _row_batch(self, who, res, rows, row0, n_rows, mode):
     """what collate_rows / collate_rows_unpadded (who) take -> (mode, rows, row0, n)"""
+    if res.kind == 'mlm' and not self.CODE:
+      raise ValueError('%s: MLM-only rows (nsp=False) have no pair and no NSP label: MlmCollate collates them' % who)
     if not res.spans:
       raise ValueError('%s needs a PackResult with spans (Packer.pack(..., spans=True))' % who)
     if mode is None:
@@ -401,6 +427,7 @@ class _RowCollate:
                      h2d(bin_count))
     res.ids, res.src0, res.src1 = ids, src0, src1
     res.cls_id, res.sep_id = self.tok.cls_id, self.tok.sep_id
+    res.kind = self.KIND
     if static:
       res.n_masked = n_masked
       res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token = mlm_off, mlm[0], mlm[1], mlm[2]
@@ -476,7 +503,7 @@ class BertCollate(_RowCollate):
   collate_fn (tuples of 3 or 5 fields), or a pyarrow RecordBatch / Table of
   the shard schema (zero-copy columns; ``collate_arrow``)."""
   SHARD_COLUMNS, SHARD_KIND = ('A', 'B'), 'BERT'
-  OTHER_SHARDS = 'CodeBERT shards are loaded by CodeCollate'
+  OTHER_SHARDS = 'CodeBERT shards are loaded by CodeCollate, MLM-only shards (A without B) by MlmCollate'
 
   def _run(self, cols, is_random_next, static, mode=None):
     """lddl_collate_seq_len + lddl_collate_bert over staged columns.  mode None:
@@ -593,6 +620,7 @@ class CodeCollate(_RowCollate):
   no next_sentence_labels and no static masking; mode defaults to dynamic and
   draws as BertCollate does, keyed by (seed, batch counter, row, column)."""
   CODE = True
+  KIND = 'codebert'
   VOCAB = _lib.VOCAB_CODEBERT
   SHARD_COLUMNS, SHARD_KIND = ('doc', 'code', 'num_tokens'), 'CodeBERT'
   OTHER_SHARDS = 'BERT shards are loaded by BertCollate'
@@ -626,6 +654,37 @@ class CodeCollate(_RowCollate):
     any other value is refused.  bins / part / nbins as there."""
     cols, nt = _code_shard_columns(table)
     return self._load_table(cols, nt, False, bins, part, nbins)
+
+
+class MlmCollate(CodeCollate):
+  """The loader of MLM-only rows (``Packer.pack(..., nsp=False)``,
+  ``preprocess --no-nsp``): consecutive sentences of one document as
+  ``[CLS] tokens [SEP]``, for recipes that train without NSP.  CodeCollate's
+  surface over the BERT vocabulary: ``collate_rows`` /
+  ``collate_rows_unpadded`` over an MLM-only pack result, ``load_rows`` /
+  ``load_shards`` over MLM-only shards (A, num_tokens), ``whole_word_mask``
+  and ``compact_mlm`` as on the other classes.  Batches hold input_ids,
+  token_type_ids (all 0), attention_mask (unpadded: position_ids, cu_seqlens,
+  max_seqlen) and labels (mode 0: special_tokens_mask); there is no
+  next_sentence_labels.  Such a row is a CodeBERT row without docstring, so
+  the calls are CodeCollate's (lddl_collate_code_rows*,
+  lddl_code_rows_from_strings*)."""
+  KIND = 'mlm'
+  VOCAB = _lib.VOCAB_BERT
+  SHARD_COLUMNS, SHARD_KIND = ('A', 'num_tokens'), 'MLM-only'
+  OTHER_SHARDS = 'BERT shards are loaded by BertCollate, CodeBERT shards by CodeCollate'
+
+  def load_rows(self, table, bins=None, part=None, nbins=None):
+    """The rows of an MLM-only shard as a GPU row table, once: a pyarrow
+    Table / RecordBatch with A (string or large_string) and num_tokens
+    columns and no B, or a list of such tables.  A goes to the code segment
+    beside an empty doc column; num_tokens must be len(A.split()) + 2.
+    bins / part / nbins as ``BertCollate.load_rows``."""
+    cols, nt = _mlm_shard_columns(table)
+    res = self._load_table(cols, nt, False, bins, part, nbins)
+    if bool(res.flags[:res.n_pairs].any()):  # (len + 3: the C call reads a [SEP] after the empty doc segment)
+      raise ValueError('an MLM-only row whose num_tokens is not len(A.split()) + 2')
+    return res
 
 
 def plan_row_batches(bins, batch_size, seed=12345, epoch=0, drop_last=False, n_rows=None):

@@ -276,6 +276,11 @@ def attach_args(parser=None, codebert=False):
                  'bundled bert-base-uncased (BERT) or codebert_52000 (CodeBERT) vocab')
   attach_bool_arg(p, 'masking', default=False, help_str='static masking (pretrain.py:859-866)')
   p.add_argument('--masked-lm-ratio', type=float, default=0.15)
+  if not codebert:
+    attach_bool_arg(p, 'nsp', default=True,
+                    help_str='--no-nsp: MLM-only rows, [CLS] consecutive sentences of one document [SEP], written as '
+                             'A / num_tokens shards for loader.MlmCollate (no B, no NSP label; this front end\'s '
+                             'own flag, not with --masking or --output-format txt)')
   p.add_argument('--sentence-splitter', type=str, default='auto', choices=['auto', 'punkt', 'rules'])
   attach_split_device_arg(p)
   p.add_argument('--chunk-mb', type=float, default=32.0,
@@ -305,6 +310,8 @@ def run_key(args, codebert, files, vocab, how, n_part):
   keys = ['target_seq_length', 'short_seq_prob', 'block_size', 'num_blocks', 'bin_size', 'sample_ratio', 'seed',
           'duplicate_factor', 'masking', 'masked_lm_ratio', 'output_format', 'wikipedia_lang']
   d = {k: getattr(args, k, None) for k in keys}
+  if not getattr(args, 'nsp', True):  # (only then: the keys of runs without the flag stay what they were)
+    d['nsp'] = False
   d.update(codebert=codebert, splitter=how, n_part=n_part, vocab=os.path.abspath(vocab),
            vocab_size=os.path.getsize(vocab),
            files=[(os.path.abspath(f), os.path.getsize(f), os.stat(f).st_mtime_ns) for f in files])
@@ -360,7 +367,21 @@ def save_marker(sink, a, b, key, files, counts, n_pairs):
   os.replace(tmp, p)
 
 
+def _check_nsp(args):
+  """--no-nsp packs MLM-only rows: no static masking (MlmCollate masks dynamically) and no txt sink; -> the
+  complaint, or None"""
+  if getattr(args, 'nsp', True):
+    return None
+  if getattr(args, 'masking', False):
+    return '--no-nsp does not go with --masking: MLM-only rows are masked dynamically by loader.MlmCollate'
+  if args.output_format == 'txt':
+    return '--no-nsp writes parquet shards only, not --output-format txt'
+  return None
+
+
 def _check(args):
+  if _check_nsp(args):
+    raise ValueError(_check_nsp(args))
   if args.output_format == 'txt' and getattr(args, 'num_shards', None):
     raise ValueError('--num-shards balances parquet shards; it does not apply to --output-format txt')
   if args.bin_size is not None:
@@ -796,6 +817,7 @@ def main(args, codebert=False):
   if not os.path.isfile(vocab):
     raise ValueError('--vocab-file must be a local vocab.txt (no hub access): %s' % vocab)
   masking = args.masking and not codebert
+  nsp = codebert or getattr(args, 'nsp', True)  # (False: MLM-only rows, the BERT sub-command's --no-nsp)
   t = {}
   wall0 = t0 = time.perf_counter()
   gloo = _dist_init(world)
@@ -859,7 +881,7 @@ def main(args, codebert=False):
         res = pk.pack(sh, ids_d, ntok, toff, target_seq_length=args.target_seq_length,
                       short_seq_prob=args.short_seq_prob, duplicate_factor=args.duplicate_factor, seed=args.seed + a,
                       bin_size=args.bin_size, codebert=codebert, masking=masking,
-                      masked_lm_ratio=args.masked_lm_ratio, spans=True)
+                      masked_lm_ratio=args.masked_lm_ratio, spans=True, nsp=nsp)
         counts[a - lo:b - lo] = res.bin_count.view(b - a, -1).to(torch.int64)
         torch.cuda.synchronize()
         t['gpu_s'] += time.perf_counter() - t0
@@ -870,7 +892,7 @@ def main(args, codebert=False):
         if ws.enc is None:
           wrote = writer.write_txt(pk, res, sink, **kw)
         else:
-          wrote = writer.write_shards(pk, res, sink, executor=ws.enc, pending=cf, **kw)
+          wrote = writer.write_shards(pk, res, sink, executor=ws.enc, pending=cf, nsp=nsp, **kw)
           for k_ in ('setup_s', 'render_s', 'table_s'):  # (the writer's stages: table_s = slot copies + hand-off)
             t['writer_' + k_] = t.get('writer_' + k_, 0.0) + writer.LAST_STATS.get(k_, 0.0)
         out += wrote
@@ -910,8 +932,17 @@ def _run(fn, *args):
   print('Running the pipeline took {} s'.format(time.perf_counter() - tic))
 
 
+def parse_args(argv=None, codebert=False):
+  """the BERT / CodeBERT sub-command's arguments; a flag combination that cannot run is an argument error"""
+  p = attach_args(codebert=codebert)
+  args = p.parse_args(argv)
+  if _check_nsp(args):
+    p.error(_check_nsp(args))
+  return args
+
+
 def console_script(argv=None, codebert=False):
-  _run(main, attach_args(codebert=codebert).parse_args(argv), codebert)
+  _run(main, parse_args(argv, codebert), codebert)
 
 
 # ----------------------------------------------------------------- BART --

@@ -12,6 +12,8 @@ written even when empty, binning.py:353-431):
             [, bin_id int64]                               pretrain.py:450-498
   CodeBERT  id string, doc string, code string, num_tokens uint16
             [, bin_id int64]                       pretrain_codebert.py:495-537
+  MLM-only  A string, num_tokens uint16 [, bin_id int64]
+            (nsp=False: single-segment rows, no counterpart in the reference)
 
 Here the rows of a pack call are already in file order on the device
 (partition-major, bin-major, shuffled order within a bin), so a file is a
@@ -41,10 +43,17 @@ BERT_SCHEMA = [('A', pa.string()), ('B', pa.string()), ('is_random_next', pa.boo
                ('num_tokens', pa.uint16())]
 MLM_SCHEMA = [('masked_lm_positions', pa.binary()), ('masked_lm_labels', pa.string())]
 CODEBERT_SCHEMA = [('id', pa.string()), ('doc', pa.string()), ('code', pa.string()), ('num_tokens', pa.uint16())]
+MLM_ONLY_SCHEMA = [('A', pa.string()), ('num_tokens', pa.uint16())]
 
 
-def schema(codebert=False, masking=False, binned=False):
-  f = list(CODEBERT_SCHEMA if codebert else BERT_SCHEMA)
+def _check_nsp(nsp, codebert, masking):
+  if not nsp and (codebert or masking):
+    raise ValueError('nsp=False (MLM-only rows) goes with neither codebert nor static masking')
+
+
+def schema(codebert=False, masking=False, binned=False, nsp=True):
+  _check_nsp(nsp, codebert, masking)
+  f = list(CODEBERT_SCHEMA if codebert else BERT_SCHEMA if nsp else MLM_ONLY_SCHEMA)
   if masking and not codebert:
     f += MLM_SCHEMA
   if binned:
@@ -115,6 +124,15 @@ def seg_columns(packer, res, r0, n, codebert=False, stream=None, host=True):
   kw = dict(len0=res.len0, len1=res.len1, flags=res.flags, codebert=codebert, stream=stream, host=host)
   return (render(packer, res.tokens, res.tok_off, r0, n, SEG0, **kw),
           render(packer, res.tokens, res.tok_off, r0, n, SEG1, **kw))
+
+
+def mlm_only_column(packer, res, r0, n, stream=None, host=True):
+  """the one string column (A) of MLM-only rows [r0, r0 + n): their segment 1,
+  which no [SEP] precedes (the CodeBERT layout of a row without docstring)"""
+  if res.spans:
+    return render(packer, res.ids, res.src1, r0, n, SPAN, len0=res.len1, stream=stream, host=host)
+  return render(packer, res.tokens, res.tok_off, r0, n, SEG1, len0=res.len0, len1=res.len1, flags=res.flags,
+                codebert=True, stream=stream, host=host)
 
 
 def row_docs(packer, res, n_copy=None, stream=None):
@@ -536,9 +554,11 @@ LAST_STATS = {}  # the last write_shards call's stage seconds (bench.py reports 
 
 def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=False, doc_ids=None,
                  part_base=0, compression='snappy', batch_rows=1 << 16, max_parts=None, stream=None,
-                 executor=None, pending=None):
+                 executor=None, pending=None, nsp=True):
   """Write the rows of ``res`` (a pipeline.PackResult) as the reference's
-  parquet files under out_dir.  Partition p of this pack call is file
+  parquet files under out_dir.  nsp=False: ``res`` holds MLM-only rows
+  (``Packer.pack(..., nsp=False)``); the files have the same names and hold
+  A (the row's tokens) and num_tokens, no B, is_random_next or id.  Partition p of this pack call is file
   ``part.{part_base + p}.parquet`` (unbinned) or ``part.{..}.parquet_{b}``
   for every bin b (binned).  doc_ids: CodeBERT 'id' strings (list or Arrow array) per document of
   the packed corpus.  max_parts: only the first max_parts partitions.
@@ -552,12 +572,16 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
   Returns the list of files (written once the futures are done)."""
   t_start = time.perf_counter()
   EncodeSink.check(executor, pending)
+  _check_nsp(nsp, codebert, masking)
+  kind = getattr(res, 'kind', 'bert')
+  if (kind == 'mlm') == bool(nsp):
+    raise ValueError('nsp=%s with a %r pack result' % (bool(nsp), kind))
   os.makedirs(out_dir, exist_ok=True)
   binned = bin_size is not None
   masking = masking and not codebert
   plan = pack_plan(res, bin_size, max_parts, part_base)
   assert plan.file_start[-1] == res.n_pairs, (plan.file_start[-1], res.n_pairs)
-  sch = schema(codebert, masking, binned)
+  sch = schema(codebert, masking, binned, nsp)
   # dictionary pages only where values repeat (flags, lengths, bins, the
   # CodeBERT id of a document's rows): the segment / label strings are unique
   # per row and the encoder would build and then discard a dictionary for them
@@ -584,7 +608,10 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
     flist = plan.files(f, g, out_dir, 'parquet')
     files.extend(f_[0] for f_ in flist)
     t0 = time.perf_counter()
-    var = dict(zip((seg0, seg1), seg_columns(packer, res, r0, n, codebert, stream, host=sink.host)))
+    if nsp:
+      var = dict(zip((seg0, seg1), seg_columns(packer, res, r0, n, codebert, stream, host=sink.host)))
+    else:
+      var = {'A': mlm_only_column(packer, res, r0, n, stream, host=sink.host)}
     if masking:
       var['masked_lm_labels'] = render(packer, res.mlm_label, res.mlm_off, r0, n, ROW, stream=stream, host=sink.host)
       var['masked_lm_positions'] = mlm_positions(packer, res, r0, r1, n_rows, host_mlm, stream, host=sink.host)
@@ -619,7 +646,7 @@ def encode_workers():
 
 
 def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False, doc_ids=None, part_base=0,
-              batch_rows=1 << 20, max_parts=None, stream=None):
+              batch_rows=1 << 20, max_parts=None, stream=None, nsp=True):
   """The reference's txt sink (--output-format txt, pretrain.py:501-531,
   pretrain_codebert.py:540-559): one line per row,
 
@@ -632,7 +659,10 @@ def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False
   {p}.txt per partition (to_textfiles' default name), or {p}_{b}.txt for
   every bin b (binning.py:439-476: the bin parsed back from the line's last
   field, rows in shuffled order within a bin == this packer's row order).
-  Every file is created, empty ones included.  Returns the files."""
+  Every file is created, empty ones included.  Returns the files.
+  MLM-only rows (nsp=False) have no txt form: ValueError."""
+  if not nsp:
+    raise ValueError('write_txt: MLM-only rows (nsp=False) are written as parquet only')
   os.makedirs(out_dir, exist_ok=True)
   plan = pack_plan(res, bin_size, max_parts, part_base)
   n_rows = plan.n_rows

@@ -83,7 +83,12 @@ int lddl_vocab_token(const lddl_ctx *ctx, int32_t id, char *buf, int64_t cap);
  * finds d_out_tok_off[n_sent] > out_cap calls again with a larger buffer;
  * out_cap >= nbytes always suffices (#tokens <= #bytes).  nbytes must be >=
  * d_sent_off[n_sent] - d_sent_off[0]; 1 <= max_tok <= 65534.  d_bytes:
- * 4-byte aligned.  lddl_pack_* / lddl_materialize read d_out_ids with 16-B
+ * 4-byte aligned.  The scan reads from the 16-byte boundary at or below
+ * d_bytes + d_sent_off[s], which for a d_bytes that is not 16-byte aligned
+ * lies up to 12 bytes in front of d_bytes: a stated property, harmless
+ * because an allocation starts 16-byte aligned, so such a d_bytes is always
+ * interior to one.  d_sent_off[0] need not be 0; d_out_ids may be NULL when
+ * out_cap is 0.  lddl_pack_* / lddl_materialize read d_out_ids with 16-B
  * loads: keep it 16-B aligned with 16 entries of padding past the total. */
 int lddl_tokenize(lddl_ctx *ctx, const uint8_t *d_bytes, int64_t nbytes, const int64_t *d_sent_off,
                   int64_t n_sent, int32_t max_tok, uint16_t *d_out_ids, int64_t out_cap, int32_t *d_out_ntok,

@@ -484,6 +484,56 @@ int lddl_collate_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64
                                int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
                                int64_t *d_labels, int64_t *d_next_sentence_labels, void *stream);
 
+/* ---- fixed-shape padding-free collate --------------------------------------
+ * The padding-free batch in outputs whose sizes do not depend on the batch,
+ * offsets and fill in one call, one launch and one synchronise: for a trainer
+ * that wants every tensor of a step at a fixed shape (one hipBLASLt problem
+ * size, a step that is captured or compiled once).  No counterpart in the
+ * reference (lddl/torch/bert.py:69-153 pads rows, never the stream).  Three
+ * capacities: tok_cap = T tokens, seq_cap = N sequence slots, max_seqlen = S,
+ * the longest sequence the attention call is told about.  The four token
+ * outputs are [T], d_cu_seqlens is an output, int32 [N + 1], and
+ * next_sentence_labels is [N].  With the n = n_rows rows picked as in
+ * lddl_collate_rows_unpadded, n_r tokens each, total = sum of n_r:
+ *
+ * Real rows.  Outputs [0, total), cu_seqlens[0 .. n] and
+ * next_sentence_labels[0 .. n) are those of lddl_collate_rows_cu_seqlens +
+ * lddl_collate_rows_unpadded for the same rows, mode, ignore_index,
+ * mlm_probability, seed, counter and whole-word switch, bit for bit.
+ *
+ * Slack.  [total, T) is cut into p = ceil((T - total) / S) pad sequences in
+ * slots n .. n + p - 1, each of S tokens but possibly the last, so that no
+ * token of the stream lies outside a sequence.  A pad token at offset j of its
+ * pad sequence has input_ids 0, token_type_ids 0, position_ids j and labels
+ * ignore_index (mode 0: special_tokens_mask 1, as on the pad columns of
+ * lddl_collate_rows).  Slots n + p .. N - 1 are empty: cu_seqlens[r] = T for
+ * n + p <= r <= N; cu_seqlens[N] is always T.  next_sentence_labels[r] =
+ * ignore_index for r >= n.
+ *
+ * *out_total = total, *out_n_rows = n, *out_n_seqs = n + p; d_status, int32
+ * [4] on the device, receives {total, n, n + p, S} for a trainer that reads
+ * them without the host.  Synchronises the stream.
+ *
+ * Errors, a row's before the capacities' and among rows the first one wins,
+ * none faults, and nothing is stored outside the capacities in any case:
+ * LDDL_ECAPACITY (total > T, with total in
+ * *out_total, and the rows that would pass T left unwritten; a row longer than
+ * S, left unwritten; n + p > N; n > N; S not in [3, 2048]; T > INT32_MAX;
+ * N not in [1, 2^20]), LDDL_EINDEX (a row index outside [0, n_total), checked
+ * before any load through it; a static position >= n_r), LDDL_EINVAL
+ * (n_rows <= 0, null pointers, mode not in 0..2, mlm_probability not in
+ * [0, 1], a row whose flags lack bit 1: a CodeBERT row). */
+int lddl_collate_rows_fixed(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                            const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                            const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                            const int64_t *d_mlm_off, const uint16_t *d_mlm_pos, const uint16_t *d_mlm_label,
+                            const uint16_t *d_mlm_token, int32_t *d_cu_seqlens, int64_t tok_cap, int64_t seq_cap,
+                            int64_t max_seqlen, int32_t mode, int64_t ignore_index, double mlm_probability,
+                            uint64_t seed, uint64_t counter, int64_t *d_input_ids, int64_t *d_token_type_ids,
+                            int64_t *d_position_ids, int64_t *d_labels, int64_t *d_next_sentence_labels,
+                            int32_t *d_status, int64_t *out_total, int64_t *out_n_rows, int64_t *out_n_seqs,
+                            void *stream);
+
 /* ---- collate CodeBERT rows straight from a pack result ----------------------
  * The four calls above for the rows of lddl_pack_codebert (or of
  * lddl_code_rows_from_strings): the row pretrain_codebert.py:425-433 saves as
@@ -561,6 +611,22 @@ int lddl_collate_code_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const 
                                     int64_t ignore_index, double mlm_probability, uint64_t seed, uint64_t counter,
                                     int64_t *d_input_ids, int64_t *d_token_type_ids, int64_t *d_position_ids,
                                     int64_t *d_labels, void *stream);
+
+/* lddl_collate_rows_fixed for CodeBERT rows (pretrain_codebert.py:425-433; no
+ * loader in the reference): the real part is lddl_collate_code_rows_cu_seqlens +
+ * lddl_collate_code_rows_unpadded, bit for bit in modes 0 and 2; the slack, the
+ * cu_seqlens tail, d_status and the three counts as there.  No static arrays
+ * and no next_sentence_labels.  Errors as there, with max_seqlen in [2, 2048],
+ * a mode other than 0 or 2 LDDL_EINVAL, and LDDL_EINVAL for a row with s = 0
+ * and a > 0 in place of the CodeBERT-row refusal. */
+int lddl_collate_code_rows_fixed(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                                 const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                                 const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                 int32_t *d_cu_seqlens, int64_t tok_cap, int64_t seq_cap, int64_t max_seqlen,
+                                 int32_t mode, int64_t ignore_index, double mlm_probability, uint64_t seed,
+                                 uint64_t counter, int64_t *d_input_ids, int64_t *d_token_type_ids,
+                                 int64_t *d_position_ids, int64_t *d_labels, int32_t *d_status, int64_t *out_total,
+                                 int64_t *out_n_rows, int64_t *out_n_seqs, void *stream);
 
 /* ---- compact MLM targets ----------------------------------------------------
  * The masked positions of a batch and their labels, in order: what a trainer

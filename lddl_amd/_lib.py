@@ -74,6 +74,9 @@ SIGNATURES = {
                                              c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p]),
     'lddl_collate_rows_unpadded': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 5 +
                                    [c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] + [c_void_p] * 6),
+    'lddl_collate_rows_fixed': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 5 +
+                                [c_int64, c_int64, c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] +
+                                [c_void_p] * 6 + [ctypes.POINTER(c_int64)] * 3 + [c_void_p]),
     'lddl_rows_from_strings_len': (c_int, [c_void_p] * 9 + [c_int64] + [c_void_p] * 6 +
                                    [ctypes.POINTER(c_int64), c_void_p]),
     'lddl_rows_from_strings': (c_int, [c_void_p] * 10 + [c_int64] + [c_void_p] * 6 + [c_int64] + [c_void_p] * 4 +
@@ -86,6 +89,9 @@ SIGNATURES = {
                                                   ctypes.POINTER(c_int64), ctypes.POINTER(c_int64), c_void_p]),
     'lddl_collate_code_rows_unpadded': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] +
                                         [c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] + [c_void_p] * 5),
+    'lddl_collate_code_rows_fixed': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] +
+                                     [c_int64, c_int64, c_int64, c_int32, c_int64, c_double, c_uint64, c_uint64] +
+                                     [c_void_p] * 5 + [ctypes.POINTER(c_int64)] * 3 + [c_void_p]),
     'lddl_mlm_targets': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                  c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'lddl_code_rows_from_strings_len': (c_int, [c_void_p] * 6 + [c_int64] + [c_void_p] * 5 +

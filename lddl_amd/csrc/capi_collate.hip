@@ -1,5 +1,5 @@
 // C-ABI, host side of the training-time collate (kernels: collate.hip,
-// collate_rows.hip, collate_unpadded.hip, rows_from_strings.hip, mlm_targets.hip).
+// collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, rows_from_strings.hip, mlm_targets.hip).
 #include "capi_ctx.h"
 
 static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
@@ -170,11 +170,12 @@ static int collate_rows_error(uint32_t e, int64_t seq_len) {
   }
 }
 
-// collate_rows_error with the unpadded calls' wording where seq_len has no meaning
-static int collate_unpadded_error(uint32_t e) {
+// collate_rows_error with the unpadded calls' wording where seq_len has no meaning (max_len: the bound of a row, the
+// fixed calls' max_seqlen)
+static int collate_unpadded_error(uint32_t e, int64_t max_len = COLLATE_MAX_LEN) {
   const unsigned long long row = e >> 4;
   switch (e & 15u) {
-    case CERR_LONG: return set_err(LDDL_ECAPACITY, "batch row %llu longer than %d tokens", row, COLLATE_MAX_LEN);
+    case CERR_LONG: return set_err(LDDL_ECAPACITY, "batch row %llu longer than %lld tokens", row, (long long)max_len);
     case CERR_POS_RANGE: return set_err(LDDL_EINDEX, "batch row %llu: masked position beyond the row's tokens", row);
     default: return collate_rows_error(e, 0);
   }
@@ -227,12 +228,38 @@ extern "C" int lddl_collate_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, co
                                      stream);
 }
 
+// what lddl_collate[_code]_rows_fixed take beyond the unpadded fill call's arguments
+struct CollateFixedArgs {
+  int64_t tok_cap, seq_cap, max_seqlen;
+  int32_t* d_status;
+  int64_t *out_total, *out_n_rows, *out_n_seqs;
+};
+
+// the pad sequences that the slack of a fixed batch is cut into
+static int64_t fixed_pad_seqs(int64_t total, const CollateFixedArgs& F) {
+  return total < F.tok_cap ? (F.tok_cap - total + F.max_seqlen - 1) / F.max_seqlen : 0;
+}
+
+// collate_unpadded_error with the two refusals of the fixed calls
+static int collate_fixed_error(uint32_t e, int64_t total, int64_t n_rows, const CollateFixedArgs& F) {
+  switch (e & 15u) {
+    case CERR_TOK_CAP:
+      return set_err(LDDL_ECAPACITY, "the batch holds %lld tokens, tok_cap %lld", (long long)total, (long long)F.tok_cap);
+    case CERR_SEQ_CAP:
+      return set_err(LDDL_ECAPACITY, "%lld rows and %lld pad sequences of max_seqlen %lld, seq_cap %lld", (long long)n_rows,
+                     (long long)fixed_pad_seqs(total, F), (long long)F.max_seqlen, (long long)F.seq_cap);
+    default: return collate_unpadded_error(e, F.max_seqlen);
+  }
+}
+
 // lddl_collate_rows (unpadded 0: seq_len, d_attention_mask) and lddl_collate_rows_unpadded (1: d_cu_seqlens,
 // total, d_position_ids) validate their arguments and fill CollateRowsParams here, once.  The range check
 // between the mode and the probability checks, the launch and the wording of the device's errors are each
 // call's own; the arguments of the other call arrive as 0 / NULL and are passed on as that.  code 1: the
 // lddl_collate_code_rows[_unpadded] twins, CodeBERT rows: modes 0 and 2, no static arrays, no
-// d_next_sentence_labels, a row of two tokens at least, and an empty batch is refused.
+// d_next_sentence_labels, a row of two tokens at least, and an empty batch is refused.  F: the
+// lddl_collate[_code]_rows_fixed calls, unpadded 1 with total = tok_cap and seq_len = max_seqlen, both range
+// checks, d_cu_seqlens an output, the capacities' own checks and one launch that also makes the offsets.
 static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16_t* d_ids, const int64_t* d_src0,
                                const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
                                const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
@@ -241,18 +268,28 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
                                const int32_t* d_cu_seqlens, int64_t total, int32_t mode, int64_t ignore_index,
                                double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
                                int64_t* d_token_type_ids, int64_t* d_attention_mask, int64_t* d_position_ids,
-                               int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream) {
+                               int64_t* d_labels, int64_t* d_next_sentence_labels, void* stream,
+                               const CollateFixedArgs* F = nullptr) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   if (n_rows < 0 || n_total < 0) return set_err(LDDL_EINVAL, "negative n_rows / n_total");
-  if (code && n_rows == 0) return set_err(LDDL_EINVAL, "empty batch");
+  if ((code || F) && n_rows == 0) return set_err(LDDL_EINVAL, "empty batch");
   if (code && mode != COLLATE_SPECIAL_MASK && mode != COLLATE_DYNAMIC)
     return set_err(LDDL_EINVAL, "mode %d: CodeBERT rows have no static masks, the modes are 0 and 2", mode);
   if (mode < COLLATE_SPECIAL_MASK || mode > COLLATE_DYNAMIC) return set_err(LDDL_EINVAL, "mode %d not in 0..2", mode);
   const int min_len = code ? 2 : 3;
-  if (!unpadded && (seq_len < min_len || seq_len > COLLATE_MAX_LEN))
-    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [%d, %d]", (long long)seq_len, min_len, COLLATE_MAX_LEN);
-  if (unpadded && total < 0) return set_err(LDDL_EINVAL, "negative total");
-  if (unpadded && total > INT32_MAX) return set_err(LDDL_ECAPACITY, "total %lld: cu_seqlens are int32", (long long)total);
+  if ((!unpadded || F) && (seq_len < min_len || seq_len > COLLATE_MAX_LEN))
+    return set_err(LDDL_ECAPACITY, "%s %lld not in [%d, %d]", F ? "max_seqlen" : "seq_len", (long long)seq_len, min_len,
+                   COLLATE_MAX_LEN);
+  if (unpadded && total < 0) return set_err(LDDL_EINVAL, "negative %s", F ? "tok_cap" : "total");
+  if (unpadded && total > INT32_MAX)
+    return set_err(LDDL_ECAPACITY, "%s %lld: cu_seqlens are int32", F ? "tok_cap" : "total", (long long)total);
+  if (F) {
+    if (!F->d_status || !F->out_total || !F->out_n_rows || !F->out_n_seqs) return set_err(LDDL_EINVAL, "null pointer");
+    if (F->seq_cap < 1 || F->seq_cap > (1 << 20))
+      return set_err(LDDL_ECAPACITY, "seq_cap %lld not in [1, 2^20]", (long long)F->seq_cap);
+    if (n_rows > F->seq_cap)
+      return set_err(LDDL_ECAPACITY, "%lld rows, seq_cap %lld", (long long)n_rows, (long long)F->seq_cap);
+  }
   if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
   if (n_rows > 0 && (!d_ids || !d_src0 || !d_src1 || !d_len0 || !d_len1 || !d_flags || !d_input_ids || !d_token_type_ids ||
                      (unpadded ? !d_cu_seqlens || !d_position_ids : !d_attention_mask) || !d_labels ||
@@ -293,6 +330,32 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
   U.total = total;
   int rc;
   uint32_t e;
+  if (F) {
+    // one buffer, one memset, one copy: total, then the rows' error word and the capacities' (the layout of
+    // HW_CU_TOTAL, HW_MAX_LEN); a row's error is reported first
+    CollateFixedParams X{};
+    int64_t* meta;
+    if ((rc = ws_get(c, CW_SHARED_META, 2, &meta))) return rc;
+    P.err = (uint32_t*)(meta + 1);
+    X.R = P;
+    X.cu_seqlens = U.cu_seqlens;
+    X.position_ids = d_position_ids;
+    X.tok_cap = F->tok_cap;
+    X.seq_cap = F->seq_cap;
+    X.status = F->d_status;
+    X.total_out = meta;
+    HIP_TRY(hipMemsetAsync(meta, 0, 16, st));
+    HIP_TRY(launch_collate_fixed(X, code != 0, mode, c->n_cu, st));
+    HIP_TRY(fetch_word(c, HW_CU_TOTAL, meta, 16, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t batch = c->h_tot[HW_CU_TOTAL];
+    e = (uint32_t)(c->h_tot[HW_MAX_LEN] & 0xFFFFFFFF);
+    if (!e) e = (uint32_t)((uint64_t)c->h_tot[HW_MAX_LEN] >> 32);
+    *F->out_total = batch;
+    *F->out_n_rows = n_rows;
+    *F->out_n_seqs = n_rows + fixed_pad_seqs(batch, *F);
+    return e ? collate_fixed_error(e, batch, n_rows, *F) : 0;
+  }
   if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
   HIP_TRY(hipMemsetAsync(P.err, 0, 4, st));
   HIP_TRY(unpadded ? launch_collate_unpadded(U, code != 0, mode, c->n_cu, st)
@@ -381,6 +444,24 @@ extern "C" int lddl_collate_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, co
                              d_labels, d_next_sentence_labels, stream);
 }
 
+// ------------------------------- fixed-shape padding-free collate from a pack result --
+extern "C" int lddl_collate_rows_fixed(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                       const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                       const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                       const int64_t* d_mlm_off, const uint16_t* d_mlm_pos, const uint16_t* d_mlm_label,
+                                       const uint16_t* d_mlm_token, int32_t* d_cu_seqlens, int64_t tok_cap,
+                                       int64_t seq_cap, int64_t max_seqlen, int32_t mode, int64_t ignore_index,
+                                       double mlm_probability, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                       int64_t* d_token_type_ids, int64_t* d_position_ids, int64_t* d_labels,
+                                       int64_t* d_next_sentence_labels, int32_t* d_status, int64_t* out_total,
+                                       int64_t* out_n_rows, int64_t* out_n_seqs, void* stream) {
+  const CollateFixedArgs F{tok_cap, seq_cap, max_seqlen, d_status, out_total, out_n_rows, out_n_seqs};
+  return collate_rows_common(c, 1, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, d_mlm_off,
+                             d_mlm_pos, d_mlm_label, d_mlm_token, max_seqlen, d_cu_seqlens, tok_cap, mode, ignore_index,
+                             mlm_probability, seed, counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids,
+                             d_labels, d_next_sentence_labels, stream, &F);
+}
+
 // ------------------------------------------------- the same for CodeBERT rows --
 extern "C" int lddl_collate_code_rows_seq_len(lddl_ctx* c, const uint16_t* d_len0, const uint16_t* d_len1,
                                               const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
@@ -419,6 +500,21 @@ extern "C" int lddl_collate_code_rows_unpadded(lddl_ctx* c, const uint16_t* d_id
   return collate_rows_common(c, 1, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, nullptr,
                              nullptr, nullptr, nullptr, 0, d_cu_seqlens, total, mode, ignore_index, mlm_probability, seed,
                              counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids, d_labels, nullptr, stream);
+}
+
+extern "C" int lddl_collate_code_rows_fixed(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                            const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                            const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                            int64_t n_total, int32_t* d_cu_seqlens, int64_t tok_cap, int64_t seq_cap,
+                                            int64_t max_seqlen, int32_t mode, int64_t ignore_index, double mlm_probability,
+                                            uint64_t seed, uint64_t counter, int64_t* d_input_ids, int64_t* d_token_type_ids,
+                                            int64_t* d_position_ids, int64_t* d_labels, int32_t* d_status, int64_t* out_total,
+                                            int64_t* out_n_rows, int64_t* out_n_seqs, void* stream) {
+  const CollateFixedArgs F{tok_cap, seq_cap, max_seqlen, d_status, out_total, out_n_rows, out_n_seqs};
+  return collate_rows_common(c, 1, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, nullptr,
+                             nullptr, nullptr, nullptr, max_seqlen, d_cu_seqlens, tok_cap, mode, ignore_index, mlm_probability,
+                             seed, counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids, d_labels, nullptr, stream,
+                             &F);
 }
 
 // ------------------------------------------------------ compact MLM targets --

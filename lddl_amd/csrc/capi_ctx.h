@@ -95,7 +95,8 @@ enum CtxWs {
                    // lddl_collate_rows_cu_seqlens / lddl_rows_from_strings_len: chunk sums of their scans;
                    // lddl_mlm_targets: M, its error word, then the chunk sums of its scan (one memset)
   CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len;
-                   // lddl_collate_rows_cu_seqlens: total, max_len; lddl_rows_from_strings_len: its three totals
+                   // lddl_collate_rows_cu_seqlens: total, max_len; lddl_rows_from_strings_len: its three totals;
+                   // lddl_collate_rows_fixed: total, its error word (one memset)
                    // the lddl_bart_* calls use the three too: ROWS = chunks per document (plan_len) / bytes per chunk
                    // (plan), BSUM = block sums of their scans, META = {bytes total, refused chunk, error word}
   CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded] / lddl_rows_from_strings[_len]:
@@ -135,7 +136,8 @@ enum HostWord {
   HW_MARENA_USED,   // lddl_pack_bert (masking): the arena entries the bump allocator handed out
   HW_NDENSE,        // lddl_pack_bert / _codebert: the tokenizer's dense ids
   HW_CU_TOTAL = HW_NDENSE,  // the same word; lddl_collate_rows_cu_seqlens: the batch's tokens (one 16-byte copy with HW_MAX_LEN);
-                            // lddl_mlm_targets: M, with its error word in HW_MAX_LEN by the same copy
+                            // lddl_mlm_targets: M, with its error word in HW_MAX_LEN by the same copy;
+                            // lddl_collate_rows_fixed: the batch's tokens, with its error word in HW_MAX_LEN likewise
   HW_MAX_LEN,       // lddl_collate_seq_len / lddl_collate_rows_seq_len / lddl_collate_rows_cu_seqlens: the longest row (int32)
   HW_RENDER_BYTES = HW_MAX_LEN,  // the same word; lddl_render_strings / _npy / _masked: the bytes of the rendered column
   HW_ERR,           // lddl_bin, lddl_render_npy, lddl_collate_bert, lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded],

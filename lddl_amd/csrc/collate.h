@@ -112,6 +112,21 @@ struct CollateUnpaddedParams {
   int64_t n_chunks;        // collate_chunks(n_rows)
 };
 
+// lddl_collate_rows_fixed / lddl_collate_code_rows_fixed (collate_fixed.hip): the
+// padding-free batch in outputs of fixed capacity, offsets and fill in one
+// launch.  R.seq_len is max_seqlen, the bound of a row and the length of a pad
+// sequence; R.attention_mask and R.max_len are unused.
+struct CollateFixedParams {
+  CollateRowsParams R;     // input_ids, token_type_ids, labels: [tok_cap]; next_sentence_labels: [seq_cap];
+                           // err: [2], the rows' error word, then CERR_TOK_CAP / CERR_SEQ_CAP
+  int32_t* cu_seqlens;     // [seq_cap + 1], written
+  int64_t* position_ids;   // [tok_cap]
+  int64_t tok_cap, seq_cap;
+  int64_t rows_per_block;  // the run of batch rows a block takes: a multiple of 4
+  int32_t* status;         // [4] total, n_rows, n_seqs, max_seqlen
+  int64_t* total_out;      // [1] tokens of the batch, 64-bit
+};
+
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
 // lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
@@ -175,7 +190,9 @@ enum : uint32_t {
   CERR_ROW_COUNTS = 8,  // rows_from_strings.hip: a row's len / src / mlm_off are not what its strings give
   CERR_TABLE_CAP = 9,   // rows_from_strings.hip: the table ends beyond ids_cap / mlm_cap
   CERR_NMASK = 10,      // rows_from_strings.hip: more masked positions than the longest row has tokens
-  CERR_CODE_ROW = 11    // a CodeBERT row whose s is not 0 or 1 (num_tokens - a - b - 2, rows_from_strings.hip), or is 0 with a > 0
+  CERR_CODE_ROW = 11,   // a CodeBERT row whose s is not 0 or 1 (num_tokens - a - b - 2, rows_from_strings.hip), or is 0 with a > 0
+  CERR_TOK_CAP = 12,    // collate_fixed.hip: the batch holds more tokens than tok_cap
+  CERR_SEQ_CAP = 13     // collate_fixed.hip: the rows and the pad sequences of the slack take more slots than seq_cap
 };
 
 constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
@@ -190,6 +207,7 @@ hipError_t launch_collate_rows_len(const CollateRowsParams& P, bool code, int n_
 hipError_t launch_collate_rows(const CollateRowsParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, hipStream_t s);
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
+hipError_t launch_collate_fixed(const CollateFixedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 // (a CodeBERT shard when P.num_tokens is set)

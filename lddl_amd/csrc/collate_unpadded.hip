@@ -26,12 +26,9 @@
 // blocks: launch-bound.
 //
 // Fill pass: one wave per batch row, four rows per block and the per-wave LDS
-// row of mode 1, as collate_rows_kernel.  A row starts at any 8-B aligned token
-// offset, so the wave works on the 16-B aligned token pairs that cover
-// [cu_seqlens[r], cu_seqlens[r] + n_r): a lane computes both tokens of a pair and
-// stores 16 B per output; the first pair of a row with an odd start and the
-// last pair of one with an odd end hold one token of this row and store 8 B.
-// Outputs whose base is not 16-B aligned take the lane = token path.
+// row of mode 1, as collate_rows_kernel.  The row's tokens are stream_row's
+// (collate_row.h): 16-B aligned token pairs over [cu_seqlens[r], cu_seqlens[r] +
+// n_r), or lane = token when an output base is not 16-B aligned.
 //
 // No input faults: cu_seqlens is not trusted.  A row whose offsets are not
 // [c, c + n_r) within [0, total) sets CERR_CU_SEQLENS; the row opener's checks
@@ -104,9 +101,7 @@ __global__ __launch_bounds__(256) void collate_cu_scan_kernel(CollateUnpaddedPar
 
 }  // namespace
 
-// WWM (mode 2 only): whole-word masking, as in collate_rows_kernel.  A step of
-// the wide path is the 128 tokens of 64 aligned pairs, the first of them -1
-// (not a token of the row) when the row starts at an odd offset.
+// WWM (mode 2 only): whole-word masking, as in collate_rows_kernel.  The row's tokens: stream_row (collate_row.h).
 template <int MODE, bool CODE, bool WWM = false>
 __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedParams P) {
   static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
@@ -138,89 +133,7 @@ __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedPa
       if (lane == 0) set_err(R.err, code, r);
       continue;
     }
-    int64_t* o_ids = R.input_ids + c0;
-    int64_t* o_tt = R.token_type_ids + c0;
-    int64_t* o_pos = P.position_ids + c0;
-    int64_t* o_lab = R.labels + c0;
-    if constexpr (WWM) {
-      int32_t carry = -1;
-      if (wide) {
-        const int32_t head = (int32_t)(c0 & 1);
-        const int32_t nq = (head + n + 1) >> 1;
-        for (int32_t qb = 0; qb < nq; qb += 64) {
-          const int32_t q = qb + lane;
-          const int32_t j0 = 2 * q - head, j1 = j0 + 1;
-          const bool v0 = q < nq && j0 >= 0, v1 = q < nq && j1 < n;
-          const WordColumn w0 = word_column(R, S, j0, v0, false);
-          const WordColumn w1 = word_column(R, S, j1, v1, false);
-          int32_t wh[2];
-          word_heads<2>(2 * qb - head, {w0.start, w1.start}, carry, wh);
-          const RowColumn t0 = row_column_word(R, S, r, j0, w0, wh[0]);
-          const RowColumn t1 = row_column_word(R, S, r, j1, w1, wh[1]);
-          if (v0 && v1) {
-            *reinterpret_cast<longlong2*>(o_ids + j0) = make_longlong2(t0.id, t1.id);
-            *reinterpret_cast<longlong2*>(o_tt + j0) = make_longlong2(t0.tt, t1.tt);
-            *reinterpret_cast<longlong2*>(o_pos + j0) = make_longlong2(j0, j1);
-            *reinterpret_cast<longlong2*>(o_lab + j0) = make_longlong2(t0.lab, t1.lab);
-          } else if (v0 || v1) {
-            const RowColumn t = v0 ? t0 : t1;
-            const int32_t k = v0 ? j0 : j1;
-            o_ids[k] = t.id;
-            o_tt[k] = t.tt;
-            o_pos[k] = k;
-            o_lab[k] = t.lab;
-          }
-        }
-      } else {
-        for (int32_t base = 0; base < n; base += 64) {
-          const int32_t j = base + lane;
-          const WordColumn w0 = word_column(R, S, j, j < n, false);
-          int32_t wh[1];
-          word_heads<1>(base, {w0.start}, carry, wh);
-          if (j < n) {
-            const RowColumn t = row_column_word(R, S, r, j, w0, wh[0]);
-            o_ids[j] = t.id;
-            o_tt[j] = t.tt;
-            o_pos[j] = j;
-            o_lab[j] = t.lab;
-          }
-        }
-      }
-    } else if (wide) {
-      // pair q holds tokens 2q - head and 2q - head + 1: 16-B aligned in the
-      // stream.  The first pair of an odd start and the last of an odd end have
-      // one token of this row (n >= 2: never the same pair, never neither).
-      const int32_t head = (int32_t)(c0 & 1);
-      const int32_t nq = (head + n + 1) >> 1;
-      for (int32_t q = lane; q < nq; q += 64) {
-        const int32_t j0 = 2 * q - head, j1 = j0 + 1;
-        const bool v0 = j0 >= 0, v1 = j1 < n;
-        const int32_t k0 = v0 ? j0 : 0, k1 = v1 ? j1 : n - 1;
-        const RowColumn t0 = row_column<MODE>(R, S, mlm, r, k0, false);
-        const RowColumn t1 = row_column<MODE>(R, S, mlm, r, k1, false);
-        if (v0 && v1) {
-          *reinterpret_cast<longlong2*>(o_ids + j0) = make_longlong2(t0.id, t1.id);
-          *reinterpret_cast<longlong2*>(o_tt + j0) = make_longlong2(t0.tt, t1.tt);
-          *reinterpret_cast<longlong2*>(o_pos + j0) = make_longlong2(j0, j1);
-          *reinterpret_cast<longlong2*>(o_lab + j0) = make_longlong2(t0.lab, t1.lab);
-        } else {
-          const RowColumn t = v0 ? t0 : t1;
-          const int32_t k = v0 ? k0 : k1;
-          o_ids[k] = t.id;
-          o_tt[k] = t.tt;
-          o_pos[k] = k;
-          o_lab[k] = t.lab;
-        }
-      }
-    } else {
-      for (int32_t j = lane; j < n; j += 64) {
-        const RowColumn t = row_column<MODE>(R, S, mlm, r, j, false);
-        o_ids[j] = t.id;
-        o_tt[j] = t.tt;
-        o_pos[j] = j;
-        o_lab[j] = t.lab;
-      }
-    }
+    stream_row<MODE, WWM>(R, S, mlm, r, c0, wide, P.position_ids);
     if (!CODE && lane == 0) R.next_sentence_labels[r] = S.flags & 1u;
   }
 }

@@ -324,17 +324,30 @@ class _RowCollate:
       raise ValueError('empty batch')  # max() of an empty sequence in bert.py:94-95
     return mode, rows, row0, n
 
-  def _collate(self, unpadded, res, rows, row0, n_rows, mode):
-    """collate_rows (unpadded False) and collate_rows_unpadded of both classes:
-    the length call (lddl_collate[_code]_rows_seq_len / _cu_seqlens), the
-    outputs it sizes, the fill call, the batch counter and the dict."""
-    who = 'collate_rows_unpadded' if unpadded else 'collate_rows'
+  def _collate(self, unpadded, res, rows, row0, n_rows, mode, fixed=None):
+    """collate_rows (unpadded False), collate_rows_unpadded and
+    collate_rows_fixed (unpadded True with fixed = (max_tokens, max_seqs,
+    max_seqlen)) of both classes: the length call (lddl_collate[_code]_rows_seq_len
+    / _cu_seqlens) and the outputs it sizes, or the outputs of the given
+    capacities; the fill call, the batch counter and the dict."""
+    who = 'collate_rows_fixed' if fixed else 'collate_rows_unpadded' if unpadded else 'collate_rows'
     mode, rows, row0, n = self._row_batch(who, res, rows, row0, n_rows, mode)
     L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
     name = 'lddl_collate_code_rows' if self.CODE else 'lddl_collate_rows'
     lens = (p(res.len0), p(res.len1)) + ((p(res.flags),) if self.CODE else ())
     pick = (p(rows), row0, n, res.n_pairs)
-    if unpadded:
+    n_slots, end = n, ()
+    if fixed:
+      T, n_slots, S = (int(x) for x in fixed)
+      if T < 1 or n_slots < 1 or S < 1:
+        raise ValueError('%s: max_tokens %d, max_seqs %d, max_seqlen %d: each is 1 at least' % (who, T, n_slots, S))
+      cu = torch.empty(n_slots + 1, dtype=torch.int32, device=self.device)
+      status = torch.empty(4, dtype=torch.int32, device=self.device)
+      counts = [ctypes.c_int64() for _ in range(3)]  # tokens, rows, sequences
+      out = torch.empty((4, T), dtype=torch.int64, device=self.device)
+      shape = (p(cu), T, n_slots, S)
+      end = (p(status),) + tuple(ctypes.byref(x) for x in counts)
+    elif unpadded:
       cu = torch.empty(n + 1, dtype=torch.int32, device=self.device)
       total, longest = ctypes.c_int64(), ctypes.c_int64()
       _check(getattr(L, name + '_cu_seqlens')(h, *lens, *pick, p(cu), ctypes.byref(total), ctypes.byref(longest), st))
@@ -353,10 +366,11 @@ class _RowCollate:
     if self.CODE:
       nsl, mlm, tail = None, (), ()
     else:
-      nsl = torch.empty(n, dtype=torch.int64, device=self.device)
+      nsl = torch.empty(n_slots, dtype=torch.int64, device=self.device)
       mlm = (res.mlm_off, res.mlm_pos, res.mlm_label, res.mlm_token) if mode == MODE_STATIC else (None,) * 4
       mlm, tail = tuple(p(x) for x in mlm), (p(nsl),)
-    rc = getattr(L, name + ('_unpadded' if unpadded else ''))(h, *table, *pick, *mlm, *shape, *draw, *outs, *tail, st)
+    call = getattr(L, name + ('_fixed' if fixed else '_unpadded' if unpadded else ''))
+    rc = call(h, *table, *pick, *mlm, *shape, *draw, *outs, *tail, *end, st)
     if mode != MODE_SPECIAL_MASK:
       self.counter += 1
     _check(rc)
@@ -364,7 +378,10 @@ class _RowCollate:
              'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]}
     if nsl is not None:
       batch['next_sentence_labels'] = nsl
-    if unpadded:
+    if fixed:
+      batch['cu_seqlens'], batch['max_seqlen'], batch['status'] = cu, S, status
+      batch['num_tokens'], batch['num_rows'], batch['num_seqs'] = (int(x.value) for x in counts)
+    elif unpadded:
       batch['cu_seqlens'], batch['max_seqlen'] = cu, int(longest.value)
     return self._with_targets(batch, cu if unpadded else None)
 
@@ -581,6 +598,33 @@ class BertCollate(_RowCollate):
     nothing is padded."""
     return self._collate(True, res, rows, row0, n_rows, mode)
 
+  def collate_rows_fixed(self, res, rows=None, row0=0, n_rows=None, mode=None, *, max_tokens, max_seqs, max_seqlen):
+    """The batch of ``collate_rows_unpadded`` in tensors whose shapes do not
+    depend on the batch (lddl_collate_rows_fixed: offsets and fill in one call,
+    one launch, one synchronise), for a step that is captured or compiled
+    once: input_ids, token_type_ids, position_ids and labels (mode 0:
+    special_tokens_mask) as int64 [max_tokens], cu_seqlens as int32
+    [max_seqs + 1], next_sentence_labels as int64 [max_seqs], and max_seqlen,
+    the argument.  With n rows of ``total`` tokens, [0, total),
+    cu_seqlens[0..n] and next_sentence_labels[0..n) are
+    ``collate_rows_unpadded`` at the same seed and counter, bit for bit.  The
+    slack [total, max_tokens) is cut into p = ceil(slack / max_seqlen) pad
+    sequences in slots n .. n + p - 1, so that every token lies in a sequence:
+    input_ids 0, token_type_ids 0, position_ids restarting at 0 in each,
+    labels ignore_index (special_tokens_mask 1).  The remaining slots are
+    empty, cu_seqlens = max_tokens; next_sentence_labels is ignore_index from
+    slot n on.  Also returned: num_tokens (total), num_rows (n) and num_seqs
+    (n + p) as Python ints, and ``status``, an int32 [4] device tensor
+    {total, n, n + p, max_seqlen} for a trainer that reads them without the
+    host.  More than max_tokens tokens, a row longer than max_seqlen, or
+    n + p > max_seqs raise; ``fixed_seq_cap`` gives a max_seqs that the
+    batches of ``RowBatches(res, max_tokens=, max_rows=)`` never exceed.  The
+    batch counter advances as in ``collate_rows_unpadded``; with
+    ``compact_mlm`` the targets are those of the real rows (pad sequences
+    have none) and masked_lm_offsets is [max_seqs + 1]: ``compact_mlm=K``
+    makes every tensor of the step fixed-shape."""
+    return self._collate(True, res, rows, row0, n_rows, mode, (max_tokens, max_seqs, max_seqlen))
+
   def load_rows(self, table, bins=None, part=None, nbins=None):
     """The rows of a shard as a GPU row table, once (lddl_rows_from_strings_len
     + lddl_rows_from_strings): the decode-and-lookup half of the reference's
@@ -643,6 +687,14 @@ class CodeCollate(_RowCollate):
     [n + 1] and max_seqlen as a Python int."""
     return self._collate(True, res, rows, row0, n_rows, mode)
 
+  def collate_rows_fixed(self, res, rows=None, row0=0, n_rows=None, mode=None, *, max_tokens, max_seqs, max_seqlen):
+    """``collate_rows_unpadded`` in tensors of fixed shape
+    (lddl_collate_code_rows_fixed), as ``BertCollate.collate_rows_fixed``
+    without next_sentence_labels: the real rows first, bit for bit, then the
+    slack as pad sequences of at most max_seqlen tokens, cu_seqlens as int32
+    [max_seqs + 1], num_tokens / num_rows / num_seqs and ``status``."""
+    return self._collate(True, res, rows, row0, n_rows, mode, (max_tokens, max_seqs, max_seqlen))
+
   def load_rows(self, table, bins=None, part=None, nbins=None):
     """The rows of a CodeBERT shard as a GPU row table, once
     (lddl_code_rows_from_strings_len + lddl_code_rows_from_strings): a
@@ -661,7 +713,8 @@ class MlmCollate(CodeCollate):
   ``preprocess --no-nsp``): consecutive sentences of one document as
   ``[CLS] tokens [SEP]``, for recipes that train without NSP.  CodeCollate's
   surface over the BERT vocabulary: ``collate_rows`` /
-  ``collate_rows_unpadded`` over an MLM-only pack result, ``load_rows`` /
+  ``collate_rows_unpadded`` / ``collate_rows_fixed`` over an MLM-only pack
+  result, ``load_rows`` /
   ``load_shards`` over MLM-only shards (A, num_tokens), ``whole_word_mask``
   and ``compact_mlm`` as on the other classes.  Batches hold input_ids,
   token_type_ids (all 0), attention_mask (unpadded: position_ids, cu_seqlens,
@@ -750,6 +803,20 @@ def plan_token_batches(lengths, max_tokens, max_rows=None, seed=12345, epoch=0):
   return batches
 
 
+def fixed_seq_cap(max_tokens, max_rows, max_seqlen):
+  """The ``max_seqs`` of ``collate_rows_fixed`` that no batch of
+  ``RowBatches(res, max_tokens=max_tokens, max_rows=max_rows)`` can exceed:
+  max_rows + ceil(max_tokens / max_seqlen).  A fixed batch takes n slots for
+  its rows and p = ceil((max_tokens - total) / max_seqlen) for the pad
+  sequences of its slack; the plan gives n <= max_rows, and total >= 0 gives
+  p <= ceil(max_tokens / max_seqlen), whatever the batch holds: the short last
+  batch of an epoch, which is mostly slack, is covered as well."""
+  max_tokens, max_rows, max_seqlen = int(max_tokens), int(max_rows), int(max_seqlen)
+  if max_tokens < 1 or max_rows < 1 or max_seqlen < 1:
+    raise ValueError('max_tokens %d, max_rows %d, max_seqlen %d: each is 1 at least' % (max_tokens, max_rows, max_seqlen))
+  return max_rows + -(-max_tokens // max_seqlen)
+
+
 class RowBatches:
   """Iterable of int64 row-index tensors (on the result's device), one per
   batch, over a PackResult: ``for idx in RowBatches(res, 256): batch =
@@ -759,7 +826,8 @@ class RowBatches:
   With ``max_tokens`` in place of ``batch_size`` (exactly one of the two) the
   batches are for ``collate_rows_unpadded``: plan_token_batches over a host
   copy of len0 + len1 + 2 + ((flags >> 1) & 1), at most max_tokens tokens (and max_rows rows) each;
-  bins are ignored and drop_last has no meaning."""
+  bins are ignored and drop_last has no meaning.  For ``collate_rows_fixed``
+  give max_rows too: ``fixed_seq_cap(max_tokens, max_rows, max_seqlen)`` is then its max_seqs."""
 
   def __init__(self, res, batch_size=None, seed=12345, epoch=0, drop_last=False, max_tokens=None, max_rows=None):
     if (batch_size is None) == (max_tokens is None):

@@ -193,7 +193,43 @@ def shard_files(names):
   return sorted((tuple(f) for f in out), key=lambda f: (f[1], -1 if f[2] is None else f[2], f[0]))
 
 
-def load_shards(collate, path_or_paths):
+def _check_rank(rank, world_size):
+  rank, world_size = int(rank), int(world_size)
+  if world_size < 1 or not 0 <= rank < world_size:
+    raise ValueError('rank %d outside a world of %d' % (rank, world_size))
+  return rank, world_size
+
+
+def rank_shard_files(files, rank, world_size):
+  """The entries of ``files`` (shard_files' output) that rank ``rank`` of
+  ``world_size`` reads, in the same order: whole partitions dealt round-robin,
+  the partition at position i of the sorted distinct partitions to rank
+  i % world_size with all its bin files, as the reference's
+  ``files[rank::world_size]`` (lddl/torch/datasets.py:167) deals balanced
+  shards.  The partition count must be a multiple of world_size
+  (datasets.py:143), so that every rank holds as many shards as any other."""
+  rank, world_size = _check_rank(rank, world_size)
+  parts = sorted({f[1] for f in files})
+  if len(parts) % world_size:
+    raise ValueError('%d partitions are not a multiple of world_size %d: balance to a multiple of it (--num-shards)'
+                     % (len(parts), world_size))
+  mine = set(parts[rank::world_size])
+  return [f for f in files if f[1] in mine]
+
+
+def rank_seed(base_seed, rank):
+  """A ``base_seed`` for rank ``rank``'s collate: the dynamic draw is keyed by
+  (seed, batch counter, batch row, column), so ranks that share a seed would
+  mask the same positions of their batches.  The splitmix64 output function
+  over base_seed + (rank + 1) * 0x9E3779B97F4A7C15, a 64-bit int."""
+  m = (1 << 64) - 1
+  z = (int(base_seed) + (int(rank) + 1) * 0x9E3779B97F4A7C15) & m
+  z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+  z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+  return z ^ (z >> 31)
+
+
+def load_shards(collate, path_or_paths, rank=None, world_size=None):
   """Every ``*.parquet`` / ``*.parquet_<b>`` file under a directory (or the
   files of a list) as one GPU row table: read with pyarrow in (partition, bin)
   order (shard_files), each row's bin from its file's suffix and its partition
@@ -201,8 +237,15 @@ def load_shards(collate, path_or_paths):
   balancer's output), then one ``collate.load_rows``.  The collate decides
   what is read: a BertCollate takes BERT shards (A / B / is_random_next and the
   static columns), a CodeCollate CodeBERT shards (doc / code / num_tokens; the
-  id column is not loaded).  Shards of the other kind raise ValueError."""
+  id column is not loaded).  Shards of the other kind raise ValueError.
+
+  rank / world_size (both or neither): only the files of rank_shard_files are
+  read, so a rank of a data-parallel job holds its own partitions and no
+  others.  The table keeps each row's original partition number in ``part``
+  and the bin count of the whole directory."""
   import pyarrow.parquet as pq
+  if (rank is None) != (world_size is None):
+    raise ValueError('give rank and world_size together')
   if isinstance(path_or_paths, (str, bytes, os.PathLike)):
     path = os.fspath(path_or_paths)
     if os.path.isdir(path):
@@ -214,6 +257,10 @@ def load_shards(collate, path_or_paths):
   files = shard_files(names)
   if not files:
     raise ValueError('no parquet files in %r' % (path_or_paths,))
+  binned = files[0][2] is not None
+  nbins = max(b for _, _, b in files) + 1 if binned else None
+  if rank is not None:
+    files = rank_shard_files(files, rank, world_size)
   tables, bins, part = [], [], []
   for name, pt, b in files:
     t = pq.read_table(name)
@@ -226,9 +273,8 @@ def load_shards(collate, path_or_paths):
     bins.append(np.full(t.num_rows, b or 0, np.uint8))
     part.append(np.full(t.num_rows, pt, np.int64))
   if not tables:
-    raise ValueError('no rows in %r' % (path_or_paths,))
-  binned = files[0][2] is not None
-  nbins = max(b for _, _, b in files) + 1 if binned else None
+    whose = '' if rank is None else ' for rank %d of %d' % (rank, world_size)
+    raise ValueError('no rows in %r%s' % (path_or_paths, whose))
   return collate.load_rows(tables, np.concatenate(bins) if binned else None, np.concatenate(part), nbins)
 
 
@@ -803,6 +849,92 @@ def plan_token_batches(lengths, max_tokens, max_rows=None, seed=12345, epoch=0):
   return batches
 
 
+def _dp_generators(seed, epoch, rank):
+  """(world generator, rank generator) of the data-parallel planners: the
+  first is seeded by (seed, epoch) as in plan_row_batches and is the same on
+  every rank, the second is its SeedSequence child with spawn key (rank,)."""
+  entropy = [int(seed) & ((1 << 64) - 1), int(epoch)]
+  seqs = (np.random.SeedSequence(entropy), np.random.SeedSequence(entropy, spawn_key=(int(rank),)))
+  return tuple(np.random.Generator(np.random.PCG64(s)) for s in seqs)
+
+
+def plan_row_batches_dp(bins, counts, rank, batch_size, seed=12345, epoch=0, drop_last=False, n_rows=None):
+  """plan_row_batches for rank ``rank`` of a data-parallel job: every rank
+  gets the same number of batches, and at every step all ranks' batches come
+  from the same bin and have the same length, so padded lengths agree and no
+  rank runs out first (what the reference gets from one world generator,
+  lddl/torch/dataloader.py:32-91, and from equal shards, datasets.py:143-152).
+  Returns this rank's batches, int64 index arrays into its own rows.
+
+  bins: the bin id of each of this rank's rows (None: n_rows rows of bin 0).
+  counts: int64 [world_size, nbins], the rows every rank holds per bin; row
+  ``rank`` must be the counts of ``bins``.  Bin b serves n_b = min over ranks
+  of counts[:, b] rows on every rank, in n_b // batch_size batches with
+  drop_last, else ceil(n_b / batch_size), the short one last.  The list of
+  steps (bin ids) is permuted by a generator seeded by (seed, epoch) alone;
+  this rank's rows inside each bin are permuted by one seeded by (seed, epoch,
+  rank), and a rank that holds more than n_b rows leaves the tail of that
+  permutation out for this epoch: the reference loses the surplus of its
+  larger files the same way (datasets.py:147-152), here it is drawn afresh
+  every epoch.  The k-th step of a bin takes that bin's k-th batch."""
+  batch_size = int(batch_size)
+  if batch_size < 1:
+    raise ValueError('batch_size %d < 1' % batch_size)
+  counts = np.asarray(counts, dtype=np.int64)
+  if counts.ndim != 2:
+    raise ValueError('counts: [world_size, nbins]')
+  rank, _ = _check_rank(rank, counts.shape[0])
+  nbins = counts.shape[1]
+  if bins is None:
+    bins = np.zeros(int(n_rows), dtype=np.int64)
+  bins = np.asarray(bins).reshape(-1).astype(np.int64)
+  if bins.size and int(bins.max()) >= nbins:
+    raise ValueError('a bin id >= the %d bins of counts' % nbins)
+  if not np.array_equal(np.bincount(bins, minlength=nbins), counts[rank]):
+    raise ValueError('counts[%d] is not the bin count of this rank\'s rows' % rank)
+  world_rng, rank_rng = _dp_generators(seed, epoch, rank)
+  used = counts.min(axis=0)
+  order = np.argsort(bins, kind='stable')
+  lo = np.concatenate([np.zeros(1, np.int64), np.cumsum(counts[rank])])
+  per_bin, steps = [], []
+  for b in range(nbins):  # ascending bin id: every rank draws in the same order
+    c, n = int(counts[rank, b]), int(used[b])
+    rows = order[lo[b]:lo[b] + c][rank_rng.permutation(c)][:n]
+    full = (n // batch_size) * batch_size
+    cut = [rows[i:i + batch_size] for i in range(0, full, batch_size)]
+    if full < n and not drop_last:
+      cut.append(rows[full:])
+    per_bin.append(cut)
+    steps += [b] * len(cut)
+  step_bins = np.asarray(steps, dtype=np.int64)[world_rng.permutation(len(steps))]
+  taken = [0] * nbins
+  batches = []
+  for b in step_bins.tolist():
+    batches.append(per_bin[b][taken[b]])
+    taken[b] += 1
+  return batches
+
+
+def plan_token_batches_dp(lengths, rank, max_tokens, max_rows=None, seed=12345, epoch=0, steps=None):
+  """plan_token_batches for rank ``rank`` of a data-parallel job: this rank's
+  rows are permuted by a generator seeded by (seed, epoch, rank), built as in
+  plan_row_batches_dp, and plan_token_batches cuts that order.  steps: the
+  batches of this epoch, the minimum over ranks of their own plans' lengths
+  (RowBatches agrees on it); the plan is cut to its first ``steps`` batches
+  and the rows behind them sit this epoch out.  None keeps the whole plan;
+  more steps than the plan has raise ValueError."""
+  lengths = np.asarray(lengths).reshape(-1).astype(np.int64)
+  _, rank_rng = _dp_generators(seed, epoch, rank)
+  perm = rank_rng.permutation(lengths.size).astype(np.int64)
+  plan = [perm[b] for b in plan_token_batches(lengths[perm], max_tokens, max_rows, seed, epoch)]
+  if steps is not None:
+    steps = int(steps)
+    if not 0 <= steps <= len(plan):
+      raise ValueError('steps %d, but rank %d has %d batches' % (steps, int(rank), len(plan)))
+    plan = plan[:steps]
+  return plan
+
+
 def fixed_seq_cap(max_tokens, max_rows, max_seqlen):
   """The ``max_seqs`` of ``collate_rows_fixed`` that no batch of
   ``RowBatches(res, max_tokens=max_tokens, max_rows=max_rows)`` can exceed:
@@ -827,13 +959,42 @@ class RowBatches:
   batches are for ``collate_rows_unpadded``: plan_token_batches over a host
   copy of len0 + len1 + 2 + ((flags >> 1) & 1), at most max_tokens tokens (and max_rows rows) each;
   bins are ignored and drop_last has no meaning.  For ``collate_rows_fixed``
-  give max_rows too: ``fixed_seq_cap(max_tokens, max_rows, max_seqlen)`` is then its max_seqs."""
+  give max_rows too: ``fixed_seq_cap(max_tokens, max_rows, max_seqlen)`` is then its max_seqs.
 
-  def __init__(self, res, batch_size=None, seed=12345, epoch=0, drop_last=False, max_tokens=None, max_rows=None):
+  ``start_step=k`` (here or in ``set_epoch``) resumes in the middle of an
+  epoch: iteration skips the first k batches of the plan and ``len()`` still
+  reports the whole epoch.  With ``collate.counter = k`` beside it the dynamic
+  masks are those of the uninterrupted job.
+
+  With ``rank`` / ``world_size`` (``res`` being that rank's table,
+  ``load_shards(..., rank=, world_size=)``) the plans are plan_row_batches_dp
+  and plan_token_batches_dp: every rank iterates the same number of batches,
+  and the binned ones share their bin and length at every step.  What the
+  ranks must agree on comes from ``group`` (None: the default process group):
+  the per-bin row counts of every rank, one all_gather_into_tensor of [nbins]
+  int64 in the constructor, or the number of token batches, one
+  all_reduce(MIN) of one int per epoch's plan.  ``counts`` ([world_size,
+  nbins]) or ``steps`` given explicitly take their place, so that one process
+  can stand in for every rank; a world of more than one rank with neither and
+  no process group raises.  world_size defaults to the group's size.  A
+  rank's plan of an epoch is kept until seed or epoch change, so ``len()`` and
+  the loop cost one collective together."""
+
+  def __init__(self, res, batch_size=None, seed=12345, epoch=0, drop_last=False, max_tokens=None, max_rows=None,
+               rank=None, world_size=None, group=None, counts=None, steps=None, start_step=0):
     if (batch_size is None) == (max_tokens is None):
       raise ValueError('give exactly one of batch_size and max_tokens')
     if max_rows is not None and max_tokens is None:
       raise ValueError('max_rows goes with max_tokens')
+    if rank is None and any(x is not None for x in (world_size, group, counts, steps)):
+      raise ValueError('world_size, group, counts and steps go with rank')
+    if counts is not None and max_tokens is not None:
+      raise ValueError('counts goes with batch_size: a token plan agrees on steps')
+    if steps is not None and max_tokens is None:
+      raise ValueError('steps goes with max_tokens: a binned plan agrees on counts')
+    self.rank = self.world_size = self.group = self.counts = self.steps = None
+    self._planned = None
+    self.start_step = self._start(start_step)
     self.seed, self.epoch, self.drop_last = seed, epoch, drop_last
     self.batch_size = int(batch_size) if batch_size is not None else None
     self.max_tokens = int(max_tokens) if max_tokens is not None else None
@@ -849,11 +1010,83 @@ class RowBatches:
       self.lengths = l0 + l1 + 2 + ((fl >> 1) & 1)  # bit 1: the [SEP] after segment 0 (every BERT row has it)
     elif res.nbins > 1:
       self.bins = res.bins[:res.n_pairs].cpu().numpy()
+    if rank is not None:
+      self._join(res, rank, world_size, group, counts, steps)
 
-  def set_epoch(self, epoch):
+  @staticmethod
+  def _start(start_step):
+    start_step = int(start_step)
+    if start_step < 0:
+      raise ValueError('start_step %d < 0' % start_step)
+    return start_step
+
+  def _collective(self, what):
+    """torch.distributed and the device its collectives over self.group take (the GPU under nccl = RCCL)"""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+      raise ValueError('rank %d of %d with no process group: init_process_group first, or give %s' %
+                       (self.rank, self.world_size, what))
+    return dist, self.device if dist.get_backend(self.group) == 'nccl' else torch.device('cpu')
+
+  def _join(self, res, rank, world_size, group, counts, steps):
+    """the constructor's data-parallel half: rank and world, and the per-bin counts of every rank for a binned plan"""
+    self.group = group
+    if world_size is None:
+      import torch.distributed as dist
+      if not (dist.is_available() and dist.is_initialized()):
+        raise ValueError('rank without world_size and no process group to take it from')
+      world_size = dist.get_world_size(group)
+    self.rank, self.world_size = _check_rank(rank, world_size)
+    if self.max_tokens is not None:
+      self.steps = None if steps is None else int(steps)
+      if self.steps is None and self.world_size > 1:
+        self._collective('steps')  # (refuse here, not in the first epoch)
+      return
+    nbins = int(res.nbins)
+    mine = np.bincount(self.bins, minlength=nbins) if self.bins is not None else np.array([self.n_rows])
+    mine = mine.astype(np.int64)
+    if counts is not None:
+      counts = np.array(counts, dtype=np.int64)
+      if counts.shape != (self.world_size, nbins):
+        raise ValueError('counts of shape %s, not [world_size %d, nbins %d]' % (counts.shape, self.world_size, nbins))
+      if not np.array_equal(counts[self.rank], mine):
+        raise ValueError('counts[%d] is not the bin count of this rank\'s rows' % self.rank)
+    elif self.world_size == 1:
+      counts = mine[None]
+    else:
+      dist, dev = self._collective('counts')
+      if dist.get_world_size(group) != self.world_size:
+        raise ValueError('world_size %d, but the group has %d ranks' % (self.world_size, dist.get_world_size(group)))
+      out = torch.empty(self.world_size * nbins, dtype=torch.int64, device=dev)
+      dist.all_gather_into_tensor(out, torch.from_numpy(mine).to(dev), group=group)
+      counts = out.cpu().numpy().reshape(self.world_size, nbins)
+    self.counts = counts
+
+  def set_epoch(self, epoch, start_step=0):
     self.epoch = epoch
+    self.start_step = self._start(start_step)
+
+  def _fewest(self, local):
+    """the token batches of this epoch: the fewest any rank has"""
+    dist, dev = self._collective('steps')
+    n = torch.tensor([local], dtype=torch.int64, device=dev)
+    dist.all_reduce(n, op=dist.ReduceOp.MIN, group=self.group)
+    return int(n.item())
 
   def plan(self):
+    if self.rank is not None:
+      key = (self.seed, self.epoch, self.drop_last, self.batch_size, self.max_tokens, self.max_rows, self.steps)
+      if self._planned is None or self._planned[0] != key:
+        if self.max_tokens is not None:
+          plan = plan_token_batches_dp(self.lengths, self.rank, self.max_tokens, self.max_rows, self.seed, self.epoch,
+                                       steps=self.steps)
+          if self.steps is None and self.world_size > 1:
+            plan = plan[:self._fewest(len(plan))]
+        else:
+          plan = plan_row_batches_dp(self.bins, self.counts, self.rank, self.batch_size, self.seed, self.epoch,
+                                     self.drop_last, n_rows=self.n_rows)
+        self._planned = (key, plan)
+      return list(self._planned[1])
     if self.max_tokens is not None:
       return plan_token_batches(self.lengths, self.max_tokens, self.max_rows, self.seed, self.epoch)
     return plan_row_batches(self.bins, self.batch_size, self.seed, self.epoch, self.drop_last, n_rows=self.n_rows)
@@ -862,7 +1095,7 @@ class RowBatches:
     return len(self.plan())
 
   def __iter__(self):
-    plan = self.plan()
+    plan = self.plan()[self.start_step:]
     if not plan:
       return
     flat = torch.from_numpy(np.concatenate(plan)).to(self.device)  # the indices only: one copy per epoch

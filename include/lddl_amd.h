@@ -387,6 +387,63 @@ int lddl_mask_tokens(lddl_ctx *ctx, int64_t *d_inputs, const int64_t *d_special_
  * tests/wwm_model.py is this in numpy. */
 int lddl_set_whole_word_mask(lddl_ctx *ctx, int on);
 
+/* Span dynamic masking (ALBERT's n-gram masking, SpanBERT's span masking, the
+ * n-gram option of Megatron-style BERT pipelines): contiguous runs of whole
+ * words are selected.  The reference has no counterpart.  Parameters:
+ * max_span L in [1, 16], geo_p g in (0, 1] and the call's mlm_probability p.
+ *
+ * Length law (SpanBERT's clipped geometric, renormalised):
+ *   P(len = l) = g (1 - g)^(l - 1) / (1 - (1 - g)^L)  for l = 1 .. L
+ *   cdf[t] = P(len <= t) for t = 1 .. L, cdf[L] = 1 exactly
+ *   S_0 = 1, S_t = 1 - cdf[t]
+ * Start probability q, chosen so that an interior word (one with L - 1 words
+ * of its segment in front of it) is covered with probability p:
+ *   L == 1: q = p exactly; otherwise q is the root in [0, p] of
+ *   1 - prod_{t = 0 .. L-1} (1 - q S_t) = p  (0 at q = 0, at least p at q = p,
+ *   monotone), by 64 bisection steps in double on the host: the upper end of
+ *   the last interval, which is 0 for p = 0 and 1 for p = 1.
+ *
+ * Per row, with special(j), cont(id), start(j), head(j), k, i(row, col), sm
+ * and unit as in the whole-word definition above:
+ *   a segment  is a maximal run of non-special columns; spans live inside one
+ *              segment, so a span never covers or crosses a [SEP], [CLS], pad
+ *              column or caller-marked special column
+ *   w(j)       the number of start columns of j's segment at or before j
+ *   ks         = sm(k ^ 0x5350414E4D41534B)
+ *   open(h)    for a start column h: iff unit(sm(k + i(row, h))) < q, the
+ *              select draw of lddl_mask_tokens taken at the head h
+ *   len(h)     = 1 + #{t in [1, L - 1] : unit(sm(ks + i(row, h))) >= cdf[t]}
+ *   selected   iff !special(j) and there is a start column h <= j in j's
+ *              segment with open(h) and w(j) - w(h) < len(h)
+ *   a selected j has label id_j and its own second and third draws
+ *   (i(row, j) + 1, + 2) decide [MASK] / random id / kept, exactly as without
+ *   the switch: replacement stays per token, as with whole words (SpanBERT
+ *   replaces per span: all of a span's tokens alike); an unselected j keeps
+ *   its id and has label ignore_index.
+ * Consequences: with L = 1 the result is bit for bit whole-word masking.
+ * Overlapping spans simply union.  The first L - 1 words of a segment are
+ * covered slightly less often than p, because fewer heads lie in front of
+ * them.  A span that would run past its segment's end is clipped there.
+ * tests/span_model.py is this in numpy.
+ *
+ * lddl_span_params: q and cdf for (max_span, geo_p, mlm_probability), on the
+ * host (no ctx, no GPU).  out_cdf[t - 1] = cdf[t] for t = 1 .. L, 1.0 behind
+ * them.  The one place they are computed: every collate call of a ctx with
+ * the switch on takes them from here at call time, from its own
+ * mlm_probability.  LDDL_EINVAL: max_span outside [1, 16], geo_p outside
+ * (0, 1], mlm_probability outside [0, 1], a NULL output. */
+int lddl_span_params(int32_t max_span, double geo_p, double mlm_probability, double *out_q, double out_cdf[16]);
+
+/* The switch: max_span == 0 turns span masking off (the default; geo_p is
+ * then ignored).  While it is on, lddl_mask_tokens and mode 2 of every collate
+ * call of the ctx (lddl_collate_bert, lddl_collate_rows[_unpadded | _fixed],
+ * lddl_collate_code_rows[_unpadded | _fixed]) select as defined above, and
+ * the whole-word switch is ignored; modes 0 and 1 ignore it; a vocabulary
+ * without "##" entries is accepted (every token is then a word).
+ * LDDL_EINVAL: max_span outside [0, 16] or geo_p outside (0, 1]; the switch
+ * then stays as it was. */
+int lddl_set_span_mask(lddl_ctx *ctx, int32_t max_span, double geo_p);
+
 /* ---- collate straight from a pack result ---------------------------------
  * The same lddl/torch/bert.py:69-153 `_to_encoded_inputs` (+ :156-196
  * `_mask_tokens`) for rows that never became parquet: batch row r is row

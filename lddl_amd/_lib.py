@@ -66,6 +66,8 @@ SIGNATURES = {
     'lddl_mask_tokens': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_double, c_int64,
                                  c_uint64, c_uint64, c_void_p]),
     'lddl_set_whole_word_mask': (c_int, [c_void_p, c_int]),
+    'lddl_span_params': (c_int, [c_int32, c_double, c_double, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
+    'lddl_set_span_mask': (c_int, [c_void_p, c_int32, c_double]),
     'lddl_collate_rows_seq_len': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
                                           ctypes.POINTER(c_int64), c_void_p]),
     'lddl_collate_rows': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 4 +

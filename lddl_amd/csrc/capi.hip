@@ -177,6 +177,21 @@ extern "C" int lddl_set_whole_word_mask(lddl_ctx* c, int on) {
   return 0;
 }
 
+extern "C" int lddl_set_span_mask(lddl_ctx* c, int32_t max_span, double geo_p) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (max_span == 0) {
+    c->span_max = 0;
+    return 0;
+  }
+  // the ranges are lddl_span_params': nothing is kept that a collate call would refuse later
+  double q, cdf[16];
+  const int rc = lddl_span_params(max_span, geo_p, 0.0, &q, cdf);
+  if (rc) return rc;
+  c->span_max = max_span;
+  c->span_geo = geo_p;
+  return 0;
+}
+
 extern "C" int lddl_set_tokenize_algo(lddl_ctx* c, int algo, int* out_algo) {
   if (!c) return set_err(LDDL_EINVAL, "null ctx");
   if (algo != 0 && algo != 5) return set_err(LDDL_EINVAL, "tokenize algo must be 0 or 5");

@@ -2,6 +2,8 @@
 // collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, rows_from_strings.hip, mlm_targets.hip).
 #include "capi_ctx.h"
 
+#include <math.h>
+
 static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
   if (!c->d_ctab) {
     const size_t n = c->vocab.size();
@@ -36,6 +38,48 @@ static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
   V->mask_id = (int32_t)c->special[4];
   V->n_random = c->vocab_size;
   return 0;
+}
+
+// ---------------------------------------------------------------- span masking --
+extern "C" int lddl_span_params(int32_t max_span, double geo_p, double mlm_probability, double* out_q,
+                                double out_cdf[16]) {
+  if (!out_q || !out_cdf) return set_err(LDDL_EINVAL, "null output pointer");
+  if (max_span < 1 || max_span > 16) return set_err(LDDL_EINVAL, "max_span %d not in [1, 16]", max_span);
+  if (!(geo_p > 0.0 && geo_p <= 1.0)) return set_err(LDDL_EINVAL, "geo_p not in (0, 1]");
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  const int L = max_span;
+  const double p = mlm_probability;
+  // 1 - (1 - g)^t = -expm1(t * log1p(-g)): no cancellation for a small g, and 1 for g = 1
+  const double lg = log1p(-geo_p), all = -expm1(L * lg);
+  for (int t = 1; t <= 16; ++t) out_cdf[t - 1] = t < L ? std::min(-expm1(t * lg) / all, 1.0) : 1.0;
+  if (L == 1) {
+    *out_q = p;
+    return 0;
+  }
+  // 1 - prod (1 - q * S_t), S_0 = 1, S_t = 1 - cdf[t], is 0 at 0, >= p at p and monotone.  Compared as the product
+  // against 1 - p, which stays exact near p = 1.  64 halvings of [0, p] keep missed(lo) > 1 - p >= missed(hi);
+  // q = hi, which is exactly 0 for p = 0 and exactly 1 for p = 1.
+  const auto missed = [&](double q) {
+    double keep = 1.0 - q;
+    for (int t = 1; t < L; ++t) keep *= 1.0 - q * (1.0 - out_cdf[t - 1]);
+    return keep;
+  };
+  double lo = 0.0, hi = p;
+  for (int it = 0; it < 64; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    if (missed(mid) > 1.0 - p) lo = mid;
+    else hi = mid;
+  }
+  *out_q = hi;
+  return 0;
+}
+
+// the span law of a dynamic call over c, from its own mlm_probability; L = 0 while the switch is off
+static int span_law(const lddl_ctx* c, double mlm_probability, SpanLaw* S) {
+  *S = SpanLaw{};
+  if (!c->span_max) return 0;
+  S->L = c->span_max;
+  return lddl_span_params(c->span_max, c->span_geo, mlm_probability, &S->q, S->cdf);
 }
 
 // the longest row m rounded up to a multiple of sequence_length_alignment (bert.py:94-97)
@@ -98,7 +142,8 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
   P.mlm_probability = mlm_probability;
   P.seed = seed;
   P.counter = counter;
-  P.cont = c->whole_word ? c->d_cont : nullptr;  // picks the whole-word instantiation of mode 2
+  P.cont = c->whole_word || c->span_max ? c->d_cont : nullptr;  // picks the whole-word or the span instantiation of mode 2
+  if (mode == COLLATE_DYNAMIC && (rc = span_law(c, mlm_probability, &P.span))) return rc;
   P.input_ids = d_input_ids;
   P.token_type_ids = d_token_type_ids;
   P.attention_mask = d_attention_mask;
@@ -145,7 +190,9 @@ extern "C" int lddl_mask_tokens(lddl_ctx* c, int64_t* d_inputs, const int64_t* d
   M.mlm_probability = mlm_probability;
   M.seed = seed;
   M.counter = counter;
-  M.cont = c->whole_word ? c->d_cont : nullptr;  // picks the wave-per-row kernel
+  M.cont = c->whole_word || c->span_max ? c->d_cont : nullptr;  // picks the wave-per-row kernel
+  int rc;
+  if ((rc = span_law(c, mlm_probability, &M.span))) return rc;
   HIP_TRY(launch_mask_tokens(M, c->n_cu, (hipStream_t)stream));
   return 0;
 }
@@ -302,6 +349,7 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
   hipStream_t st = (hipStream_t)stream;
   CollateUnpaddedParams U{};
   CollateRowsParams& P = U.R;
+  int rc;
   collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   P.ids = d_ids;
   P.src0 = d_src0;
@@ -319,7 +367,8 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
   P.mlm_probability = mlm_probability;
   P.seed = seed;
   P.counter = counter;
-  P.cont = c->whole_word ? c->d_cont : nullptr;  // picks the whole-word instantiation of mode 2
+  P.cont = c->whole_word || c->span_max ? c->d_cont : nullptr;  // picks the whole-word or the span instantiation of mode 2
+  if (mode == COLLATE_DYNAMIC && (rc = span_law(c, mlm_probability, &P.span))) return rc;
   P.input_ids = d_input_ids;
   P.token_type_ids = d_token_type_ids;
   P.attention_mask = d_attention_mask;
@@ -328,7 +377,6 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
   U.cu_seqlens = const_cast<int32_t*>(d_cu_seqlens);  // read only by the fill pass
   U.position_ids = d_position_ids;
   U.total = total;
-  int rc;
   uint32_t e;
   if (F) {
     // one buffer, one memset, one copy: total, then the rows' error word and the capacities' (the layout of

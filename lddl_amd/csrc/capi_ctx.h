@@ -185,6 +185,8 @@ struct lddl_ctx {
   uint32_t* d_rinfo = nullptr;   // [V] offset << 8 | length into d_rpool
   uint32_t* d_cont = nullptr;    // [(V + 31) / 32] bit id: entry id begins with "##" (whole-word masking)
   bool whole_word = false;       // lddl_set_whole_word_mask
+  int32_t span_max = 0;          // lddl_set_span_mask: max_span (0: off) and geo_p
+  double span_geo = 0.0;
   uint32_t maxb[2] = {0, 0};
   uint4* d_vt = nullptr;         // v4 bucketed vocab table
   uint32_t vt_mask = 0;

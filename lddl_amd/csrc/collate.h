@@ -8,6 +8,17 @@ namespace lddl {
 
 enum : int32_t { COLLATE_SPECIAL_MASK = 0, COLLATE_STATIC = 1, COLLATE_DYNAMIC = 2 };
 
+// What mode 2 selects, a template constant of its kernels: tokens (`_mask_tokens`), whole words
+// (lddl_set_whole_word_mask) or geometric spans of whole words (lddl_set_span_mask).
+enum : int { SEL_TOKEN = 0, SEL_WORD = 1, SEL_SPAN = 2 };
+
+// Span masking: lddl_span_params' outputs for the call's mlm_probability.  L = 0: off.
+struct SpanLaw {
+  double q;        // a word start opens a span iff its select draw is below q
+  double cdf[16];  // P(len <= t + 1) in [t], 1.0 from t = L - 1 on
+  int32_t L;       // max_span
+};
+
 // Whole-token vocab table for convert_tokens_to_ids: open addressing over
 // slots {hash, id}; the key bytes are verified against the render pool
 // (vinfo[id] = offset << 8 | length, the full entry text incl. "##").
@@ -44,6 +55,7 @@ struct CollateParams {
   double mlm_probability;
   uint64_t seed, counter;
   const uint32_t* cont;      // whole-word masking (mode 2 with lddl_set_whole_word_mask on): bit id = entry id begins with "##"; else NULL
+  SpanLaw span;              // span masking (mode 2 with lddl_set_span_mask on; cont is then set as well)
   int64_t* input_ids;        // [n_rows, seq_len]
   int64_t* token_type_ids;
   int64_t* attention_mask;
@@ -63,6 +75,7 @@ struct MaskParams {
   double mlm_probability;
   uint64_t seed, counter;
   const uint32_t* cont;       // whole-word masking: as CollateParams::cont, over n_random entries; else NULL
+  SpanLaw span;               // span masking: as CollateParams::span
 };
 
 // lddl_collate_rows_seq_len / lddl_collate_rows: batch row r is row
@@ -89,6 +102,7 @@ struct CollateRowsParams {
   double mlm_probability;
   uint64_t seed, counter;
   const uint32_t* cont;      // whole-word masking: as CollateParams::cont, over n_random entries; else NULL
+  SpanLaw span;              // span masking: as CollateParams::span
   int64_t* input_ids;        // [n_rows, seq_len]
   int64_t* token_type_ids;
   int64_t* attention_mask;
@@ -200,6 +214,9 @@ constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
 // rows per block of the offsets scans (collate_row.h), 8 per thread, and the blocks that n_rows take
 constexpr int kChunk = 2048;
 inline int64_t collate_chunks(int64_t n_rows) { return (n_rows + kChunk - 1) / kChunk; }
+
+// what a dynamic launch selects, from its params' cont and span
+inline int collate_sel(const uint32_t* cont, const SpanLaw& span) { return span.L > 0 ? SEL_SPAN : cont ? SEL_WORD : SEL_TOKEN; }
 
 uint32_t collate_hash_host(const uint8_t* p, int n);
 // code: the rows are CodeBERT rows (modes 0 and 2 only)

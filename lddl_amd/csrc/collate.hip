@@ -53,9 +53,10 @@ __global__ __launch_bounds__(256) void collate_len_kernel(CollateParams P) {
   }
 }
 
-// WWM (launched for mode 2 only, P.cont set): whole-word masking; pass 2 finds
-// every column's word head with word_heads over the ids of the LDS row
-template <bool WWM>
+// SEL (word or span: launched for mode 2 only, P.cont set): whole-word or span
+// masking; pass 2 finds every column's pick with step_picks over the ids of
+// the LDS row
+template <int SEL>
 __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
   __shared__ int32_t s_ids[4][COLLATE_MAX_LEN];
   __shared__ int32_t s_lab[4][COLLATE_MAX_LEN];
@@ -122,8 +123,8 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
     int64_t* o_tt = P.token_type_ids + r * (int64_t)L;
     int64_t* o_am = P.attention_mask + r * (int64_t)L;
     int64_t* o_lab = P.labels + r * (int64_t)L;
-    if constexpr (WWM) {
-      int32_t carry = -1;
+    if constexpr (SEL != SEL_TOKEN) {
+      StepCarry carry;
       for (int32_t base = 0; base < L; base += 64) {
         const int32_t j = base + lane;
         const bool pad = j >= L || S.pad(j);
@@ -131,12 +132,12 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
         int64_t id = 0;
         if (!pad) id = S.base_id(j, V.cls, V.sep, [&](int32_t c) { return ids[c]; });
         const bool start = !special && (S.special(j - 1) || !word_cont(P.cont, V.n_random, id));
-        int32_t head[1];
-        word_heads<1>(base, {start}, carry, head);
+        int32_t pick[1];
+        step_picks<SEL, 1>(P.span, P.seed, P.counter, r, base, {start}, {special}, carry, pick);
         if (j < L) {
           int64_t l;
-          id = mask_one_at(id, special, r, j, head[0], P.seed, P.counter, P.mlm_probability, V.mask_id, V.n_random,
-                           P.ignore_index, l);
+          id = mask_one_picked<SEL>(id, special, r, j, pick[0], P.seed, P.counter, P.mlm_probability, V.mask_id,
+                                    V.n_random, P.ignore_index, l);
           o_ids[j] = id;
           o_tt[j] = S.token_type(j);
           o_am[j] = pad ? 0 : 1;
@@ -182,7 +183,9 @@ __global__ __launch_bounds__(256) void mask_tokens_kernel(MaskParams M) {
 // is the row's first, follows a special one or holds no "##" entry (an id
 // outside the vocabulary is none).  A lane reads its id and its special flag,
 // and takes the flag of the column to its left from its neighbour (lane 0:
-// from lane 63 of the step before), before it stores.
+// from lane 63 of the step before), before it stores.  SEL: whole words, or
+// spans of them (special: the caller's mask, and the columns behind the row).
+template <int SEL>
 __global__ __launch_bounds__(256) void mask_tokens_word_kernel(MaskParams M) {
   const int lane = threadIdx.x & 63;
   const int32_t S = M.seq_len;
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(256) void mask_tokens_word_kernel(MaskParams M) {
     int64_t* in = M.inputs + r * (int64_t)S;
     const int64_t* sp = M.special + r * (int64_t)S;
     int64_t* lab = M.labels + r * (int64_t)S;
-    int32_t carry = -1;
+    StepCarry carry;
     uint32_t left_special = 1;  // of the column in front of the step: none in front of column 0
     for (int32_t base = 0; base < S; base += 64) {
       const int32_t j = base + lane;
@@ -202,12 +205,12 @@ __global__ __launch_bounds__(256) void mask_tokens_word_kernel(MaskParams M) {
       const uint32_t before = lane ? shifted : left_special;
       left_special = lane_get(special, 63);
       const bool start = !special && (before || !word_cont(M.cont, M.n_random, id));
-      int32_t head[1];
-      word_heads<1>(base, {start}, carry, head);
+      int32_t pick[1];
+      step_picks<SEL, 1>(M.span, M.seed, M.counter, r, base, {start}, {special != 0}, carry, pick);
       if (in_row) {
         int64_t l;
-        in[j] = mask_one_at(id, special != 0, r, j, head[0], M.seed, M.counter, M.mlm_probability, M.mask_id,
-                            M.n_random, M.ignore_index, l);
+        in[j] = mask_one_picked<SEL>(id, special != 0, r, j, pick[0], M.seed, M.counter, M.mlm_probability, M.mask_id,
+                                     M.n_random, M.ignore_index, l);
         lab[j] = l;
       }
     }
@@ -223,8 +226,10 @@ hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s) {
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.n_rows, n_cu)), block(256);
-  if (P.mode == COLLATE_DYNAMIC && P.cont) hipLaunchKernelGGL(collate_fill_kernel<true>, grid, block, 0, s, P);
-  else hipLaunchKernelGGL(collate_fill_kernel<false>, grid, block, 0, s, P);
+  const int sel = P.mode == COLLATE_DYNAMIC ? collate_sel(P.cont, P.span) : SEL_TOKEN;
+  if (sel == SEL_SPAN) hipLaunchKernelGGL(collate_fill_kernel<SEL_SPAN>, grid, block, 0, s, P);
+  else if (sel == SEL_WORD) hipLaunchKernelGGL(collate_fill_kernel<SEL_WORD>, grid, block, 0, s, P);
+  else hipLaunchKernelGGL(collate_fill_kernel<SEL_TOKEN>, grid, block, 0, s, P);
   return hipGetLastError();
 }
 
@@ -232,7 +237,9 @@ hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s) {
   const int64_t total = M.n_rows * (int64_t)M.seq_len;
   if (total <= 0) return hipSuccess;
   if (M.cont) {
-    hipLaunchKernelGGL(mask_tokens_word_kernel, dim3(grid_rows(M.n_rows, n_cu)), dim3(256), 0, s, M);
+    const dim3 grid(grid_rows(M.n_rows, n_cu)), block(256);
+    if (M.span.L > 0) hipLaunchKernelGGL(mask_tokens_word_kernel<SEL_SPAN>, grid, block, 0, s, M);
+    else hipLaunchKernelGGL(mask_tokens_word_kernel<SEL_WORD>, grid, block, 0, s, M);
     return hipGetLastError();
   }
   int64_t g = (total + 255) / 256;

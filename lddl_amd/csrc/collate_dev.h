@@ -2,13 +2,15 @@
 // strings; rows_from_strings.hip: a row table from parquet strings;
 // collate_rows.hip / collate_unpadded.hip: rows from a pack result's
 // spans, padded and padding-free): the error word, the counter-based draws of
-// `_mask_tokens`, and what reads a string column: Python's str.split(), the
+// `_mask_tokens` with the wave-level scans of whole-word and span selection,
+// and what reads a string column: Python's str.split(), the
 // whole-token vocab lookup and the np.save header of masked_lm_positions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "collate.h"
+#include "wave.h"
 
 namespace lddl {
 
@@ -34,6 +36,19 @@ __device__ __forceinline__ uint64_t mask_idx(int64_t row, int32_t col) {
   return ((uint64_t)row << 20 | (uint64_t)col) * 3ull;
 }
 
+// a selected column (row, col): its label, and [MASK] / a random id / the id
+// kept by its own second and third draws
+__device__ __forceinline__ int64_t mask_selected(int64_t id, int64_t row, int32_t col, uint64_t k, int32_t mask_id,
+                                                 int32_t n_random, int64_t& label) {
+  label = id;
+  const uint64_t idx = mask_idx(row, col);
+  const uint64_t h = splitmix64(k + idx + 1);
+  if (unit53(h) < 0.8) return mask_id;
+  const uint64_t g = splitmix64(k + idx + 2);
+  if (unit53(g) < 0.5) return (int64_t)(((g & 0xFFFFFFFFull) * (uint64_t)n_random) >> 32);
+  return id;
+}
+
 // _mask_tokens for one column whose select draw is taken at column sel of its
 // row and whose replacement draws are its own: returns the (possibly replaced)
 // input id and sets label
@@ -43,13 +58,7 @@ __device__ __forceinline__ int64_t mask_one_at(int64_t id, bool special, int64_t
   const uint64_t k = mask_key(seed, counter);
   label = ignore;
   if (special || !(unit53(splitmix64(k + mask_idx(row, sel))) < p)) return id;
-  label = id;
-  const uint64_t idx = mask_idx(row, col);
-  const uint64_t h = splitmix64(k + idx + 1);
-  if (unit53(h) < 0.8) return mask_id;
-  const uint64_t g = splitmix64(k + idx + 2);
-  if (unit53(g) < 0.5) return (int64_t)(((g & 0xFFFFFFFFull) * (uint64_t)n_random) >> 32);
-  return id;
+  return mask_selected(id, row, col, k, mask_id, n_random, label);
 }
 
 // _mask_tokens for one column: every column selects for itself
@@ -97,6 +106,104 @@ __device__ __forceinline__ void word_heads(int32_t base, const bool (&st)[W], in
   for (int t = 0; t < W; ++t)
     if (m[t]) last = max(last, base + W * (63 - __clzll((long long)m[t])) + t);
   carry = last;
+}
+
+// ------------------------------------------------------------ span masking --
+// (lddl_set_span_mask; include/lddl_amd.h defines it.)  What a row carries
+// from step to step, wave-uniform: the running word index, and the furthest
+// reach of the open heads so far.
+struct SpanCarry {
+  uint32_t word = 0, reach = 0;
+};
+
+// len(h) of the open head at (row, col): 1 + the entries of cdf that its draw
+// is not below.  The entries from L - 1 on are 1.0, above every draw, so the
+// compares need no L and every index is a constant (scalar loads).
+__device__ __forceinline__ uint32_t span_len(const SpanLaw& S, uint64_t ks, int64_t row, int32_t col) {
+  const double u = unit53(splitmix64(ks + mask_idx(row, col)));
+  uint32_t len = 1;
+#pragma unroll
+  for (int t = 0; t < 15; ++t) len += u >= S.cdf[t] ? 1u : 0u;
+  return len;
+}
+
+// Which columns of one step of a row are selected.  The step and st are
+// word_heads'; sp[k]: the lane's column k is special (true as well on a column
+// that is not the row's).  The word index of a column is a running count over
+// the row, + 1 at every word start and + L at every special column: the
+// ballots' bits below the lane, the lane's own columns and carry.word.  An
+// open head h reaches up to index(h) + len(h); a column is selected iff the
+// furthest reach of the open heads at or before it (an inclusive max-scan over
+// the lanes, and carry.reach) exceeds its index.  The + L keeps a reach out of
+// the segments behind it: their indices start above index(h) + L.  The length
+// draw is taken on the lanes that hold an open head only.  Registers, scalars
+// and wave operations only.  Every lane of the wave calls it.
+template <int W>
+__device__ __forceinline__ void span_select(const SpanLaw& S, uint64_t seed, uint64_t counter, int64_t row,
+                                            int32_t base, const bool (&st)[W], const bool (&sp)[W], SpanCarry& carry,
+                                            bool (&sel)[W]) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t k = mask_key(seed, counter), ks = splitmix64(k ^ 0x5350414E4D41534Bull);
+  const uint32_t L = (uint32_t)S.L;
+  uint32_t x = carry.word, step = 0;
+#pragma unroll
+  for (int t = 0; t < W; ++t) {
+    const uint64_t ms = __ballot(st[t]), mp = __ballot(sp[t]);
+    x += (uint32_t)bits_below(ms) + L * (uint32_t)bits_below(mp);
+    step += (uint32_t)__popcll(ms) + L * (uint32_t)__popcll(mp);
+  }
+  uint32_t index[W], reach[W], m = 0;  // reach[t]: of the lane's own open heads up to its column t
+#pragma unroll
+  for (int t = 0; t < W; ++t) {
+    x += st[t] ? 1u : sp[t] ? L : 0u;
+    index[t] = x;
+    const int32_t col = base + W * lane + t;
+    if (st[t] && unit53(splitmix64(k + mask_idx(row, col))) < S.q) m = max(m, x + span_len(S, ks, row, col));
+    reach[t] = m;
+  }
+  const uint32_t incl = wave_incl_max(m);
+  const uint32_t before = max(carry.reach, wave_shr1(incl));  // of the lanes below, and of the steps before
+#pragma unroll
+  for (int t = 0; t < W; ++t) sel[t] = !sp[t] && max(before, reach[t]) > index[t];
+  carry.word += step;
+  carry.reach = max(carry.reach, lane_get(incl, 63));
+}
+
+// -------------------------------- a step of whole-word or of span selection --
+struct StepCarry {
+  int32_t head = -1;  // SEL_WORD: word_heads' carry
+  SpanCarry span;     // SEL_SPAN
+};
+
+// pick[k] of the lane's column k: the head of its word (SEL_WORD), or whether
+// a span covers it (SEL_SPAN); st and sp as span_select has them
+template <int SEL, int W>
+__device__ __forceinline__ void step_picks(const SpanLaw& S, uint64_t seed, uint64_t counter, int64_t row, int32_t base,
+                                           const bool (&st)[W], const bool (&sp)[W], StepCarry& carry,
+                                           int32_t (&pick)[W]) {
+  static_assert(SEL == SEL_WORD || SEL == SEL_SPAN, "tokens select for themselves");
+  if constexpr (SEL == SEL_WORD) {
+    word_heads<W>(base, st, carry.head, pick);
+  } else {
+    bool sel[W];
+    span_select<W>(S, seed, counter, row, base, st, sp, carry.span, sel);
+#pragma unroll
+    for (int t = 0; t < W; ++t) pick[t] = sel[t] ? 1 : 0;
+  }
+}
+
+// _mask_tokens for one column with its pick of step_picks
+template <int SEL>
+__device__ __forceinline__ int64_t mask_one_picked(int64_t id, bool special, int64_t row, int32_t col, int32_t pick,
+                                                   uint64_t seed, uint64_t counter, double p, int32_t mask_id,
+                                                   int32_t n_random, int64_t ignore, int64_t& label) {
+  if constexpr (SEL == SEL_WORD) {
+    return mask_one_at(id, special, row, col, pick, seed, counter, p, mask_id, n_random, ignore, label);
+  } else {
+    label = ignore;
+    if (!pick) return id;
+    return mask_selected(id, row, col, mask_key(seed, counter), mask_id, n_random, label);
+  }
 }
 
 static constexpr uint32_t kEmpty = 0xFFFFFFFFu;

@@ -59,10 +59,10 @@ __device__ __forceinline__ unsigned long long wave_total64(uint32_t x) {
 
 }  // namespace
 
-template <int MODE, bool CODE, bool WWM = false>
+template <int MODE, bool CODE, int SEL = SEL_TOKEN>
 __global__ __launch_bounds__(256) void collate_fixed_kernel(CollateFixedParams P) {
   static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
-  static_assert(!WWM || MODE == COLLATE_DYNAMIC, "whole-word masking is dynamic masking");
+  static_assert(SEL == SEL_TOKEN || MODE == COLLATE_DYNAMIC, "whole-word and span masking are dynamic masking");
   // mode 1 only: per wave, label | token << 16 of every masked token
   __shared__ uint32_t s_mlm[MODE == COLLATE_STATIC ? 4 : 1][MODE == COLLATE_STATIC ? COLLATE_MAX_LEN : 1];
   __shared__ unsigned long long s_sum[2];  // tokens in front of the block's run, tokens of the batch
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void collate_fixed_kernel(CollateFixedParams P
       }
       const int64_t c1 = s_end[t];
       if (c1 > T) continue;  // the batch passes tok_cap (block 0 says so): a row that would pass it is not stored
-      stream_row<MODE, WWM>(R, O, mlm, rr, c1 - O.L.n, wide, P.position_ids);
+      stream_row<MODE, SEL>(R, O, mlm, rr, c1 - O.L.n, wide, P.position_ids);
       if (!CODE && lane == 0) R.next_sentence_labels[rr] = O.flags & 1u;
     }
     // (the next step's s_wave / s_end are written behind its first barrier / after every wave has left this loop)
@@ -198,9 +198,13 @@ hipError_t launch_collate_fixed(const CollateFixedParams& P0, bool code, int32_t
   const int g = grid_rows(n > P.tok_cap / 256 ? n : P.tok_cap / 256, n_cu);
   P.rows_per_block = ((n + g - 1) / g + 3) & ~(int64_t)3;
   const dim3 grid(g), block(256);
-  if (mode == COLLATE_DYNAMIC && P.R.cont) {
-    if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, true>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, true>), grid, block, 0, s, P);
+  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.R.cont, P.R.span) : SEL_TOKEN;
+  if (sel == SEL_SPAN) {
+    if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, SEL_SPAN>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, SEL_SPAN>), grid, block, 0, s, P);
+  } else if (sel == SEL_WORD) {
+    if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, SEL_WORD>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, SEL_WORD>), grid, block, 0, s, P);
   } else if (code) {
     dispatch_code_mode(mode, [&](auto m) {
       hipLaunchKernelGGL((collate_fixed_kernel<decltype(m)::value, true>), grid, block, 0, s, P);

@@ -146,8 +146,8 @@ __device__ __forceinline__ RowColumn row_column(const CollateRowsParams& P, cons
   return o;
 }
 
-// Whole-word masking (mode 2, P.cont set): a column in two halves, with
-// word_heads (collate_dev.h) over the start flags of the step between them.
+// Whole-word and span masking (mode 2, P.cont set): a column in two halves,
+// with step_picks (collate_dev.h) over the start flags of the step between them.
 struct WordColumn {
   int64_t id;    // the unmasked id (0 where !valid or pad)
   bool special;  // never selected: a special token, a pad column, or not a column of the row
@@ -168,12 +168,27 @@ __device__ __forceinline__ WordColumn word_column(const CollateRowsParams& P, co
   return c;
 }
 
-// row_column<COLLATE_DYNAMIC> of a column whose word starts at column head
-__device__ __forceinline__ RowColumn row_column_word(const CollateRowsParams& P, const OpenRow& R, int64_t r, int32_t j,
-                                                     const WordColumn& c, int32_t head) {
+// the picks of a step of batch row r (step_picks, collate_dev.h): lane l holds columns base + W * l + k
+template <int SEL, int W>
+__device__ __forceinline__ void row_picks(const CollateRowsParams& P, int64_t r, int32_t base, const WordColumn (&c)[W],
+                                          StepCarry& carry, int32_t (&pick)[W]) {
+  bool st[W], sp[W];
+#pragma unroll
+  for (int k = 0; k < W; ++k) {
+    st[k] = c[k].start;
+    sp[k] = c[k].special;
+  }
+  step_picks<SEL, W>(P.span, P.seed, P.counter, r, base, st, sp, carry, pick);
+}
+
+// row_column<COLLATE_DYNAMIC> of a column with its pick: the column where its word starts (SEL_WORD), or whether a
+// span covers it (SEL_SPAN)
+template <int SEL>
+__device__ __forceinline__ RowColumn row_column_picked(const CollateRowsParams& P, const OpenRow& R, int64_t r, int32_t j,
+                                                       const WordColumn& c, int32_t pick) {
   RowColumn o;
-  o.id = mask_one_at(c.id, c.special, r, j, head, P.seed, P.counter, P.mlm_probability, P.mask_id, P.n_random,
-                     P.ignore_index, o.lab);
+  o.id = mask_one_picked<SEL>(c.id, c.special, r, j, pick, P.seed, P.counter, P.mlm_probability, P.mask_id, P.n_random,
+                              P.ignore_index, o.lab);
   o.tt = R.L.token_type(j);
   return o;
 }
@@ -187,10 +202,10 @@ __device__ __forceinline__ RowColumn row_column_word(const CollateRowsParams& P,
 // token pairs that cover the row: a lane computes both tokens of a pair and
 // stores 16 B per output; the first pair of an odd start and the last pair of an
 // odd end hold one token of this row and store 8 B.  Without it, lane = token.
-// WWM (mode 2 only): whole-word masking, as in collate_rows_kernel.  A step of
-// the wide path is the 128 tokens of 64 aligned pairs, the first of them -1
-// (not a token of the row) when the row starts at an odd offset.
-template <int MODE, bool WWM>
+// SEL (word or span: mode 2 only): what is selected, as in collate_rows_kernel.
+// A step of the wide path is the 128 tokens of 64 aligned pairs, the first of
+// them -1 (not a token of the row) when the row starts at an odd offset.
+template <int MODE, int SEL>
 __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const OpenRow& S, const uint32_t* mlm, int64_t r,
                                            int64_t c0, bool wide, int64_t* position_ids) {
   const int lane = threadIdx.x & 63;
@@ -199,8 +214,8 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
   int64_t* o_tt = R.token_type_ids + c0;
   int64_t* o_pos = position_ids + c0;
   int64_t* o_lab = R.labels + c0;
-  if constexpr (WWM) {
-    int32_t carry = -1;
+  if constexpr (SEL != SEL_TOKEN) {
+    StepCarry carry;
     if (wide) {
       const int32_t head = (int32_t)(c0 & 1);
       const int32_t nq = (head + n + 1) >> 1;
@@ -208,12 +223,11 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
         const int32_t q = qb + lane;
         const int32_t j0 = 2 * q - head, j1 = j0 + 1;
         const bool v0 = q < nq && j0 >= 0, v1 = q < nq && j1 < n;
-        const WordColumn w0 = word_column(R, S, j0, v0, false);
-        const WordColumn w1 = word_column(R, S, j1, v1, false);
-        int32_t wh[2];
-        word_heads<2>(2 * qb - head, {w0.start, w1.start}, carry, wh);
-        const RowColumn t0 = row_column_word(R, S, r, j0, w0, wh[0]);
-        const RowColumn t1 = row_column_word(R, S, r, j1, w1, wh[1]);
+        const WordColumn w[2] = {word_column(R, S, j0, v0, false), word_column(R, S, j1, v1, false)};
+        int32_t pick[2];
+        row_picks<SEL, 2>(R, r, 2 * qb - head, w, carry, pick);
+        const RowColumn t0 = row_column_picked<SEL>(R, S, r, j0, w[0], pick[0]);
+        const RowColumn t1 = row_column_picked<SEL>(R, S, r, j1, w[1], pick[1]);
         if (v0 && v1) {
           *reinterpret_cast<longlong2*>(o_ids + j0) = make_longlong2(t0.id, t1.id);
           *reinterpret_cast<longlong2*>(o_tt + j0) = make_longlong2(t0.tt, t1.tt);
@@ -231,11 +245,11 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
     } else {
       for (int32_t base = 0; base < n; base += 64) {
         const int32_t j = base + lane;
-        const WordColumn w0 = word_column(R, S, j, j < n, false);
-        int32_t wh[1];
-        word_heads<1>(base, {w0.start}, carry, wh);
+        const WordColumn w[1] = {word_column(R, S, j, j < n, false)};
+        int32_t pick[1];
+        row_picks<SEL, 1>(R, r, base, w, carry, pick);
         if (j < n) {
-          const RowColumn t = row_column_word(R, S, r, j, w0, wh[0]);
+          const RowColumn t = row_column_picked<SEL>(R, S, r, j, w[0], pick[0]);
           o_ids[j] = t.id;
           o_tt[j] = t.tt;
           o_pos[j] = j;

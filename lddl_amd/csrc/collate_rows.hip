@@ -67,14 +67,16 @@ __global__ __launch_bounds__(256) void collate_rows_len_kernel(CollateRowsParams
   if ((threadIdx.x & 63) == 63 && m) atomicMax(P.max_len, (int32_t)m);
 }
 
-// WWM (mode 2 only): whole-word masking.  The select draw of a column is taken
-// at the head of its word; the wave finds the heads of a step's columns from
-// ballots of the word starts and carries the last one to the next step
-// (word_heads), so the loops run for the whole wave and predicate the stores.
-template <int MODE, bool CODE, bool WWM = false>
+// SEL (mode 2 only) SEL_WORD: whole-word masking.  The select draw of a column
+// is taken at the head of its word; the wave finds the heads of a step's
+// columns from ballots of the word starts and carries the last one to the next
+// step (word_heads), so the loops run for the whole wave and predicate the
+// stores.  SEL_SPAN: span masking, the same loops with span_select's scan in
+// place of word_heads.
+template <int MODE, bool CODE, int SEL = SEL_TOKEN>
 __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) {
   static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
-  static_assert(!WWM || MODE == COLLATE_DYNAMIC, "whole-word masking is dynamic masking");
+  static_assert(SEL == SEL_TOKEN || MODE == COLLATE_DYNAMIC, "whole-word and span masking are dynamic masking");
   // mode 1 only: per wave, label | token << 16 of every masked column
   __shared__ uint32_t s_mlm[MODE == COLLATE_STATIC ? 4 : 1][MODE == COLLATE_STATIC ? COLLATE_MAX_LEN : 1];
   const int lane = threadIdx.x & 63;
@@ -98,18 +100,17 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
     int64_t* o_tt = P.token_type_ids + r * (int64_t)L;
     int64_t* o_am = P.attention_mask + r * (int64_t)L;
     int64_t* o_lab = P.labels + r * (int64_t)L;
-    if constexpr (WWM) {
-      int32_t carry = -1;
+    if constexpr (SEL != SEL_TOKEN) {
+      StepCarry carry;
       if (wide) {
         for (int32_t base = 0; base < L; base += 128) {
           const int32_t j = base + 2 * lane;  // L is even: j < L means j + 1 < L
-          const WordColumn w0 = word_column(P, R, j, j < L, j >= n);
-          const WordColumn w1 = word_column(P, R, j + 1, j < L, j + 1 >= n);
-          int32_t head[2];
-          word_heads<2>(base, {w0.start, w1.start}, carry, head);
+          const WordColumn wc[2] = {word_column(P, R, j, j < L, j >= n), word_column(P, R, j + 1, j < L, j + 1 >= n)};
+          int32_t pick[2];
+          row_picks<SEL, 2>(P, r, base, wc, carry, pick);
           if (j < L) {
-            const RowColumn c0 = row_column_word(P, R, r, j, w0, head[0]);
-            const RowColumn c1 = row_column_word(P, R, r, j + 1, w1, head[1]);
+            const RowColumn c0 = row_column_picked<SEL>(P, R, r, j, wc[0], pick[0]);
+            const RowColumn c1 = row_column_picked<SEL>(P, R, r, j + 1, wc[1], pick[1]);
             *reinterpret_cast<longlong2*>(o_ids + j) = make_longlong2(c0.id, c1.id);
             *reinterpret_cast<longlong2*>(o_tt + j) = make_longlong2(c0.tt, c1.tt);
             *reinterpret_cast<longlong2*>(o_am + j) = make_longlong2(j < n ? 1 : 0, j + 1 < n ? 1 : 0);
@@ -119,11 +120,11 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
       } else {
         for (int32_t base = 0; base < L; base += 64) {
           const int32_t j = base + lane;
-          const WordColumn w0 = word_column(P, R, j, j < L, j >= n);
-          int32_t head[1];
-          word_heads<1>(base, {w0.start}, carry, head);
+          const WordColumn wc[1] = {word_column(P, R, j, j < L, j >= n)};
+          int32_t pick[1];
+          row_picks<SEL, 1>(P, r, base, wc, carry, pick);
           if (j < L) {
-            const RowColumn c = row_column_word(P, R, r, j, w0, head[0]);
+            const RowColumn c = row_column_picked<SEL>(P, R, r, j, wc[0], pick[0]);
             o_ids[j] = c.id;
             o_tt[j] = c.tt;
             o_am[j] = j < n ? 1 : 0;
@@ -166,9 +167,13 @@ hipError_t launch_collate_rows_len(const CollateRowsParams& P, bool code, int n_
 hipError_t launch_collate_rows(const CollateRowsParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.n_rows, n_cu)), block(256);
-  if (mode == COLLATE_DYNAMIC && P.cont) {
-    if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, true>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, true>), grid, block, 0, s, P);
+  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.cont, P.span) : SEL_TOKEN;
+  if (sel == SEL_SPAN) {
+    if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, SEL_SPAN>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, SEL_SPAN>), grid, block, 0, s, P);
+  } else if (sel == SEL_WORD) {
+    if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, SEL_WORD>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, SEL_WORD>), grid, block, 0, s, P);
   } else if (code) {
     dispatch_code_mode(mode, [&](auto m) {
       hipLaunchKernelGGL((collate_rows_kernel<decltype(m)::value, true>), grid, block, 0, s, P);

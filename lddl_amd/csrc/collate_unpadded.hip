@@ -101,11 +101,11 @@ __global__ __launch_bounds__(256) void collate_cu_scan_kernel(CollateUnpaddedPar
 
 }  // namespace
 
-// WWM (mode 2 only): whole-word masking, as in collate_rows_kernel.  The row's tokens: stream_row (collate_row.h).
-template <int MODE, bool CODE, bool WWM = false>
+// SEL (mode 2 only): tokens, whole words or spans, as in collate_rows_kernel.  The row's tokens: stream_row (collate_row.h).
+template <int MODE, bool CODE, int SEL = SEL_TOKEN>
 __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedParams P) {
   static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
-  static_assert(!WWM || MODE == COLLATE_DYNAMIC, "whole-word masking is dynamic masking");
+  static_assert(SEL == SEL_TOKEN || MODE == COLLATE_DYNAMIC, "whole-word and span masking are dynamic masking");
   // mode 1 only: per wave, label | token << 16 of every masked token
   __shared__ uint32_t s_mlm[MODE == COLLATE_STATIC ? 4 : 1][MODE == COLLATE_STATIC ? COLLATE_MAX_LEN : 1];
   const CollateRowsParams& R = P.R;
@@ -133,7 +133,7 @@ __global__ __launch_bounds__(256) void collate_unpadded_kernel(CollateUnpaddedPa
       if (lane == 0) set_err(R.err, code, r);
       continue;
     }
-    stream_row<MODE, WWM>(R, S, mlm, r, c0, wide, P.position_ids);
+    stream_row<MODE, SEL>(R, S, mlm, r, c0, wide, P.position_ids);
     if (!CODE && lane == 0) R.next_sentence_labels[r] = S.flags & 1u;
   }
 }
@@ -154,9 +154,13 @@ hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, 
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.R.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.R.n_rows, n_cu)), block(256);
-  if (mode == COLLATE_DYNAMIC && P.R.cont) {
-    if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, true>), grid, block, 0, s, P);
-    else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, true>), grid, block, 0, s, P);
+  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.R.cont, P.R.span) : SEL_TOKEN;
+  if (sel == SEL_SPAN) {
+    if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, SEL_SPAN>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, SEL_SPAN>), grid, block, 0, s, P);
+  } else if (sel == SEL_WORD) {
+    if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, SEL_WORD>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, SEL_WORD>), grid, block, 0, s, P);
   } else if (code) {
     dispatch_code_mode(mode, [&](auto m) {
       hipLaunchKernelGGL((collate_unpadded_kernel<decltype(m)::value, true>), grid, block, 0, s, P);

@@ -278,6 +278,28 @@ def load_shards(collate, path_or_paths, rank=None, world_size=None):
   return collate.load_rows(tables, np.concatenate(bins) if binned else None, np.concatenate(part), nbins)
 
 
+def _span_args(span_mask):
+  """``span_mask=`` of the collates -> (max_span, geo_p), or None when off"""
+  if span_mask is None or span_mask is False:
+    return None
+  if span_mask is True:
+    return 10, 0.2
+  try:
+    if isinstance(span_mask, dict):
+      extra = set(span_mask) - {'max_span', 'geo_p'}
+      if extra:
+        raise ValueError('unknown keys %s' % sorted(extra))
+      L, g = span_mask.get('max_span', 10), span_mask.get('geo_p', 0.2)
+    else:
+      L, g = span_mask
+    if isinstance(L, bool) or int(L) != L or not 1 <= int(L) <= 16 or not 0.0 < float(g) <= 1.0:
+      raise ValueError('max_span is an int in [1, 16], geo_p in (0, 1]')
+  except (TypeError, ValueError) as e:
+    raise ValueError('span_mask %r: None / False, True (max_span 10, geo_p 0.2), a (max_span, geo_p) pair or a dict '
+                     'of the two (%s)' % (span_mask, e)) from None
+  return int(L), float(g)
+
+
 class _RowCollate:
   """What BertCollate and CodeCollate share: the constructor, the staging of
   string columns, the collate of row-table batches (padded and padding-free),
@@ -288,13 +310,24 @@ class _RowCollate:
   VOCAB = _lib.VOCAB_BERT
 
   def __init__(self, vocab_file=None, device=None, sequence_length_alignment=8, ignore_index=-1,
-               mlm_probability=0.15, base_seed=12345, tokenizer=None, whole_word_mask=False, compact_mlm=False):
+               mlm_probability=0.15, base_seed=12345, tokenizer=None, whole_word_mask=False, compact_mlm=False,
+               span_mask=None):
     """whole_word_mask: dynamic masking (mode 2 and ``mask_tokens``) selects
     words, not tokens: a piece and the ``##`` pieces after it are masked
     together (lddl_set_whole_word_mask; include/lddl_amd.h defines it).  The
     switch lives on the tokenizer's ctx and is set here, on or off: with
     ``tokenizer=`` a shared ctx, every collate over that ctx follows the one
     constructed last.
+
+    span_mask: dynamic masking selects contiguous runs of whole words inside
+    one segment (ALBERT's n-gram masking, SpanBERT's span masking): True for
+    ``max_span=10, geo_p=0.2``, or a ``(max_span, geo_p)`` pair or dict; None
+    or False: off (lddl_set_span_mask; include/lddl_amd.h defines it).  Span
+    lengths follow SpanBERT's clipped geometric law, and spans start so often
+    that a word is covered with ``mlm_probability``; the 80/10/10 replacement
+    stays per token.  Set on the ctx as ``whole_word_mask`` is, on or off, with
+    the same rule for a shared ctx; not to be combined with
+    ``whole_word_mask=True`` (``max_span=1`` is whole-word masking).
 
     compact_mlm: every batch with ``labels`` (modes 1 and 2) also carries the
     compact targets of ``mlm_targets`` over those labels, as
@@ -310,12 +343,17 @@ class _RowCollate:
         raise ValueError('compact_mlm %r: False, True or a capacity >= 0' % (compact_mlm,))
     if compact_mlm is not False and int(ignore_index) >= 0:  # (before the ctx is made: nothing here needs a GPU)
       raise ValueError('compact_mlm needs a negative ignore_index: %d could be a label' % int(ignore_index))
+    self.span_mask = _span_args(span_mask)
+    if self.span_mask and whole_word_mask:
+      raise ValueError('span_mask and whole_word_mask=True: one selection at a time (spans are made of whole words)')
     self.compact_mlm = compact_mlm
     self.tok = tokenizer if tokenizer is not None else Tokenizer(vocab_file or self.VOCAB, device)
     self.whole_word_mask = bool(whole_word_mask)
     L = _lib.lib()
     if self.whole_word_mask or hasattr(L, 'lddl_set_whole_word_mask'):  # (an A/B library of an older revision lacks it)
       _lib.check(L.lddl_set_whole_word_mask(self.tok.handle, 1 if self.whole_word_mask else 0))
+    if self.span_mask or hasattr(L, 'lddl_set_span_mask'):
+      _lib.check(L.lddl_set_span_mask(self.tok.handle, *(self.span_mask or (0, 0.0))))
     self.device = self.tok.device
     self.sequence_length_alignment = sequence_length_alignment
     self.ignore_index = int(ignore_index)
@@ -761,8 +799,8 @@ class MlmCollate(CodeCollate):
   surface over the BERT vocabulary: ``collate_rows`` /
   ``collate_rows_unpadded`` / ``collate_rows_fixed`` over an MLM-only pack
   result, ``load_rows`` /
-  ``load_shards`` over MLM-only shards (A, num_tokens), ``whole_word_mask``
-  and ``compact_mlm`` as on the other classes.  Batches hold input_ids,
+  ``load_shards`` over MLM-only shards (A, num_tokens), ``whole_word_mask``,
+  ``span_mask`` and ``compact_mlm`` as on the other classes.  Batches hold input_ids,
   token_type_ids (all 0), attention_mask (unpadded: position_ids, cu_seqlens,
   max_seqlen) and labels (mode 0: special_tokens_mask); there is no
   next_sentence_labels.  Such a row is a CodeBERT row without docstring, so

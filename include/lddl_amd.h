@@ -181,6 +181,35 @@ int lddl_pack_mlm(lddl_ctx *ctx, lddl_pack *pack, const int32_t *d_ntok, const i
                   int64_t n_part, int32_t target_seq_length, double short_seq_prob, int32_t duplicate_factor,
                   uint64_t seed, int32_t bin_size, int64_t *out_totals, void *stream);
 
+/* Sentence-order packing (SOP, ALBERT's binary head): both segments of a row
+ * are consecutive sentences of ONE document, and is_random_next says whether
+ * they were exchanged.  The reference has no such mode; the draw order reuses
+ * its seams: random.seed(seed + p) per partition; per kept document (>= 2
+ * non-empty sentences; a document with fewer gives no row and consumes no
+ * draw; corpus order, duplicate_factor passes) the short_seq_prob draw of
+ * create_pairs_from_document (pretrain.py:259-265: target =
+ * target_seq_length - 3, or randint(2, that) when random() < short_seq_prob);
+ * sentences accumulate into a chunk that is flushed at the document's last
+ * sentence or once it holds >= target tokens and >= 2 sentences (no sentence
+ * is put back; a flushed chunk of one sentence, a document's trailing one,
+ * gives no row and no draw); per chunk of n sentences a_end = randint(1,
+ * n - 1) (:285-286, drawn for n == 2 too), swap = random() < 0.5, A =
+ * chunk[:a_end] and B = chunk[a_end:] exchanged when swap, then
+ * _truncate_seq_pair(A, B, target_seq_length - 3) on the post-swap pair
+ * (:161-176: the longer side, B on a tie, loses one token per random() coin,
+ * front when < 0.5); then random.shuffle of the partition's rows (:401) and
+ * the stable binning of binning.py:63-93.  Arguments, checks and out_totals
+ * as lddl_pack_mlm (out_totals[3] = 0); every d_ntok count <= 32768.  There
+ * is no error path.  A row is an lddl_pack_bert row ([CLS] A [SEP] B [SEP],
+ * flags bit0 = swap, bit1 set), so lddl_materialize, lddl_row_spans,
+ * lddl_row_docs and the render calls read it unchanged;
+ * lddl_masked_lm[_spans] refuse it (dynamic masking in the collate calls
+ * covers these rows). */
+int lddl_pack_sop(lddl_ctx *ctx, lddl_pack *pack, const int32_t *d_ntok, const int64_t *d_tok_off, const int64_t *d_sent_off,
+                  int64_t n_sent, const int64_t *d_doc_sent_off, int64_t n_doc, const int64_t *d_part_doc_off,
+                  int64_t n_part, int32_t target_seq_length, double short_seq_prob, int32_t duplicate_factor,
+                  uint64_t seed, int32_t bin_size, int64_t *out_totals, void *stream);
+
 /* d_ids: the dense ids lddl_tokenize wrote (and the pack call read).
  * Write the rows of `pack` in output order (partition-major,
  * bin-major, shuffled order within a bin = the reference's part.{p}.parquet_{b}

@@ -43,6 +43,8 @@ SIGNATURES = {
                                    ctypes.POINTER(c_int64), c_void_p]),
     'lddl_pack_mlm': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                               c_int64, c_int32, c_double, c_int32, c_uint64, c_int32, ctypes.POINTER(c_int64), c_void_p]),
+    'lddl_pack_sop': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                              c_int64, c_int32, c_double, c_int32, c_uint64, c_int32, ctypes.POINTER(c_int64), c_void_p]),
     'lddl_materialize': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p]),
     'lddl_row_spans': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

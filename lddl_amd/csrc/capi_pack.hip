@@ -78,7 +78,7 @@ static int pack_debug_report(const PackParams& P, int64_t n_part, hipStream_t st
 }
 
 // which packer a pack call runs (pack_common)
-enum PackKind { PACK_BERT = 0, PACK_CODEBERT = 1, PACK_MLM = 2 };
+enum PackKind { PACK_BERT = 0, PACK_CODEBERT = 1, PACK_MLM = 2, PACK_SOP = 3 };
 
 static int pack_common(lddl_ctx* c, lddl_pack* pk, PackKind kind, const int32_t* d_ntok, const int64_t* d_tok_off,
                        const int64_t* d_sent_off, int64_t n_sent,
@@ -227,6 +227,7 @@ static int pack_common(lddl_ctx* c, lddl_pack* pk, PackKind kind, const int32_t*
     }
     HIP_TRY(kind == PACK_CODEBERT ? launch_pack_codebert_wave(P, st)
             : kind == PACK_MLM    ? launch_pack_mlm_wave(P, st)
+            : kind == PACK_SOP    ? launch_pack_sop_wave(P, st)
                                   : launch_pack_bert_wave(P, st));
     if (P.dbg && kind == PACK_BERT && (rc = pack_debug_report(P, n_part, st))) return rc;
     HIP_TRY(launch_scan_parts(P.part_npairs, P.part_ntok, n_part, pair_base, tok_base, P.part_err, err_any, st));
@@ -291,6 +292,15 @@ extern "C" int lddl_pack_mlm(lddl_ctx* c, lddl_pack* pk, const int32_t* d_ntok, 
                              double short_seq_prob, int32_t duplicate_factor, uint64_t seed, int32_t bin_size,
                              int64_t* out_totals, void* stream) {
   return pack_common(c, pk, PACK_MLM, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, nullptr, n_doc, d_part_doc_off,
+                     n_part, target_seq_length, short_seq_prob, duplicate_factor, seed, bin_size, out_totals, stream);
+}
+
+extern "C" int lddl_pack_sop(lddl_ctx* c, lddl_pack* pk, const int32_t* d_ntok, const int64_t* d_tok_off,
+                             const int64_t* d_sent_off, int64_t n_sent, const int64_t* d_doc_sent_off, int64_t n_doc,
+                             const int64_t* d_part_doc_off, int64_t n_part, int32_t target_seq_length,
+                             double short_seq_prob, int32_t duplicate_factor, uint64_t seed, int32_t bin_size,
+                             int64_t* out_totals, void* stream) {
+  return pack_common(c, pk, PACK_SOP, d_ntok, d_tok_off, d_sent_off, n_sent, d_doc_sent_off, nullptr, n_doc, d_part_doc_off,
                      n_part, target_seq_length, short_seq_prob, duplicate_factor, seed, bin_size, out_totals, stream);
 }
 

@@ -7,7 +7,8 @@
 namespace lddl {
 
 // One packed instance.  BERT: seg0 = A, seg1 = B; CodeBERT: seg0 = doc,
-// seg1 = code; MLM-only: seg0 empty, seg1 = the row.  A segment is the concatenation of n filtered sentences
+// seg1 = code; MLM-only: seg0 empty, seg1 = the row; sentence-order pairs: as BERT, both segments from one
+// document, bit0 = exchanged.  A segment is the concatenation of n filtered sentences
 // starting at filtered-sentence slot fs, cut to the token window [lo, hi).
 struct PairRec {
   int64_t fs0, fs1;
@@ -155,6 +156,8 @@ size_t pack_dyn_bytes(int cap_lens, int cap_docs, int cap_pairs, bool mask);
 hipError_t launch_pack_codebert_wave(const PackParams& P, hipStream_t s);
 // MLM-only rows (single segment, no NSP): the CodeBERT packer's docstring-less record
 hipError_t launch_pack_mlm_wave(const PackParams& P, hipStream_t s);
+// sentence-order pairs (both segments from one document): the BERT packer's record, bit 0 = swapped
+hipError_t launch_pack_sop_wave(const PackParams& P, hipStream_t s);
 hipError_t launch_scan_parts(const int64_t* a, const int64_t* b, int64_t n, int64_t* sa, int64_t* sb,
                              const int32_t* err, int32_t* err_any, hipStream_t s);
 // algo 1: wave per partition (u16 copies); otherwise wave per 64 pairs with

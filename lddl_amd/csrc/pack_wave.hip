@@ -1645,4 +1645,183 @@ hipError_t launch_pack_mlm_wave(const PackParams& P, hipStream_t s) {
   return hipGetLastError();
 }
 
+
+// ------------------------------------------------- sentence-order pairs ----
+// _truncate_seq_pair (pretrain.py:161-176) on the segments [alo, ahi) and
+// [blo, bhi) down to max_num tokens together, 64 steps per round (the closed
+// form pack_bert_wave_kernel has inline).  Step t trims A while t < th when A
+// starts longer (pos), B while t < th otherwise -- B on a tie -- then the
+// sides alternate: side_a(t) = t < th ? pos : odd(t - th) == pos.  One coin (=
+// one random() call, 2 MT words) per step, front when the first word's MSB is
+// 0: a round reads its coins with one LDS load per lane and counts them with
+// ballots.  Rounds end at the MT19937 state's end; a coin that straddles the
+// twist is one serial step.  The counts stay on the vector unit (vpopc64): the
+// bounds are lane-uniform VGPR values, which the record's stores take as they
+// are (the CU's one scalar unit is what the packer waves share).
+__device__ __forceinline__ void trunc_pair_wave(WaveRng& rng, PackWaveLds& L, int lane, int& alo, int& ahi, int& blo,
+                                                int& bhi, int max_num) {
+  int E = (ahi - alo) + (bhi - blo) - max_num;
+  if (E <= 0) return;
+  int t0 = 0;
+  const int d0l = vgpr(ahi - alo) - (bhi - blo);
+  const int posi = d0l > 0 ? 1 : 0;
+  const int th = posi ? d0l : 1 - d0l;
+  while (E > 0) {
+    const int avail = (MT_N - rng.idx) >> 1;
+    if (avail == 0) {  // a coin straddles the twist: one serial step
+      // (arithmetic on the four bounds, no branch that picks one of them: they stay in registers)
+      const int sa = t0 < th ? posi : (((t0 - th) & 1) ^ posi ^ 1);
+      const int fr = rng.coin_lt_half() ? 1 : 0;
+      alo += sa & fr;
+      ahi -= sa & (fr ^ 1);
+      blo += (sa ^ 1) & fr;
+      bhi -= (sa ^ 1) & (fr ^ 1);
+      ++t0;
+      --E;
+      continue;
+    }
+    const int n = min(min(E, 64), avail);
+    const uint64_t act = __ballot(lane < n);
+    const int t = t0 + lane;
+    const int sbit = t < th ? posi : (((t - th) & 1) ^ posi ^ 1);  // 1: this step trims A
+    const int w = (int)WaveRng::temper(L.mt[min(rng.idx + 2 * lane, MT_N - 1)]);
+    const uint64_t SA = __ballot(sbit != 0) & act, F = __ballot(w >= 0) & act;  // front: MSB 0
+    const int x = vpopc64(SA & F), a = vpopc64(SA), f = vpopc64(F);
+    alo += x;
+    ahi -= a - x;
+    blo += f - x;
+    bhi -= n - a - f + x;
+    rng.idx += 2 * n;
+    t0 += n;
+    E -= n;
+  }
+}
+
+// Sentence-order pairs (SOP, ALBERT's binary head): both segments are
+// consecutive sentences of ONE document and the label says whether they were
+// exchanged (DESIGN.md "Sentence-order rows" holds the row definition).  The
+// reference has no such mode; the draws are its building blocks in its order:
+// the short_seq_prob draw of create_pairs_from_document (pretrain.py:259-265),
+// the A split a_end = randint(1, n - 1) (:285-286), one random() < 0.5 for the
+// swap, _truncate_seq_pair on the post-swap pair (:161-176), random.shuffle of
+// the partition's rows (:401), binning.py:63-93.  One wave per partition, in
+// the CodeBERT / MLM-only packers' shape: filter_slots, a chunk scan (the
+// first 64 sentences in registers, find_over beyond them), trunc_pair_wave,
+// then the shared shuffle and binning over global-memory arrays.  A row is an
+// NSP record with both windows in one document: seg0 = the post-swap A, seg1
+// = B, flags = swap | 2.
+// A chunk [cs, i] is flushed at the document's last sentence or once it holds
+// >= target tokens and >= 2 sentences; no sentence goes back.  A one-sentence
+// chunk (only a document's trailing sentence) gives no row and no draw, and a
+// document of < 2 kept sentences is dropped by the filter (no draw at all).
+// No error path: a side is trimmed only while the pair holds > max_num >= 2
+// tokens, i.e. >= 3, and the trimmed side is the longer one (B on a tie), so
+// it holds >= 2 tokens before the step and >= 1 after; the other side is not
+// touched.  Both sides start with >= 1 sentence of >= 1 token.
+// Capacities: every row holds >= 2 kept sentences and no sentence is in two
+// rows of a pass, so rows per pass <= kept sentences / 2 and np <= dup *
+// nsent / 2, within the partition's record slots.  A chunk of k >= 3
+// sentences holds < target tokens in its first k - 1, so k <= target <= 32765
+// (n0, n1: u16) and a side before truncation holds <= target - 1 + 32768
+// tokens; in a chunk of 2 sentences a side is one sentence, <= 32768
+// (d_ntok's bound, lddl_amd.h): lo / hi fit u16.  The chunk's sum is an int
+// (< 32765 + 65535); num_tokens <= max_seq <= 32768.
+__global__ __launch_bounds__(64) void pack_sop_wave_kernel(PackParams P) {
+  __shared__ PackWaveLds L;
+  const int lane = threadIdx.x;
+  const int64_t p = blockIdx.x;
+  if (p >= P.n_part) return;
+  const PartOpen O = open_part(P, p);
+  const int64_t d0 = O.d0, s0 = O.s0, pb = O.pb;
+  const int ndoc = O.ndoc;
+  // ---- filter: kept sentence slots (wave scan), documents with >= 2 -------
+  int32_t* kept_before = filter_slots(P, O, p, lane);
+  int nd_docs = 0;
+  for (int k = 0; k < ndoc; k += 64) {
+    const int kk = k + lane;
+    int first = 0, cnt = 0;
+    if (kk < ndoc) {
+      const int a = (int)(P.doc_sent_off[d0 + kk] - s0), b = (int)(P.doc_sent_off[d0 + kk + 1] - s0);
+      first = kept_before[a];
+      cnt = kept_before[b] - first;
+    }
+    const int keep = (kk < ndoc && cnt >= 2) ? 1 : 0;
+    const int incl = wave_incl_add(keep);
+    if (keep) {
+      const int di = nd_docs + incl - 1;
+      P.fd_first[d0 + di] = s0 + first;
+      P.fd_n[d0 + di] = cnt;
+    }
+    nd_docs += lane_get(incl, 63);
+  }
+  group_sync();
+  auto len_abs = [&](int64_t slot) -> int { return P.fs_ntok[slot]; };
+
+  WaveRng rng{L, lane, MT_N};
+  rng.load(P.mt_states + (int64_t)p * MT_N);
+  const int max_num = P.max_seq - 3;
+  PairRec* out = P.pairs + pb;
+  int np = 0;
+  for (int dup = 0; dup < P.dup; ++dup) {
+    for (int di = 0; di < nd_docs; ++di) {
+      const int64_t first = P.fd_first[d0 + di];
+      const int n = P.fd_n[d0 + di];
+      int target = max_num;
+      if (rng.random() < P.short_seq_prob) target = (int)rng.randint(2, max_num);
+      int cs = 0;
+      while (cs + 1 < n) {  // (cs == n - 1: the trailing one-sentence chunk, no row)
+        // the chunk's end i: the first sentence after cs that is the
+        // document's last or brings the chunk to >= target tokens.  The 64
+        // sentences from cs are scanned in registers (their prefix sums then
+        // give the A length with no second read); a longer chunk goes on
+        // with find_over from the scan's total.
+        const int kk = cs + lane;
+        const int l = kk < n ? len_abs(first + kk) : 0;
+        const int ps = wave_incl_add(l);
+        const uint64_t m = __ballot(kk < n && lane > 0 && (kk == n - 1 || ps >= target));
+        int i, cur, a_end, la;
+        if (m) {
+          const int j = (int)__builtin_ctzll(m);
+          i = cs + j;
+          cur = lane_get(ps, j);
+          a_end = (int)rng.randint(1, j);  // (n == 2: randint(1, 1) is still drawn)
+          la = lane_get(ps, a_end - 1);
+        } else {
+          i = find_over([&](int k) { return len_abs(first + k); }, cs + 64, n, n - 1, lane_get(ps, 63), target - 1, lane,
+                        &cur);
+          a_end = (int)rng.randint(1, i - cs);
+          la = range_sum([&](int k) { return len_abs(first + k); }, cs, cs + a_end, lane);
+        }
+        const int nchunk = i - cs + 1;
+        const bool swap = rng.coin_lt_half();
+        // the post-swap pair: A = the chunk's first a_end sentences, or its rest
+        const int64_t fsa = first + cs, fsb = first + cs + a_end;
+        const int n_a = a_end, n_b = nchunk - a_end;
+        const int l_a = la, l_b = cur - la;
+        int alo = 0, ahi = swap ? l_b : l_a, blo = 0, bhi = swap ? l_a : l_b;
+        trunc_pair_wave(rng, L, lane, alo, ahi, blo, bhi, max_num);
+        if (lane == 0) {
+          PairRec r;
+          r.fs0 = swap ? fsb : fsa; r.n0 = (uint16_t)(swap ? n_b : n_a); r.lo0 = (uint16_t)alo; r.hi0 = (uint16_t)ahi;
+          r.fs1 = swap ? fsa : fsb; r.n1 = (uint16_t)(swap ? n_a : n_b); r.lo1 = (uint16_t)blo; r.hi1 = (uint16_t)bhi;
+          r.flags = (uint16_t)((swap ? 1 : 0) | 2);
+          r.num_tokens = (uint16_t)((ahi - alo) + (bhi - blo) + 3);
+          out[np] = r;
+        }
+        ++np;
+        cs = i + 1;
+      }
+    }
+  }
+  if (lane == 0) P.part_err[p] = PACK_OK;
+  group_sync();
+  shuffle_pairs<false>(P, O, PackDyn{}, rng, p, np, lane);
+  bin_pairs<0, false>(P, O, PackDyn{}, p, np, lane);
+}
+
+hipError_t launch_pack_sop_wave(const PackParams& P, hipStream_t s) {
+  hipLaunchKernelGGL(pack_sop_wave_kernel, dim3((unsigned)P.n_part), dim3(64), 0, s, P);
+  return hipGetLastError();
+}
+
 }  // namespace lddl

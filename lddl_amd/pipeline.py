@@ -212,9 +212,16 @@ class PackResult:
     return out
 
 
+def _check_sop(sop, codebert, masking, nsp):
+  if sop and (codebert or masking or not nsp):
+    raise ValueError('sop=True packs sentence-order pairs: not with %s' % (
+        'codebert=True' if codebert else 'masking=True (the collate calls mask dynamically)' if masking else
+        'nsp=False (MLM-only rows have no pair)'))
+
+
 class PackHandle:
   """A pack result (lddl_pack_new / lddl_pack_free): what one
-  lddl_pack_bert / lddl_pack_codebert / lddl_pack_mlm call leaves for the post-pack calls
+  lddl_pack_bert / lddl_pack_codebert / lddl_pack_mlm / lddl_pack_sop call leaves for the post-pack calls
   (lddl_materialize, lddl_row_spans, lddl_masked_lm[_spans],
   lddl_row_docs), which name it explicitly."""
 
@@ -307,7 +314,7 @@ class Packer:
 
   def pack(self, shards, ids, ntok, tok_off=None, target_seq_length=128, short_seq_prob=0.1, duplicate_factor=5,
            seed=12345, bin_size=None, codebert=False, masking=False, masked_lm_ratio=0.15, stream=None,
-           spans=False, into=None, nsp=True):
+           spans=False, into=None, nsp=True, sop=False):
     """into: the PackHandle to pack into (default: the Packer's own).
     ids / ntok / tok_off: tokenize()'s dense CSR result (tok_off None:
     the exclusive scan of ntok, for ids built by hand); ids must hold 16
@@ -320,10 +327,16 @@ class Packer:
     nsp=False: MLM-only rows (lddl_pack_mlm): [CLS] consecutive sentences of
     one document [SEP], no pair and no NSP label; res.kind == 'mlm', the
     tokens in segment 1 (len0 == 0).  Not with codebert or masking (dynamic
-    masking in MlmCollate covers these rows)."""
+    masking in MlmCollate covers these rows).
+    sop=True: sentence-order pairs (lddl_pack_sop): A and B are consecutive
+    sentences of one document and is_random_next says whether they were
+    exchanged.  The rows are BERT rows (res.kind == 'bert'): the writer, the
+    balancer and every BertCollate route take them as they are.  Not with
+    codebert, masking (the collate calls mask dynamically) or nsp=False."""
     if not nsp and (codebert or masking):
       raise ValueError('nsp=False packs MLM-only rows: not with %s' % ('codebert=True' if codebert else
                                                                       'masking=True (MlmCollate masks dynamically)'))
+    _check_sop(sop, codebert, masking, nsp)
     L = _lib.lib()
     if tok_off is None:
       tok_off = torch.zeros(shards.n_sent + 1, dtype=torch.int64, device=self.device)
@@ -339,10 +352,11 @@ class Packer:
                                 _ptr(shards.doc_sent_off), _ptr(shards.doc_nseg_doc), shards.n_doc,
                                 _ptr(shards.part_doc_off), shards.n_part, target_seq_length, short_seq_prob,
                                 duplicate_factor, abs(int(seed)), bin_size or 0, tot, s)
-    elif not nsp:
-      rc = L.lddl_pack_mlm(self.tok.handle, h, _ptr(ntok), _ptr(tok_off), _ptr(shards.sent_off), shards.n_sent,
-                           _ptr(shards.doc_sent_off), shards.n_doc, _ptr(shards.part_doc_off), shards.n_part,
-                           target_seq_length, short_seq_prob, duplicate_factor, abs(int(seed)), bin_size or 0, tot, s)
+    elif not nsp or sop:
+      fn = L.lddl_pack_sop if sop else L.lddl_pack_mlm
+      rc = fn(self.tok.handle, h, _ptr(ntok), _ptr(tok_off), _ptr(shards.sent_off), shards.n_sent,
+              _ptr(shards.doc_sent_off), shards.n_doc, _ptr(shards.part_doc_off), shards.n_part,
+              target_seq_length, short_seq_prob, duplicate_factor, abs(int(seed)), bin_size or 0, tot, s)
     else:
       rc = L.lddl_pack_bert(self.tok.handle, h, _ptr(ids) if masking else None, _ptr(ntok), _ptr(tok_off),
                             _ptr(shards.sent_off), shards.n_sent,
@@ -423,9 +437,10 @@ def bin_rows(tok, num_tokens, bin_size, nbins, stream=None):
 
 def run_bert(corpus, vocab_file=VOCAB_BERT, target_seq_length=128, bin_size=None, n_partitions=1, seed=12345,
              device=None, check_host=False, duplicate_factor=5, short_seq_prob=0.1, part_doc_off=None,
-             codebert=False, masking=False, masked_lm_ratio=0.15, spans=False, nsp=True):
+             codebert=False, masking=False, masked_lm_ratio=0.15, spans=False, nsp=True, sop=False):
   if not nsp and (codebert or masking):
     raise ValueError('nsp=False packs MLM-only rows: not with codebert=True or masking=True')
+  _check_sop(sop, codebert, masking, nsp)
   device = device or torch.device('cuda', 0)
   if part_doc_off is None:
     part_doc_off = partition_by_bytes(corpus, n_partitions)
@@ -433,7 +448,7 @@ def run_bert(corpus, vocab_file=VOCAB_BERT, target_seq_length=128, bin_size=None
   sh = upload(corpus, part_doc_off, device)
   res = pk.run(sh, target_seq_length=target_seq_length, short_seq_prob=short_seq_prob,
                duplicate_factor=duplicate_factor, seed=seed, bin_size=bin_size, codebert=codebert,
-               masking=masking, masked_lm_ratio=masked_lm_ratio, spans=spans, nsp=nsp)
+               masking=masking, masked_lm_ratio=masked_lm_ratio, spans=spans, nsp=nsp, sop=sop)
   torch.cuda.synchronize(device)
   res.part_doc_off = np.asarray(part_doc_off)
   if check_host:

@@ -281,6 +281,10 @@ def attach_args(parser=None, codebert=False):
                     help_str='--no-nsp: MLM-only rows, [CLS] consecutive sentences of one document [SEP], written as '
                              'A / num_tokens shards for loader.MlmCollate (no B, no NSP label; this front end\'s '
                              'own flag, not with --masking or --output-format txt)')
+    p.add_argument('--sop', action='store_true',
+                   help='sentence-order pairs: A and B are consecutive sentences of one document and is_random_next '
+                        'says whether they were exchanged (ALBERT; this front end\'s own flag, not with --masking or '
+                        '--no-nsp). Same shard schema as the NSP pairs')
   p.add_argument('--sentence-splitter', type=str, default='auto', choices=['auto', 'punkt', 'rules'])
   attach_split_device_arg(p)
   p.add_argument('--chunk-mb', type=float, default=32.0,
@@ -312,6 +316,8 @@ def run_key(args, codebert, files, vocab, how, n_part):
   d = {k: getattr(args, k, None) for k in keys}
   if not getattr(args, 'nsp', True):  # (only then: the keys of runs without the flag stay what they were)
     d['nsp'] = False
+  if getattr(args, 'sop', False):  # (likewise)
+    d['sop'] = True
   d.update(codebert=codebert, splitter=how, n_part=n_part, vocab=os.path.abspath(vocab),
            vocab_size=os.path.getsize(vocab),
            files=[(os.path.abspath(f), os.path.getsize(f), os.stat(f).st_mtime_ns) for f in files])
@@ -368,8 +374,14 @@ def save_marker(sink, a, b, key, files, counts, n_pairs):
 
 
 def _check_nsp(args):
-  """--no-nsp packs MLM-only rows: no static masking (MlmCollate masks dynamically) and no txt sink; -> the
+  """--no-nsp packs MLM-only rows: no static masking (MlmCollate masks dynamically) and no txt sink; --sop packs
+  sentence-order pairs: no static masking either (the collate calls mask dynamically), and pairs; -> the
   complaint, or None"""
+  if getattr(args, 'sop', False):
+    if getattr(args, 'masking', False):
+      return '--sop does not go with --masking: sentence-order pairs are masked dynamically by the collate calls'
+    if not getattr(args, 'nsp', True):
+      return '--sop packs pairs: it does not go with --no-nsp'
   if getattr(args, 'nsp', True):
     return None
   if getattr(args, 'masking', False):
@@ -881,7 +893,8 @@ def main(args, codebert=False):
         res = pk.pack(sh, ids_d, ntok, toff, target_seq_length=args.target_seq_length,
                       short_seq_prob=args.short_seq_prob, duplicate_factor=args.duplicate_factor, seed=args.seed + a,
                       bin_size=args.bin_size, codebert=codebert, masking=masking,
-                      masked_lm_ratio=args.masked_lm_ratio, spans=True, nsp=nsp)
+                      masked_lm_ratio=args.masked_lm_ratio, spans=True, nsp=nsp,
+                      sop=getattr(args, 'sop', False))
         counts[a - lo:b - lo] = res.bin_count.view(b - a, -1).to(torch.int64)
         torch.cuda.synchronize()
         t['gpu_s'] += time.perf_counter() - t0

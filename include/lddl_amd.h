@@ -27,7 +27,8 @@
  *
  * Conventions: every pointer named d_* is a DEVICE pointer on the ctx's
  * device; work is enqueued on `stream` (a hipStream_t, NULL = default) and is
- * asynchronous.  Return value 0 = ok, < 0 = LDDL_E* (message: lddl_last_error,
+ * asynchronous.  Inputs need only be ready in stream order on `stream`, and
+ * outputs are ready in stream order on `stream`.  Return value 0 = ok, < 0 = LDDL_E* (message: lddl_last_error,
  * thread-local).  One call at a time per ctx (the ctx owns scratch).
  * Input text must be valid UTF-8 (Python str.encode output).
  */

@@ -23,7 +23,7 @@ import pyarrow as pa
 import torch
 
 from . import _lib
-from .tokenizer import _ptr, _stream
+from .tokenizer import _on_stream, _ptr, _stream
 from .writer import EncodeSink, FilePlan, render_call
 
 SCHEMA = pa.schema([('sentences', pa.string())])  # pretrain.py:144-146
@@ -64,11 +64,14 @@ class BartResult:
     return render_call(_lib.lib().lddl_bart_render, args, n, sh.data.device, stream, host)
 
 
+@_on_stream
 def aggregate(corpus_on_device, part_doc_off=None, target_seq_length=128, tokenizer_or_ctx=None, stream=None):
   """_aggregate_sentences over every document of a sentence-split corpus on
   the device (a pipeline.ShardSet).  part_doc_off: the partitions as document
   offsets (default: the ShardSet's).  tokenizer_or_ctx: a Tokenizer, Packer or
-  lddl_ctx handle (any vocabulary: it is not read)."""
+  lddl_ctx handle (any vocabulary: it is not read).  stream: the corpus need
+  only be ready in stream order on `stream`, and the plan is ready in stream
+  order on it."""
   sh = corpus_on_device
   if tokenizer_or_ctx is None:
     raise ValueError('aggregate needs a Tokenizer, a Packer or an lddl_ctx handle')

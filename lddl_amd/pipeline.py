@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .tokenizer import Tokenizer, _ptr, _stream
+from .tokenizer import Tokenizer, _on_stream, _ptr, _stream
 
 VOCAB_BERT = _lib.VOCAB_BERT
 VOCAB_CODEBERT = _lib.VOCAB_CODEBERT
@@ -312,10 +312,14 @@ class Packer:
         cap = e.total
     raise RuntimeError('lddl_amd: tokenize did not fit its exact total')
 
+  @_on_stream
   def pack(self, shards, ids, ntok, tok_off=None, target_seq_length=128, short_seq_prob=0.1, duplicate_factor=5,
            seed=12345, bin_size=None, codebert=False, masking=False, masked_lm_ratio=0.15, stream=None,
            spans=False, into=None, nsp=True, sop=False):
     """into: the PackHandle to pack into (default: the Packer's own).
+    stream: inputs need only be ready in stream order on `stream`, and outputs
+    are ready in stream order on `stream` (the scan of ntok for tok_off=None
+    runs on it too).
     ids / ntok / tok_off: tokenize()'s dense CSR result (tok_off None:
     the exclusive scan of ntok, for ids built by hand); ids must hold 16
     entries of padding past the last id (lddl_materialize's 16-B loads).

@@ -7,6 +7,8 @@ returns the same token strings (one sentence; convenience / parity surface),
 shard in one launch, inputs and outputs resident in HBM.
 """
 import ctypes
+import functools
+import inspect
 
 import numpy as np
 import torch
@@ -26,6 +28,25 @@ def _ptr(t):
 def _stream(stream=None):
   s = stream if stream is not None else torch.cuda.current_stream()
   return ctypes.c_void_p(s.cuda_stream)
+
+
+def _on_stream(fn):
+  """Runs fn under ``torch.cuda.stream(stream)`` for the ``stream=`` it is
+  given (None: the current stream, as it is), as splitgpu.split_device does:
+  the wrapper's own torch operations and read-backs (``.cpu()``, a scan, an
+  index) are then ordered on the stream its kernels run on.  Inputs need only
+  be ready in stream order on `stream`, and outputs are ready in stream order
+  on `stream`."""
+  sig = inspect.signature(fn)
+
+  @functools.wraps(fn)
+  def on_stream(*args, **kwargs):
+    stream = sig.bind(*args, **kwargs).arguments.get('stream')
+    if stream is None:
+      return fn(*args, **kwargs)
+    with torch.cuda.stream(stream):
+      return fn(*args, **kwargs)
+  return on_stream
 
 
 class CapacityError(RuntimeError):

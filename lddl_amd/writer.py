@@ -34,7 +34,7 @@ import torch
 
 from . import _lib, encode_worker
 from .arrow_cols import fixed_column, var_buffers, var_column
-from .tokenizer import _ptr, _stream
+from .tokenizer import _on_stream, _ptr, _stream
 
 SEG0, SEG1, ROW, SPAN = 0, 1, 2, 3
 from .hostinfo import DENSE_COLS  # noqa: E402  (re-exported: writer.DENSE_COLS)
@@ -135,10 +135,12 @@ def mlm_only_column(packer, res, r0, n, stream=None, host=True):
                 codebert=True, stream=stream, host=host)
 
 
+@_on_stream
 def row_docs(packer, res, n_copy=None, stream=None):
   """document index of every row of the pack result `res` (lddl_row_docs
   over res.pack, all rows on the device); the first n_copy of them copied to
-  the host"""
+  the host, on `stream` behind the kernel.  The pack need only be ready in
+  stream order on `stream`."""
   n_rows = res.n_pairs
   out = torch.empty(max(n_rows, 1), dtype=torch.int64, device=packer.device)
   _lib.check(_lib.lib().lddl_row_docs(packer.tok.handle, res.pack.handle, _ptr(out), _stream(stream)))
@@ -486,6 +488,7 @@ def pack_plan(res, bin_size, max_parts, part_base):
   return FilePlan(res.bin_count.cpu().numpy().reshape(n_part, res.nbins), bin_size is not None, max_parts, part_base)
 
 
+@_on_stream
 def mlm_positions(packer, res, r0, r1, n_rows, cache, stream=None, host=True):
   """masked_lm_positions of rows [r0, r1) as (offsets, bytes): render_npy,
   or where its header table does not apply npy_positions on the host copy of
@@ -552,6 +555,7 @@ class EncodeSink:
 LAST_STATS = {}  # the last write_shards call's stage seconds (bench.py reports them)
 
 
+@_on_stream
 def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=False, doc_ids=None,
                  part_base=0, compression='snappy', batch_rows=1 << 16, max_parts=None, stream=None,
                  executor=None, pending=None, nsp=True):
@@ -569,6 +573,8 @@ def write_shards(packer, res, out_dir, bin_size=None, codebert=False, masking=Fa
   the encodes run on while the caller's next chunk splits and packs.
   Rows are rendered in batches of whole files of about batch_rows rows, so
   the files of one batch encode while the next renders.
+  stream: ``res`` need only be ready in stream order on `stream`: the renders
+  and every read-back of its columns run on it.
   Returns the list of files (written once the futures are done)."""
   t_start = time.perf_counter()
   EncodeSink.check(executor, pending)
@@ -645,6 +651,7 @@ def encode_workers():
   return cpu_share()
 
 
+@_on_stream
 def write_txt(packer, res, out_dir, bin_size=None, codebert=False, masking=False, doc_ids=None, part_base=0,
               batch_rows=1 << 20, max_parts=None, stream=None, nsp=True):
   """The reference's txt sink (--output-format txt, pretrain.py:501-531,

@@ -262,12 +262,13 @@ class ProcessEncoder:
   The per-file part of pyarrow's writer holds the GIL, so a thread pool
   serialises on small files (CodeBERT's, ~100 rows each); processes each
   have their own.  A batch's columns are copied once into a shared slot
-  file under /dev/shm (device columns straight from the GPU, through the
-  slot pinned with hipHostRegister when the runtime allows), then each task
-  writes a run of the batch's files from it.  `slots` batches can be in
-  flight; a slot is reused once its batch's files are written.  Create it
-  before the process touches the GPU (its workers are forked); close() ends
-  the workers and removes the slot files."""
+  file under /dev/shm (device columns through pinned staging blocks of
+  torch's caching host allocator: a file mapping cannot be allocated pinned,
+  and memory the process already has cannot be pinned on every runtime), then
+  each task writes a run of the batch's files from it.  `slots` batches can
+  be in flight; a slot is reused once its batch's files are written.  Create
+  it before the process touches the GPU (its workers are forked); close()
+  ends the workers and removes the slot files."""
 
   def __init__(self, workers=None, slots=3, context='fork'):
     import multiprocessing as mp
@@ -282,7 +283,7 @@ class ProcessEncoder:
         d = '/dev/shm'
     import tempfile
     self.dir = tempfile.mkdtemp(prefix='lddl_enc_', dir=d)
-    self.slots = [dict(path=os.path.join(self.dir, 'slot%d' % i), size=0, mm=None, t=None, pinned=False, futs=[])
+    self.slots = [dict(path=os.path.join(self.dir, 'slot%d' % i), size=0, mm=None, t=None, futs=[])
                   for i in range(slots)]
     self.disk_dir = None  # (slots that outgrew /dev/shm: _grow)
     self.next = 0
@@ -296,11 +297,6 @@ class ProcessEncoder:
 
   def submit(self, fn, *a, **kw):  # (a plain task, as an executor)
     return self.ex.submit(fn, *a, **kw)
-
-  def _unpin(self, sl):
-    if sl['pinned']:
-      torch.cuda.cudart().cudaHostUnregister(sl['t'].data_ptr())
-      sl['pinned'] = False
 
   def _grow(self, sl, new):
     """The slot file at `new` bytes, its space reserved (posix_fallocate), so
@@ -346,8 +342,6 @@ class ProcessEncoder:
     self.wait_s += time.perf_counter() - t0
     sl['futs'] = []
     if sl['size'] < size:
-      import mmap
-      self._unpin(sl)
       sl['t'] = None
       if sl['mm'] is not None:
         sl['mm'].close()
@@ -356,11 +350,6 @@ class ProcessEncoder:
       sl['mm'] = self._grow(sl, new)
       sl['size'] = new
       sl['t'] = torch.frombuffer(sl['mm'], dtype=torch.uint8)
-      if torch.cuda.is_initialized():
-        try:
-          sl['pinned'] = torch.cuda.cudart().cudaHostRegister(sl['t'].data_ptr(), new, 0) == 0
-        except Exception:  # (not available: pageable copies)
-          sl['pinned'] = False
     return sl
 
   def submit_batch(self, n, specs, sch, files, compression, dict_cols, stream=None):
@@ -384,7 +373,7 @@ class ProcessEncoder:
     sl = self._acquire(max(pos, 64))
     t0 = time.perf_counter()
     dst = sl['t']
-    dev = False
+    staged = []
     st = None
     for (name, kind, a, b), (_, _, p0, p1) in zip(specs, lay):
       for x, at in ((a, p0), (b, p1)) if kind in ('str', 'bin') else ((a, p0),):
@@ -393,13 +382,16 @@ class ProcessEncoder:
           continue
         if isinstance(x, torch.Tensor):
           st = st or stream or torch.cuda.current_stream()
+          h = torch.empty(k, dtype=torch.uint8, pin_memory=True)
           with torch.cuda.stream(st):  # (the copies on the stream the columns were rendered on)
-            dst[at:at + k].copy_(x.reshape(-1).view(torch.uint8), non_blocking=sl['pinned'])
-          dev = True
+            h.copy_(x.reshape(-1).view(torch.uint8), non_blocking=True)
+          staged.append((h, at))
         else:
           dst[at:at + k].numpy()[:] = np.ascontiguousarray(x).reshape(-1).view(np.uint8)
-    if dev:
+    if staged:
       st.synchronize()
+      for h, at in staged:
+        dst[at:at + h.numel()].copy_(h)
     self.copy_s += time.perf_counter() - t0
     # tasks of about equal rows, at least one file each, ~2 per worker
     ntask = max(1, min(len(files), 2 * self.workers))
@@ -421,7 +413,6 @@ class ProcessEncoder:
     self.ex.shutdown(wait=True)
     t1 = time.perf_counter()
     for sl in self.slots:
-      self._unpin(sl)
       sl['t'] = None
       if sl['mm'] is not None:
         sl['mm'].close()
@@ -430,7 +421,7 @@ class ProcessEncoder:
     self._fin()
     if self.disk_dir is not None:
       self._fin_disk()
-    self.close_s = (t1 - t0, t2 - t1, time.perf_counter() - t2)  # workers' exit, slot unpin / unmap, slot files
+    self.close_s = (t1 - t0, t2 - t1, time.perf_counter() - t2)  # workers' exit, slot unmap, slot files
 
 
 def _host_var(arr, r0, n):

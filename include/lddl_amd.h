@@ -417,6 +417,56 @@ int lddl_mask_tokens(lddl_ctx *ctx, int64_t *d_inputs, const int64_t *d_special_
  * tests/wwm_model.py is this in numpy. */
 int lddl_set_whole_word_mask(lddl_ctx *ctx, int on);
 
+/* Exact-count dynamic masking: a fixed, bounded number of predictions per
+ * row, as the reference's static masking has it (pretrain.py:182-238
+ * `create_masked_lm_predictions`: max(1, round(len * ratio)) tokens of a row)
+ * and as the max_predictions_per_seq of Google's and Megatron's BERT recipes
+ * caps it.  max_predictions == 0 turns it off (the default); LDDL_EINVAL: a
+ * negative value, and the switch then stays as it was.  While it is on,
+ * lddl_mask_tokens and mode 2 of every collate call of the ctx
+ * (lddl_collate_bert, lddl_collate_rows[_unpadded | _fixed],
+ * lddl_collate_code_rows[_unpadded | _fixed]) select as follows; modes 0 and 1
+ * ignore it.  For one row, with special(j), cont, start(j), head(j), k,
+ * i(row, col) and sm exactly as defined above:
+ *   c          the number of non-special columns of the row
+ *   budget     = min(max_predictions, c, max(1, rint(c * mlm_probability))),
+ *              the product in double and rounded half to even, as Python's
+ *              round(); 0 when c == 0.  c counts the candidates, not
+ *              len(tokens) as the reference's static path does:
+ *              lddl_mask_tokens knows a special_tokens_mask only, and one
+ *              rule has to hold on every route
+ *   unit       without the whole-word switch every non-special column is a
+ *              unit of weight 1; with it a unit is a word, its weight the
+ *              number of its tokens, identified by its head column h
+ *   R(row, h)  = (sm(k + i(row, h)) & ~0xFFFFF) | h: the select draw of the
+ *              unit with its low 20 bits replaced by the column (columns are
+ *              below 2^20).  Unique within a row: the order is total and
+ *              needs no tie rule
+ *   selected   units: the longest prefix of the row's units in ascending R
+ *              whose weights sum to at most budget; column j iff its unit
+ *   a selected j has label id_j and its own second and third draws
+ *   (i(row, j) + 1, + 2) decide [MASK] / random id / kept, unchanged; an
+ *   unselected j keeps its id and has label ignore_index.
+ * Consequences: in token mode exactly budget columns are selected, a uniform
+ * sample without replacement.  In whole-word mode at most budget columns are
+ * selected; the shortfall is below the length of the first word that did not
+ * fit, and a row whose first-ranked word alone exceeds budget selects
+ * nothing.  No row ever has more than max_predictions labels, so
+ * n_rows * max_predictions is a capacity that lddl_mlm_targets never exceeds.
+ * Not combined with span masking, which has its own coverage law: a dynamic
+ * call on a ctx with both switches on is LDDL_EINVAL.  With the switch on,
+ * mode 2 of lddl_collate_bert is literally mode 0 followed by
+ * lddl_mask_tokens.  tests/budget_model.py is this in numpy.
+ * The thresholds of a call's rows live in one slot of the ctx (8 bytes per
+ * batch row) from its first kernel to its last.  So, with the switch on, the
+ * dynamic calls of a ctx must be ordered on one stream, lddl_mask_tokens
+ * included, which otherwise only queues work: a second one queued on another
+ * stream would overwrite the thresholds of the first.  A call with more rows
+ * than any before it on the ctx grows the slot (hipFree + hipMalloc: it
+ * synchronises the device and cannot be captured into a graph); run the
+ * largest batch once before capturing. */
+int lddl_set_mask_budget(lddl_ctx *ctx, int32_t max_predictions);
+
 /* Span dynamic masking (ALBERT's n-gram masking, SpanBERT's span masking, the
  * n-gram option of Megatron-style BERT pipelines): contiguous runs of whole
  * words are selected.  The reference has no counterpart.  Parameters:

@@ -70,6 +70,7 @@ SIGNATURES = {
     'lddl_set_whole_word_mask': (c_int, [c_void_p, c_int]),
     'lddl_span_params': (c_int, [c_int32, c_double, c_double, ctypes.POINTER(c_double), ctypes.POINTER(c_double)]),
     'lddl_set_span_mask': (c_int, [c_void_p, c_int32, c_double]),
+    'lddl_set_mask_budget': (c_int, [c_void_p, c_int32]),
     'lddl_collate_rows_seq_len': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32,
                                           ctypes.POINTER(c_int64), c_void_p]),
     'lddl_collate_rows': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 4 +

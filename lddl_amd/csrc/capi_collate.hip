@@ -82,6 +82,24 @@ static int span_law(const lddl_ctx* c, double mlm_probability, SpanLaw* S) {
   return lddl_span_params(c->span_max, c->span_geo, mlm_probability, &S->q, S->cdf);
 }
 
+// ------------------------------------------------------- exact-count masking --
+extern "C" int lddl_set_mask_budget(lddl_ctx* c, int32_t max_predictions) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (max_predictions < 0) return set_err(LDDL_EINVAL, "max_predictions %d is negative", max_predictions);
+  c->mask_budget = max_predictions;
+  return 0;
+}
+
+// what a dynamic call over c needs while the budget switch is on: the refusal of span masking beside it, and
+// the thresholds' slot.  *thr stays NULL while it is off.
+static int mask_budget_slot(lddl_ctx* c, int64_t n_rows, uint64_t** thr, int32_t* max_predictions) {
+  if (!c->mask_budget) return 0;
+  if (c->span_max)
+    return set_err(LDDL_EINVAL, "lddl_set_mask_budget and lddl_set_span_mask are both on: span masking has its own coverage law");
+  *max_predictions = c->mask_budget;
+  return ws_get(c, CW_MASK_THR, (size_t)n_rows, thr);
+}
+
 // the longest row m rounded up to a multiple of sequence_length_alignment (bert.py:94-97)
 static int64_t aligned_seq_len(int64_t m, int32_t seq_align) { return ((m - 1) / seq_align + 1) * seq_align; }
 
@@ -127,6 +145,10 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
     return set_err(LDDL_EINVAL, "null pointer");
   if (mode == COLLATE_STATIC && n_rows > 0 && (!d_pos || !d_pos_off || !d_lab || !d_lab_off))
     return set_err(LDDL_EINVAL, "static masking needs positions and labels");
+  // exact-count masking: mode 2 is composed of what the header equates it with, mode 0 and lddl_mask_tokens
+  const bool ranked = mode == COLLATE_DYNAMIC && c->mask_budget;
+  if (ranked && c->span_max)
+    return set_err(LDDL_EINVAL, "lddl_set_mask_budget and lddl_set_span_mask are both on: span masking has its own coverage law");
   if (n_rows == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t st = (hipStream_t)stream;
@@ -137,7 +159,7 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
   P.is_random_next = d_is_random_next;
   P.n_rows = n_rows;
   P.seq_len = (int32_t)seq_len;
-  P.mode = mode;
+  P.mode = ranked ? COLLATE_SPECIAL_MASK : mode;
   P.ignore_index = ignore_index;
   P.mlm_probability = mlm_probability;
   P.seed = seed;
@@ -166,6 +188,11 @@ extern "C" int lddl_collate_bert(lddl_ctx* c, const uint8_t* d_a, const int64_t*
         return set_err(LDDL_EFORMAT, "row %llu: masked_lm_positions and masked_lm_labels differ in length", row);
     }
   }
+  // (d_labels holds the special_tokens_mask and becomes the labels: every column's flag is read before its label
+  // is stored)
+  if (ranked)
+    return lddl_mask_tokens(c, d_input_ids, d_labels, d_labels, n_rows, seq_len, mlm_probability, ignore_index, seed, counter,
+                            stream);
   return 0;
 }
 
@@ -192,7 +219,9 @@ extern "C" int lddl_mask_tokens(lddl_ctx* c, int64_t* d_inputs, const int64_t* d
   M.counter = counter;
   M.cont = c->whole_word || c->span_max ? c->d_cont : nullptr;  // picks the wave-per-row kernel
   int rc;
+  if ((rc = mask_budget_slot(c, n_rows, &M.thr, &M.max_predictions))) return rc;
   if ((rc = span_law(c, mlm_probability, &M.span))) return rc;
+  if (M.thr) HIP_TRY(launch_mask_budget_tokens(M, c->n_cu, (hipStream_t)stream));
   HIP_TRY(launch_mask_tokens(M, c->n_cu, (hipStream_t)stream));
   return 0;
 }
@@ -369,6 +398,9 @@ static int collate_rows_common(lddl_ctx* c, int unpadded, int code, const uint16
   P.counter = counter;
   P.cont = c->whole_word || c->span_max ? c->d_cont : nullptr;  // picks the whole-word or the span instantiation of mode 2
   if (mode == COLLATE_DYNAMIC && (rc = span_law(c, mlm_probability, &P.span))) return rc;
+  if (mode == COLLATE_DYNAMIC && (rc = mask_budget_slot(c, n_rows, &P.thr, &P.max_predictions))) return rc;
+  // the thresholds of the batch rows, ahead of the fill: a row may be what the fill's row opener allows
+  if (P.thr) HIP_TRY(launch_mask_budget_rows(P, code != 0, unpadded && !F ? COLLATE_MAX_LEN : (int32_t)seq_len, c->n_cu, st));
   P.input_ids = d_input_ids;
   P.token_type_ids = d_token_type_ids;
   P.attention_mask = d_attention_mask;

@@ -115,6 +115,8 @@ enum CtxWs {
   CW_SPLIT_PIECE,  // lddl_split: sentence starts per piece (int32), then their exclusive scan (int64)
   CW_SPLIT_MAP,    // lddl_split: a bit per input byte, set where a record's first sentence starts
   CW_SPLIT_SENT,   // lddl_split: per sentence, its start and its end / length in the input (int32 each)
+  CW_MASK_THR,     // lddl_set_mask_budget on: per batch row, the rank threshold that mask_budget.hip leaves for the
+                   // fill of the same dynamic call (lddl_mask_tokens, mode 2 of the collates)
   CW_COUNT
 };
 
@@ -187,6 +189,7 @@ struct lddl_ctx {
   bool whole_word = false;       // lddl_set_whole_word_mask
   int32_t span_max = 0;          // lddl_set_span_mask: max_span (0: off) and geo_p
   double span_geo = 0.0;
+  int32_t mask_budget = 0;       // lddl_set_mask_budget: max_predictions (0: off)
   uint32_t maxb[2] = {0, 0};
   uint4* d_vt = nullptr;         // v4 bucketed vocab table
   uint32_t vt_mask = 0;

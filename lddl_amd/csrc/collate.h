@@ -10,7 +10,12 @@ enum : int32_t { COLLATE_SPECIAL_MASK = 0, COLLATE_STATIC = 1, COLLATE_DYNAMIC =
 
 // What mode 2 selects, a template constant of its kernels: tokens (`_mask_tokens`), whole words
 // (lddl_set_whole_word_mask) or geometric spans of whole words (lddl_set_span_mask).
-enum : int { SEL_TOKEN = 0, SEL_WORD = 1, SEL_SPAN = 2 };
+// With lddl_set_mask_budget on, tokens and whole words are selected by rank against the row's threshold
+// (mask_budget.hip) in place of the Bernoulli draw: SEL_TOKEN_BUDGET, SEL_WORD_BUDGET.
+enum : int { SEL_TOKEN = 0, SEL_WORD = 1, SEL_SPAN = 2, SEL_TOKEN_BUDGET = 3, SEL_WORD_BUDGET = 4 };
+// the selections whose kernels walk a row in steps of the whole wave (step_picks, collate_dev.h)
+constexpr bool sel_steps(int sel) { return sel == SEL_WORD || sel == SEL_SPAN || sel == SEL_WORD_BUDGET; }
+constexpr bool sel_budget(int sel) { return sel == SEL_TOKEN_BUDGET || sel == SEL_WORD_BUDGET; }
 
 // Span masking: lddl_span_params' outputs for the call's mlm_probability.  L = 0: off.
 struct SpanLaw {
@@ -76,6 +81,8 @@ struct MaskParams {
   uint64_t seed, counter;
   const uint32_t* cont;       // whole-word masking: as CollateParams::cont, over n_random entries; else NULL
   SpanLaw span;               // span masking: as CollateParams::span
+  uint64_t* thr;              // exact-count masking: as CollateRowsParams::thr; else NULL
+  int32_t max_predictions;
 };
 
 // lddl_collate_rows_seq_len / lddl_collate_rows: batch row r is row
@@ -103,6 +110,10 @@ struct CollateRowsParams {
   uint64_t seed, counter;
   const uint32_t* cont;      // whole-word masking: as CollateParams::cont, over n_random entries; else NULL
   SpanLaw span;              // span masking: as CollateParams::span
+  uint64_t* thr;             // exact-count masking (mode 2 with lddl_set_mask_budget on): [n_rows], written by
+                             // mask_budget_kernel, read by the fill: unit h of batch row r is selected iff its rank
+                             // key is below thr[r]; else NULL
+  int32_t max_predictions;   // lddl_set_mask_budget's value (thr set)
   int64_t* input_ids;        // [n_rows, seq_len]
   int64_t* token_type_ids;
   int64_t* attention_mask;
@@ -215,8 +226,12 @@ constexpr int COLLATE_MAX_LEN = 2048;  // per-row LDS buffer (columns)
 constexpr int kChunk = 2048;
 inline int64_t collate_chunks(int64_t n_rows) { return (n_rows + kChunk - 1) / kChunk; }
 
-// what a dynamic launch selects, from its params' cont and span
-inline int collate_sel(const uint32_t* cont, const SpanLaw& span) { return span.L > 0 ? SEL_SPAN : cont ? SEL_WORD : SEL_TOKEN; }
+// what a dynamic launch selects, from its params' cont, span and thr
+inline int collate_sel(const uint32_t* cont, const SpanLaw& span, const uint64_t* thr) {
+  if (span.L > 0) return SEL_SPAN;
+  if (thr) return cont ? SEL_WORD_BUDGET : SEL_TOKEN_BUDGET;
+  return cont ? SEL_WORD : SEL_TOKEN;
+}
 
 uint32_t collate_hash_host(const uint8_t* p, int n);
 // code: the rows are CodeBERT rows (modes 0 and 2 only)
@@ -231,6 +246,10 @@ hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_rows_from_strings_len(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_rows_from_strings(const RowsFromStringsParams& P, int n_cu, hipStream_t s);
 hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s);
+// thr[r] of every batch row, ahead of the fill on the same stream (mask_budget.hip).  bound: what the fill's row
+// opener allows a row; a row that it refuses gets thr 0 and is reported by the fill.
+hipError_t launch_mask_budget_rows(const CollateRowsParams& P, bool code, int32_t bound, int n_cu, hipStream_t s);
+hipError_t launch_mask_budget_tokens(const MaskParams& M, int n_cu, hipStream_t s);
 hipError_t launch_mlm_targets(const MlmTargetsParams& P, int n_cu, hipStream_t s);
 
 }  // namespace lddl

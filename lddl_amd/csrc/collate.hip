@@ -166,14 +166,21 @@ __global__ __launch_bounds__(256) void collate_fill_kernel(CollateParams P) {
   }
 }
 
+// BUDGET: the budget form of the select test against M.thr[r] (lddl_set_mask_budget)
+template <bool BUDGET>
 __global__ __launch_bounds__(256) void mask_tokens_kernel(MaskParams M) {
   const int64_t total = M.n_rows * (int64_t)M.seq_len;
   for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
     const int64_t r = e / M.seq_len;
     const int32_t j = (int32_t)(e - r * M.seq_len);
+    const bool special = M.special[e] != 0;  // (read before labels[e] is stored: the two may be one buffer)
     int64_t l;
-    M.inputs[e] = mask_one(M.inputs[e], M.special[e] != 0, r, j, M.seed, M.counter, M.mlm_probability, M.mask_id,
-                           M.n_random, M.ignore_index, l);
+    if constexpr (BUDGET)
+      M.inputs[e] = mask_one_ranked(M.inputs[e], special, r, j, j, M.seed, M.counter, M.thr[r], M.mask_id, M.n_random,
+                                    M.ignore_index, l);
+    else
+      M.inputs[e] = mask_one(M.inputs[e], special, r, j, M.seed, M.counter, M.mlm_probability, M.mask_id, M.n_random,
+                             M.ignore_index, l);
     M.labels[e] = l;
   }
 }
@@ -195,6 +202,8 @@ __global__ __launch_bounds__(256) void mask_tokens_word_kernel(MaskParams M) {
     const int64_t* sp = M.special + r * (int64_t)S;
     int64_t* lab = M.labels + r * (int64_t)S;
     StepCarry carry;
+    uint64_t thr = 0;  // one load per row, wave-uniform
+    if constexpr (SEL == SEL_WORD_BUDGET) thr = M.thr[r];
     uint32_t left_special = 1;  // of the column in front of the step: none in front of column 0
     for (int32_t base = 0; base < S; base += 64) {
       const int32_t j = base + lane;
@@ -210,7 +219,7 @@ __global__ __launch_bounds__(256) void mask_tokens_word_kernel(MaskParams M) {
       if (in_row) {
         int64_t l;
         in[j] = mask_one_picked<SEL>(id, special != 0, r, j, pick[0], M.seed, M.counter, M.mlm_probability, M.mask_id,
-                                     M.n_random, M.ignore_index, l);
+                                     M.n_random, M.ignore_index, l, thr);
         lab[j] = l;
       }
     }
@@ -226,7 +235,7 @@ hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s) {
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.n_rows, n_cu)), block(256);
-  const int sel = P.mode == COLLATE_DYNAMIC ? collate_sel(P.cont, P.span) : SEL_TOKEN;
+  const int sel = P.mode == COLLATE_DYNAMIC ? collate_sel(P.cont, P.span, nullptr) : SEL_TOKEN;
   if (sel == SEL_SPAN) hipLaunchKernelGGL(collate_fill_kernel<SEL_SPAN>, grid, block, 0, s, P);
   else if (sel == SEL_WORD) hipLaunchKernelGGL(collate_fill_kernel<SEL_WORD>, grid, block, 0, s, P);
   else hipLaunchKernelGGL(collate_fill_kernel<SEL_TOKEN>, grid, block, 0, s, P);
@@ -239,12 +248,14 @@ hipError_t launch_mask_tokens(const MaskParams& M, int n_cu, hipStream_t s) {
   if (M.cont) {
     const dim3 grid(grid_rows(M.n_rows, n_cu)), block(256);
     if (M.span.L > 0) hipLaunchKernelGGL(mask_tokens_word_kernel<SEL_SPAN>, grid, block, 0, s, M);
+    else if (M.thr) hipLaunchKernelGGL(mask_tokens_word_kernel<SEL_WORD_BUDGET>, grid, block, 0, s, M);
     else hipLaunchKernelGGL(mask_tokens_word_kernel<SEL_WORD>, grid, block, 0, s, M);
     return hipGetLastError();
   }
   int64_t g = (total + 255) / 256;
   if (g > (int64_t)n_cu * 16) g = (int64_t)n_cu * 16;
-  hipLaunchKernelGGL(mask_tokens_kernel, dim3((int)g), dim3(256), 0, s, M);
+  if (M.thr) hipLaunchKernelGGL(mask_tokens_kernel<true>, dim3((int)g), dim3(256), 0, s, M);
+  else hipLaunchKernelGGL(mask_tokens_kernel<false>, dim3((int)g), dim3(256), 0, s, M);
   return hipGetLastError();
 }
 

@@ -61,6 +61,23 @@ __device__ __forceinline__ int64_t mask_one_at(int64_t id, bool special, int64_t
   return mask_selected(id, row, col, k, mask_id, n_random, label);
 }
 
+// Exact-count masking (lddl_set_mask_budget): the rank key of the unit headed at (row, h), the select draw with
+// its low 20 bits replaced by the column; unique within a row
+__device__ __forceinline__ uint64_t budget_key(uint64_t k, int64_t row, int32_t h) {
+  return (splitmix64(k + mask_idx(row, h)) & ~0xFFFFFull) | (uint64_t)(uint32_t)h;
+}
+
+// mask_one_at with the budget form of the select test: the unit at column sel is selected iff its rank key is below
+// the row's threshold
+__device__ __forceinline__ int64_t mask_one_ranked(int64_t id, bool special, int64_t row, int32_t col, int32_t sel,
+                                                   uint64_t seed, uint64_t counter, uint64_t thr, int32_t mask_id,
+                                                   int32_t n_random, int64_t ignore, int64_t& label) {
+  const uint64_t k = mask_key(seed, counter);
+  label = ignore;
+  if (special || !(budget_key(k, row, sel) < thr)) return id;
+  return mask_selected(id, row, col, k, mask_id, n_random, label);
+}
+
 // _mask_tokens for one column: every column selects for itself
 __device__ __forceinline__ int64_t mask_one(int64_t id, bool special, int64_t row, int32_t col, uint64_t seed,
                                             uint64_t counter, double p, int32_t mask_id, int32_t n_random,
@@ -181,8 +198,8 @@ template <int SEL, int W>
 __device__ __forceinline__ void step_picks(const SpanLaw& S, uint64_t seed, uint64_t counter, int64_t row, int32_t base,
                                            const bool (&st)[W], const bool (&sp)[W], StepCarry& carry,
                                            int32_t (&pick)[W]) {
-  static_assert(SEL == SEL_WORD || SEL == SEL_SPAN, "tokens select for themselves");
-  if constexpr (SEL == SEL_WORD) {
+  static_assert(sel_steps(SEL), "tokens select for themselves");
+  if constexpr (SEL != SEL_SPAN) {
     word_heads<W>(base, st, carry.head, pick);
   } else {
     bool sel[W];
@@ -192,13 +209,15 @@ __device__ __forceinline__ void step_picks(const SpanLaw& S, uint64_t seed, uint
   }
 }
 
-// _mask_tokens for one column with its pick of step_picks
+// _mask_tokens for one column with its pick of step_picks (thr: the row's threshold, SEL_WORD_BUDGET)
 template <int SEL>
 __device__ __forceinline__ int64_t mask_one_picked(int64_t id, bool special, int64_t row, int32_t col, int32_t pick,
                                                    uint64_t seed, uint64_t counter, double p, int32_t mask_id,
-                                                   int32_t n_random, int64_t ignore, int64_t& label) {
+                                                   int32_t n_random, int64_t ignore, int64_t& label, uint64_t thr = 0) {
   if constexpr (SEL == SEL_WORD) {
     return mask_one_at(id, special, row, col, pick, seed, counter, p, mask_id, n_random, ignore, label);
+  } else if constexpr (SEL == SEL_WORD_BUDGET) {
+    return mask_one_ranked(id, special, row, col, pick, seed, counter, thr, mask_id, n_random, ignore, label);
   } else {
     label = ignore;
     if (!pick) return id;

@@ -198,10 +198,16 @@ hipError_t launch_collate_fixed(const CollateFixedParams& P0, bool code, int32_t
   const int g = grid_rows(n > P.tok_cap / 256 ? n : P.tok_cap / 256, n_cu);
   P.rows_per_block = ((n + g - 1) / g + 3) & ~(int64_t)3;
   const dim3 grid(g), block(256);
-  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.R.cont, P.R.span) : SEL_TOKEN;
+  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.R.cont, P.R.span, P.R.thr) : SEL_TOKEN;
   if (sel == SEL_SPAN) {
     if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, SEL_SPAN>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, SEL_SPAN>), grid, block, 0, s, P);
+  } else if (sel == SEL_WORD_BUDGET) {
+    if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, SEL_WORD_BUDGET>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, SEL_WORD_BUDGET>), grid, block, 0, s, P);
+  } else if (sel == SEL_TOKEN_BUDGET) {
+    if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, SEL_TOKEN_BUDGET>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, SEL_TOKEN_BUDGET>), grid, block, 0, s, P);
   } else if (sel == SEL_WORD) {
     if (code) hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, true, SEL_WORD>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((collate_fixed_kernel<COLLATE_DYNAMIC, false, SEL_WORD>), grid, block, 0, s, P);

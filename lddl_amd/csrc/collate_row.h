@@ -124,9 +124,10 @@ struct RowColumn {
 // staged static masks (input_ids[pos] = mlm_token, labels[pos] = mlm_label,
 // ignore_index elsewhere); 2 mask_one with row = r.  pad: j is a pad column of
 // a padded batch (id 0, special); without padding j < n and pad is false.
-template <int MODE>
+// SEL_TOKEN_BUDGET (mode 2): the budget form of the select test against thr, the row's threshold.
+template <int MODE, int SEL = SEL_TOKEN>
 __device__ __forceinline__ RowColumn row_column(const CollateRowsParams& P, const OpenRow& R, const uint32_t* mlm,
-                                                int64_t r, int32_t j, bool pad) {
+                                                int64_t r, int32_t j, bool pad, uint64_t thr = 0) {
   RowColumn o;
   const bool special = pad || R.L.special(j);
   int64_t id = 0;
@@ -137,6 +138,8 @@ __device__ __forceinline__ RowColumn row_column(const CollateRowsParams& P, cons
     const uint32_t m = mlm[j];
     o.lab = m == kNoMask ? P.ignore_index : (int64_t)(m & 0xFFFFu);
     if (m != kNoMask) id = (int64_t)(m >> 16);
+  } else if constexpr (SEL == SEL_TOKEN_BUDGET) {
+    id = mask_one_ranked(id, special, r, j, j, P.seed, P.counter, thr, P.mask_id, P.n_random, P.ignore_index, o.lab);
   } else {
     id = mask_one(id, special, r, j, P.seed, P.counter, P.mlm_probability, P.mask_id, P.n_random, P.ignore_index,
                   o.lab);
@@ -182,13 +185,13 @@ __device__ __forceinline__ void row_picks(const CollateRowsParams& P, int64_t r,
 }
 
 // row_column<COLLATE_DYNAMIC> of a column with its pick: the column where its word starts (SEL_WORD), or whether a
-// span covers it (SEL_SPAN)
+// span covers it (SEL_SPAN); thr: the row's threshold (SEL_WORD_BUDGET)
 template <int SEL>
 __device__ __forceinline__ RowColumn row_column_picked(const CollateRowsParams& P, const OpenRow& R, int64_t r, int32_t j,
-                                                       const WordColumn& c, int32_t pick) {
+                                                       const WordColumn& c, int32_t pick, uint64_t thr = 0) {
   RowColumn o;
   o.id = mask_one_picked<SEL>(c.id, c.special, r, j, pick, P.seed, P.counter, P.mlm_probability, P.mask_id, P.n_random,
-                              P.ignore_index, o.lab);
+                              P.ignore_index, o.lab, thr);
   o.tt = R.L.token_type(j);
   return o;
 }
@@ -202,7 +205,7 @@ __device__ __forceinline__ RowColumn row_column_picked(const CollateRowsParams& 
 // token pairs that cover the row: a lane computes both tokens of a pair and
 // stores 16 B per output; the first pair of an odd start and the last pair of an
 // odd end hold one token of this row and store 8 B.  Without it, lane = token.
-// SEL (word or span: mode 2 only): what is selected, as in collate_rows_kernel.
+// SEL (other than SEL_TOKEN: mode 2 only): what is selected, as in collate_rows_kernel.
 // A step of the wide path is the 128 tokens of 64 aligned pairs, the first of
 // them -1 (not a token of the row) when the row starts at an odd offset.
 template <int MODE, int SEL>
@@ -214,7 +217,9 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
   int64_t* o_tt = R.token_type_ids + c0;
   int64_t* o_pos = position_ids + c0;
   int64_t* o_lab = R.labels + c0;
-  if constexpr (SEL != SEL_TOKEN) {
+  uint64_t thr = 0;  // one load per row, wave-uniform
+  if constexpr (sel_budget(SEL)) thr = R.thr[r];
+  if constexpr (sel_steps(SEL)) {
     StepCarry carry;
     if (wide) {
       const int32_t head = (int32_t)(c0 & 1);
@@ -226,8 +231,8 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
         const WordColumn w[2] = {word_column(R, S, j0, v0, false), word_column(R, S, j1, v1, false)};
         int32_t pick[2];
         row_picks<SEL, 2>(R, r, 2 * qb - head, w, carry, pick);
-        const RowColumn t0 = row_column_picked<SEL>(R, S, r, j0, w[0], pick[0]);
-        const RowColumn t1 = row_column_picked<SEL>(R, S, r, j1, w[1], pick[1]);
+        const RowColumn t0 = row_column_picked<SEL>(R, S, r, j0, w[0], pick[0], thr);
+        const RowColumn t1 = row_column_picked<SEL>(R, S, r, j1, w[1], pick[1], thr);
         if (v0 && v1) {
           *reinterpret_cast<longlong2*>(o_ids + j0) = make_longlong2(t0.id, t1.id);
           *reinterpret_cast<longlong2*>(o_tt + j0) = make_longlong2(t0.tt, t1.tt);
@@ -249,7 +254,7 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
         int32_t pick[1];
         row_picks<SEL, 1>(R, r, base, w, carry, pick);
         if (j < n) {
-          const RowColumn t = row_column_picked<SEL>(R, S, r, j, w[0], pick[0]);
+          const RowColumn t = row_column_picked<SEL>(R, S, r, j, w[0], pick[0], thr);
           o_ids[j] = t.id;
           o_tt[j] = t.tt;
           o_pos[j] = j;
@@ -267,8 +272,8 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
       const int32_t j0 = 2 * q - head, j1 = j0 + 1;
       const bool v0 = j0 >= 0, v1 = j1 < n;
       const int32_t k0 = v0 ? j0 : 0, k1 = v1 ? j1 : n - 1;
-      const RowColumn t0 = row_column<MODE>(R, S, mlm, r, k0, false);
-      const RowColumn t1 = row_column<MODE>(R, S, mlm, r, k1, false);
+      const RowColumn t0 = row_column<MODE, SEL>(R, S, mlm, r, k0, false, thr);
+      const RowColumn t1 = row_column<MODE, SEL>(R, S, mlm, r, k1, false, thr);
       if (v0 && v1) {
         *reinterpret_cast<longlong2*>(o_ids + j0) = make_longlong2(t0.id, t1.id);
         *reinterpret_cast<longlong2*>(o_tt + j0) = make_longlong2(t0.tt, t1.tt);
@@ -285,7 +290,7 @@ __device__ __forceinline__ void stream_row(const CollateRowsParams& R, const Ope
     }
   } else {
     for (int32_t j = lane; j < n; j += 64) {
-      const RowColumn t = row_column<MODE>(R, S, mlm, r, j, false);
+      const RowColumn t = row_column<MODE, SEL>(R, S, mlm, r, j, false, thr);
       o_ids[j] = t.id;
       o_tt[j] = t.tt;
       o_pos[j] = j;

@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void collate_rows_len_kernel(CollateRowsParams
 // columns from ballots of the word starts and carries the last one to the next
 // step (word_heads), so the loops run for the whole wave and predicate the
 // stores.  SEL_SPAN: span masking, the same loops with span_select's scan in
-// place of word_heads.
+// place of word_heads.  SEL_TOKEN_BUDGET / SEL_WORD_BUDGET: tokens / whole words by rank against P.thr[r].
 template <int MODE, bool CODE, int SEL = SEL_TOKEN>
 __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) {
   static_assert(!(CODE && MODE == COLLATE_STATIC), "CodeBERT rows have no static masks");
@@ -100,7 +100,9 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
     int64_t* o_tt = P.token_type_ids + r * (int64_t)L;
     int64_t* o_am = P.attention_mask + r * (int64_t)L;
     int64_t* o_lab = P.labels + r * (int64_t)L;
-    if constexpr (SEL != SEL_TOKEN) {
+    uint64_t thr = 0;  // one load per row, wave-uniform
+    if constexpr (sel_budget(SEL)) thr = P.thr[r];
+    if constexpr (sel_steps(SEL)) {
       StepCarry carry;
       if (wide) {
         for (int32_t base = 0; base < L; base += 128) {
@@ -109,8 +111,8 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
           int32_t pick[2];
           row_picks<SEL, 2>(P, r, base, wc, carry, pick);
           if (j < L) {
-            const RowColumn c0 = row_column_picked<SEL>(P, R, r, j, wc[0], pick[0]);
-            const RowColumn c1 = row_column_picked<SEL>(P, R, r, j + 1, wc[1], pick[1]);
+            const RowColumn c0 = row_column_picked<SEL>(P, R, r, j, wc[0], pick[0], thr);
+            const RowColumn c1 = row_column_picked<SEL>(P, R, r, j + 1, wc[1], pick[1], thr);
             *reinterpret_cast<longlong2*>(o_ids + j) = make_longlong2(c0.id, c1.id);
             *reinterpret_cast<longlong2*>(o_tt + j) = make_longlong2(c0.tt, c1.tt);
             *reinterpret_cast<longlong2*>(o_am + j) = make_longlong2(j < n ? 1 : 0, j + 1 < n ? 1 : 0);
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
           int32_t pick[1];
           row_picks<SEL, 1>(P, r, base, wc, carry, pick);
           if (j < L) {
-            const RowColumn c = row_column_picked<SEL>(P, R, r, j, wc[0], pick[0]);
+            const RowColumn c = row_column_picked<SEL>(P, R, r, j, wc[0], pick[0], thr);
             o_ids[j] = c.id;
             o_tt[j] = c.tt;
             o_am[j] = j < n ? 1 : 0;
@@ -135,8 +137,8 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
     } else if (wide) {
       // two columns and one 16-B store per lane and output
       for (int32_t j = 2 * lane; j < L; j += 128) {
-        const RowColumn c0 = row_column<MODE>(P, R, mlm, r, j, j >= n);
-        const RowColumn c1 = row_column<MODE>(P, R, mlm, r, j + 1, j + 1 >= n);
+        const RowColumn c0 = row_column<MODE, SEL>(P, R, mlm, r, j, j >= n, thr);
+        const RowColumn c1 = row_column<MODE, SEL>(P, R, mlm, r, j + 1, j + 1 >= n, thr);
         *reinterpret_cast<longlong2*>(o_ids + j) = make_longlong2(c0.id, c1.id);
         *reinterpret_cast<longlong2*>(o_tt + j) = make_longlong2(c0.tt, c1.tt);
         *reinterpret_cast<longlong2*>(o_am + j) = make_longlong2(j < n ? 1 : 0, j + 1 < n ? 1 : 0);
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(256) void collate_rows_kernel(CollateRowsParams P) 
       }
     } else {
       for (int32_t j = lane; j < L; j += 64) {
-        const RowColumn c = row_column<MODE>(P, R, mlm, r, j, j >= n);
+        const RowColumn c = row_column<MODE, SEL>(P, R, mlm, r, j, j >= n, thr);
         o_ids[j] = c.id;
         o_tt[j] = c.tt;
         o_am[j] = j < n ? 1 : 0;
@@ -167,10 +169,16 @@ hipError_t launch_collate_rows_len(const CollateRowsParams& P, bool code, int n_
 hipError_t launch_collate_rows(const CollateRowsParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.n_rows, n_cu)), block(256);
-  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.cont, P.span) : SEL_TOKEN;
+  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.cont, P.span, P.thr) : SEL_TOKEN;
   if (sel == SEL_SPAN) {
     if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, SEL_SPAN>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, SEL_SPAN>), grid, block, 0, s, P);
+  } else if (sel == SEL_WORD_BUDGET) {
+    if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, SEL_WORD_BUDGET>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, SEL_WORD_BUDGET>), grid, block, 0, s, P);
+  } else if (sel == SEL_TOKEN_BUDGET) {
+    if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, SEL_TOKEN_BUDGET>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, SEL_TOKEN_BUDGET>), grid, block, 0, s, P);
   } else if (sel == SEL_WORD) {
     if (code) hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, true, SEL_WORD>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((collate_rows_kernel<COLLATE_DYNAMIC, false, SEL_WORD>), grid, block, 0, s, P);

@@ -154,10 +154,16 @@ hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, 
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s) {
   if (P.R.n_rows <= 0) return hipSuccess;
   const dim3 grid(grid_rows(P.R.n_rows, n_cu)), block(256);
-  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.R.cont, P.R.span) : SEL_TOKEN;
+  const int sel = mode == COLLATE_DYNAMIC ? collate_sel(P.R.cont, P.R.span, P.R.thr) : SEL_TOKEN;
   if (sel == SEL_SPAN) {
     if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, SEL_SPAN>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, SEL_SPAN>), grid, block, 0, s, P);
+  } else if (sel == SEL_WORD_BUDGET) {
+    if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, SEL_WORD_BUDGET>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, SEL_WORD_BUDGET>), grid, block, 0, s, P);
+  } else if (sel == SEL_TOKEN_BUDGET) {
+    if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, SEL_TOKEN_BUDGET>), grid, block, 0, s, P);
+    else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, SEL_TOKEN_BUDGET>), grid, block, 0, s, P);
   } else if (sel == SEL_WORD) {
     if (code) hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, true, SEL_WORD>), grid, block, 0, s, P);
     else hipLaunchKernelGGL((collate_unpadded_kernel<COLLATE_DYNAMIC, false, SEL_WORD>), grid, block, 0, s, P);

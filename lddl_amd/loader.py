@@ -311,7 +311,7 @@ class _RowCollate:
 
   def __init__(self, vocab_file=None, device=None, sequence_length_alignment=8, ignore_index=-1,
                mlm_probability=0.15, base_seed=12345, tokenizer=None, whole_word_mask=False, compact_mlm=False,
-               span_mask=None):
+               span_mask=None, max_predictions=None):
     """whole_word_mask: dynamic masking (mode 2 and ``mask_tokens``) selects
     words, not tokens: a piece and the ``##`` pieces after it are masked
     together (lddl_set_whole_word_mask; include/lddl_amd.h defines it).  The
@@ -329,11 +329,25 @@ class _RowCollate:
     the same rule for a shared ctx; not to be combined with
     ``whole_word_mask=True`` (``max_span=1`` is whole-word masking).
 
+    max_predictions: dynamic masking selects an exact, bounded number of
+    tokens per row in place of independent draws: with c candidates (the
+    non-special columns) ``min(max_predictions, c, max(1, round(c *
+    mlm_probability)))`` of them, a uniform sample; with ``whole_word_mask``
+    whole words that hold at most that many tokens (lddl_set_mask_budget;
+    include/lddl_amd.h defines it).  The rule of the reference's static
+    masking with the ``max_predictions_per_seq`` cap of the BERT recipes.  No
+    row ever has more than ``max_predictions`` labels.  None or 0: off.  Set on
+    the ctx as ``whole_word_mask`` is, with the same rule for a shared ctx;
+    not to be combined with ``span_mask``.
+
     compact_mlm: every batch with ``labels`` (modes 1 and 2) also carries the
     compact targets of ``mlm_targets`` over those labels, as
     ``masked_lm_positions``, ``masked_lm_labels`` and ``masked_lm_offsets``:
     True for exact-size tensors, an int K for tensors of exactly K entries
-    (a batch with more masked tokens raises).  ``ignore_index`` must then be
+    (a batch with more masked tokens raises).  With ``max_predictions=P``,
+    True gives tensors of exactly ``rows * P`` entries in mode 2 (rows: the
+    sequence slots of the batch, max_seqs for ``collate_rows_fixed``), and
+    ``compact_mlm=rows * P`` cannot raise.  ``ignore_index`` must then be
     negative.  Everything else in the batch, and the batch counter, are as
     without it."""
     assert isinstance(sequence_length_alignment, int) and sequence_length_alignment >= 1
@@ -346,6 +360,13 @@ class _RowCollate:
     self.span_mask = _span_args(span_mask)
     if self.span_mask and whole_word_mask:
       raise ValueError('span_mask and whole_word_mask=True: one selection at a time (spans are made of whole words)')
+    if max_predictions is None or max_predictions is False:
+      max_predictions = 0
+    if isinstance(max_predictions, bool) or not isinstance(max_predictions, int) or not 0 <= max_predictions < 1 << 31:
+      raise ValueError('max_predictions %r: None or an int >= 0' % (max_predictions,))
+    if max_predictions and self.span_mask:
+      raise ValueError('max_predictions and span_mask: span masking has its own coverage law')
+    self.max_predictions = max_predictions
     self.compact_mlm = compact_mlm
     self.tok = tokenizer if tokenizer is not None else Tokenizer(vocab_file or self.VOCAB, device)
     self.whole_word_mask = bool(whole_word_mask)
@@ -354,6 +375,8 @@ class _RowCollate:
       _lib.check(L.lddl_set_whole_word_mask(self.tok.handle, 1 if self.whole_word_mask else 0))
     if self.span_mask or hasattr(L, 'lddl_set_span_mask'):
       _lib.check(L.lddl_set_span_mask(self.tok.handle, *(self.span_mask or (0, 0.0))))
+    if self.max_predictions or hasattr(L, 'lddl_set_mask_budget'):
+      _lib.check(L.lddl_set_mask_budget(self.tok.handle, self.max_predictions))
     self.device = self.tok.device
     self.sequence_length_alignment = sequence_length_alignment
     self.ignore_index = int(ignore_index)
@@ -467,7 +490,7 @@ class _RowCollate:
       batch['num_tokens'], batch['num_rows'], batch['num_seqs'] = (int(x.value) for x in counts)
     elif unpadded:
       batch['cu_seqlens'], batch['max_seqlen'] = cu, int(longest.value)
-    return self._with_targets(batch, cu if unpadded else None)
+    return self._with_targets(batch, cu if unpadded else None, mode == MODE_DYNAMIC)
 
   def _load_table(self, cols, per_row, static, bins, part, nbins):
     """load_rows of both classes over staged columns: the length call, the
@@ -584,10 +607,15 @@ class _RowCollate:
     m = int(count.value) if capacity is None else cap
     return pos[:m], lab[:m], off
 
-  def _with_targets(self, batch, cu_seqlens=None):
-    """the batch of a collate, with the compact targets of its labels when compact_mlm asks for them"""
+  def _with_targets(self, batch, cu_seqlens=None, dynamic=False):
+    """the batch of a collate, with the compact targets of its labels when
+    compact_mlm asks for them; dynamic: the labels are mode 2's, so no row
+    holds more than max_predictions of them (when that is set)"""
     if self.compact_mlm is not False and 'labels' in batch:
       capacity = None if self.compact_mlm is True else self.compact_mlm
+      if capacity is None and dynamic and self.max_predictions:
+        rows = batch['labels'].shape[0] if cu_seqlens is None else cu_seqlens.numel() - 1
+        capacity = rows * self.max_predictions
       pos, lab, off = self.mlm_targets(batch['labels'], cu_seqlens, capacity)
       batch['masked_lm_positions'], batch['masked_lm_labels'], batch['masked_lm_offsets'] = pos, lab, off
     return batch
@@ -635,7 +663,8 @@ class BertCollate(_RowCollate):
     del dev, host  # the stream was synchronised by the call
     return self._with_targets({'input_ids': out[0], 'token_type_ids': out[1], 'attention_mask': out[2],
                                'next_sentence_labels': nsl,
-                               'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]})
+                               'special_tokens_mask' if mode == MODE_SPECIAL_MASK else 'labels': out[3]},
+                              dynamic=mode == MODE_DYNAMIC)
 
   # ---- entry points ---------------------------------------------------------
   def __call__(self, batch):

@@ -362,6 +362,14 @@ def _cases():
   c += [Case('collate_rows[bert-padded-wwm]', 'collate', (('ids', 'ids'),), dict(cls='bert', route='padded', mode=2, wwm=True)),
         Case('collate_rows[bert-unpadded-span]', 'collate', (('ids', 'ids'),),
              dict(cls='bert', route='unpadded', mode=2, span=True))]
+  # exact-count masking (lddl_set_mask_budget): a threshold kernel ahead of the fill, through one workspace slot.  In
+  # whole-word mode it reads the staged ids for the word starts, so on another stream it ranks B's words: the cases'
+  # test also holds A and B to different selections
+  c += [Case('collate_rows[bert-padded-budget-wwm]', 'collate', (('ids', 'ids'),),
+             dict(cls='bert', route='padded', mode=2, wwm=True, budget=20)),
+        Case('collate_rows[bert-unpadded-budget-wwm]', 'collate', (('ids', 'ids'),),
+             dict(cls='bert', route='unpadded', mode=2, wwm=True, budget=20)),
+        Case('collate_rows[code-fixed-budget]', 'collate', (('ids', 'ids'),), dict(cls='code', route='fixed', mode=2, budget=20))]
   # string routes stage their own columns (rotated letters: same offsets, same token counts)
   c += [Case('load_rows[bert]', 'strings', (('samples', 'text'),), dict(what='load', static=False), host=True),
         Case('load_rows[bert-static]', 'strings', (('samples', 'text'),), dict(what='load', static=True), host=True),
@@ -372,6 +380,7 @@ def _cases():
         Case('collate_arrow', 'strings', (('samples', 'text'),), dict(what='arrow'), host=True)]
   # ids pass through as values; labels are compared with ignore_index and copied, capacity = every token
   c += [Case('mask_tokens', 'mask_tokens', (('inputs', 'ids'),)),
+        Case('mask_tokens[budget-wwm]', 'mask_tokens', (('inputs', 'ids'),), dict(wwm=True, budget=20)),
         Case('mlm_targets[padded]', 'mlm_targets', (('labels', 'values'),), dict(cu=False)),
         Case('mlm_targets[cu_seqlens]', 'mlm_targets', (('labels', 'values'),), dict(cu=True))]
   return c

@@ -48,3 +48,16 @@ def test_offsets_are_never_staged():
   a = np.arange(10, dtype=np.int64)
   with pytest.raises(AssertionError):
     SC.check_pair('tok_off', 'values', a, a + 1, {})
+
+
+def test_bumped_ids_move_word_starts():
+  """the exact-count whole-word cases rely on B's ids giving other word starts than A's: in the BERT vocabulary a
+  '##' piece and a whole word are neighbours at many ids that bump_ids moves"""
+  from lddl_amd import _lib
+  import wwm_model as wm
+  with open(_lib.VOCAB_BERT, 'rb') as f:
+    cont = wm.cont_table(f.read().split(b'\n'))
+  assert any(c.id.endswith('budget-wwm]') for c in SC.CASES)
+  a = np.arange(1000, SC.VOCAB_SIZES['bert'] - 1)
+  b = SC.bump_ids(a, SC.VOCAB_SIZES['bert'], (0, 100, 101, 102, 103))
+  assert np.array_equal(b, a + 1) and (cont[a] != cont[b]).sum() > 100

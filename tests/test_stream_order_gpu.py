@@ -339,7 +339,7 @@ def _collate(e, p, **kw):
   cls = {'bert': loader.BertCollate, 'code': loader.CodeCollate, 'mlm': loader.MlmCollate}[p.get('cls', 'bert')]
   pk = e.cpk if p.get('cls') == 'code' else e.pk
   return cls(tokenizer=pk.tok, base_seed=SEED, whole_word_mask=bool(p.get('wwm')),
-             span_mask=(3, 0.3) if p.get('span') else None, **kw)
+             span_mask=(3, 0.3) if p.get('span') else None, max_predictions=p.get('budget'), **kw)
 
 
 def k_collate(e, case):
@@ -439,8 +439,12 @@ def k_mask_tokens(e, case):
   a = inputs.cpu().numpy().copy()
 
   def call(s, which):
-    with _on(s):
-      ids, labels = col.mask_tokens(inputs, sp, counter=5)  # (in place: the harness refills `inputs` before every call)
+    col = _collate(e, case.p)  # (sets the ctx's masking switches)
+    try:
+      with _on(s):
+        ids, labels = col.mask_tokens(inputs, sp, counter=5)  # (in place: the harness refills `inputs` before every call)
+    finally:
+      _collate(e, {})  # (switches off again)
     return {'input_ids': ids.clone() if s is None else ids, 'labels': labels}
   return _live(e, case, {'inputs': (inputs, a)}), call
 
@@ -473,6 +477,10 @@ def test_side_stream(env, case, tmp_path):
   staged, call = KINDS[case.kind](env, case, tmp_path) if case.kind == 'write' else KINDS[case.kind](env, case)
   assert case.host == (not staged)
   base_a, base_b, got = SC.run_delayed(case, staged, call, env.delay, _meta(env, case))
+  if case.p.get('budget') and case.p.get('wwm'):
+    # the threshold kernel's own input differs: B's ids move word starts, so the budget falls on other columns
+    sel = [np.frombuffer(b['labels'][2], b['labels'][0]) != -1 for b in (base_a, base_b)]
+    assert sel[0].any() and not np.array_equal(*sel), 'A and B select the same columns: a misrouted threshold kernel would pass'
   SC.assert_same(case, base_a, base_b, got)
 
 

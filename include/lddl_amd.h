@@ -765,6 +765,118 @@ int lddl_collate_code_rows_fixed(lddl_ctx *ctx, const uint16_t *d_ids, const int
                                  int64_t *d_position_ids, int64_t *d_labels, int32_t *d_status, int64_t *out_total,
                                  int64_t *out_n_rows, int64_t *out_n_seqs, void *stream);
 
+/* ---- text-infilling collate --------------------------------------------------
+ * Denoising batches for a sequence-to-sequence model (BART's text infilling,
+ * MASS- and PEGASUS-style recipes) over a WordPiece vocabulary: every selected
+ * span of a row collapses to a single [MASK], so the encoder input is shorter
+ * than the row, and the decoder is teacher-forced on the row itself.  The
+ * reference stops at the BART text column; it has no such loader.  The rows are
+ * taken as lddl_collate_code_rows takes them (s = flags bit 1): MLM-only rows
+ * and CodeBERT rows, [CLS] doc [SEP] code [SEP] included; BERT pair rows are
+ * out of scope.  The law is passed per call: the ctx's whole-word, span and
+ * budget switches are neither read nor changed.
+ *
+ * Length law: Poisson(lambda) conditioned on 1 .. L, L = max_span in [1, 16]:
+ *   P(len = l) = (lambda^l / l!) / sum_{m = 1 .. L} lambda^m / m!
+ *   cdf[t] = P(len <= t) for t = 1 .. L, cdf[L] = 1 exactly
+ * Zero-length spans (fairseq's bare [MASK] insertions, about 5 % of the draws
+ * at lambda = 3) are deliberately left out: without them a corrupted row is
+ * never longer than its source, so the padded batch keeps the source's
+ * seq_len (lddl_collate_code_rows_seq_len).
+ * Start probability q: the root of span masking's coverage equation
+ * 1 - prod_{t = 0 .. L-1} (1 - q S_t) = mask_ratio, S_0 = 1, S_t = 1 - cdf[t],
+ * by the same 64 bisection steps on [0, mask_ratio] (one solver serves both
+ * laws): 0 for mask_ratio 0, 1 for mask_ratio 1, mask_ratio itself for L = 1.
+ *
+ * lddl_infill_params: q and cdf for (max_span, poisson_lambda, mask_ratio), on
+ * the host (no ctx, no GPU), in lddl_span_params' layout: out_cdf[t - 1] =
+ * cdf[t] for t = 1 .. L, 1.0 behind them.  The one place they are computed:
+ * every lddl_collate_infill_rows* call takes them from here.  LDDL_EINVAL:
+ * max_span outside [1, 16], poisson_lambda not finite or <= 0, mask_ratio
+ * outside [0, 1], a NULL output. */
+int lddl_infill_params(int32_t max_span, double poisson_lambda, double mask_ratio, double *out_q, double out_cdf[16]);
+
+/* For batch row r (row g = d_rows[r], or row0 + r, as in lddl_collate_rows)
+ * with n columns: id_j, special(j), start(j), k, ks and i(row, col) are exactly
+ * as in the span-masking definition above, with row = r, and selected(j) is
+ * span masking's `selected` under (q, cdf, L) of lddl_infill_params.  Spans are
+ * runs of whole words inside one segment, so [CLS] and each [SEP] are never
+ * selected and no span crosses them.  Then
+ *   emit(j) = 1 with token id_j    iff !selected(j)
+ *   emit(j) = 1 with token [MASK]  iff selected(j) and (j == 0 or !selected(j - 1))
+ *   emit(j) = 0                    otherwise: adjacent or overlapping spans
+ *                                  collapse into one [MASK]
+ *   e_r = sum of emit, pos(j) = the exclusive prefix sum of emit
+ *   encoder  input_ids[r, pos(j)] = the emitted token; attention_mask 1 on
+ *            [0, e_r); both 0 on [e_r, seq_len)
+ *   decoder  decoder_input_ids[r, j] = id_j for j in [0, n - 1), then 0
+ *   labels   labels[r, j] = id_{j + 1} for j in [0, n - 1), then ignore_index
+ *   enc_len[r] = e_r (int32, on the device)
+ * There is no random-token replacement and no sentence permutation (rows keep
+ * no sentence boundaries).  mask_ratio 0: the encoder input is the row itself;
+ * mask_ratio 1: every segment becomes one [MASK].  tests/infill_model.py is
+ * this in numpy.  hip_stream: the hipStream_t that the three calls queue
+ * their work on, as `stream` of the calls above.
+ *
+ * lddl_collate_infill_rows: the padded batch, four int64 [n_rows, seq_len]
+ * outputs and d_enc_len; seq_len from lddl_collate_code_rows_seq_len (or any
+ * value that holds the longest row).  Synchronises the stream.  Errors, first
+ * one wins, none faults, a refused row is left unwritten: LDDL_EINDEX (a row
+ * index outside [0, n_total), checked before any load through it),
+ * LDDL_ECAPACITY (a row longer than seq_len, seq_len not in [2, 2048]),
+ * LDDL_EINVAL (n_rows <= 0, null pointers, a refused law, a row with s = 0 and
+ * a > 0). */
+int lddl_collate_infill_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                             const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                             const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total, int64_t seq_len,
+                             int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio,
+                             uint64_t seed, uint64_t counter, int64_t *d_input_ids, int64_t *d_attention_mask,
+                             int64_t *d_decoder_input_ids, int64_t *d_labels, int32_t *d_enc_len, void *hip_stream);
+
+/* The padding-free batch: two token streams, the encoder's with row r at
+ * [cu_seqlens[r], cu_seqlens[r] + e_r) and the decoder's with row r at
+ * [decoder_cu_seqlens[r], decoder_cu_seqlens[r] + n_r - 1).  Bit for bit
+ * lddl_collate_infill_rows at the same law, seed and counter with the columns
+ * >= e_r (encoder) and >= n_r - 1 (decoder) of every row dropped.
+ *
+ * lddl_collate_infill_rows_cu_seqlens: both offset arrays, int32 [n_rows + 1]
+ * on the device (the selection is computed to count e_r, so the table and the
+ * law are arguments here too); out_totals = {encoder tokens, decoder tokens},
+ * out_max_seqlens = {max e_r, max n_r - 1}.  Synchronises the stream.
+ * LDDL_EINDEX (a row index outside [0, n_total)), LDDL_EINVAL (n_rows <= 0,
+ * null pointers, a refused law, a row with s = 0 and a > 0), LDDL_ECAPACITY (a
+ * row longer than 2048 tokens; a stream of 2^31 tokens or more, summed in 64
+ * bits: the arrays then hold no offsets). */
+int lddl_collate_infill_rows_cu_seqlens(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                        const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                        const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                        int64_t n_total, int32_t max_span, double poisson_lambda, double mask_ratio,
+                                        uint64_t seed, uint64_t counter, int32_t *d_cu_seqlens,
+                                        int32_t *d_decoder_cu_seqlens, int64_t out_totals[2],
+                                        int64_t out_max_seqlens[2], void *hip_stream);
+
+/* Fill the streams: for t = cu_seqlens[r] + p, 0 <= p < e_r: input_ids[t] =
+ * input_ids[r, p] of the padded batch and position_ids[t] = p; for
+ * t = decoder_cu_seqlens[r] + j, 0 <= j < n_r - 1: decoder_input_ids[t] = id_j,
+ * labels[t] = id_{j + 1}, decoder_position_ids[t] = j.  The encoder outputs are
+ * int64 [total], the decoder outputs int64 [decoder_total] (the totals of the
+ * offsets call, or more).  Both offset arrays are checked, not trusted.
+ * Synchronises the stream.  Errors, first one wins, none faults, the row is
+ * left unwritten and no row stores outside its own tokens: LDDL_EINVAL (a row
+ * whose offsets are negative, do not hold e_r and n_r - 1 tokens or end beyond
+ * the totals; n_rows <= 0, null pointers, a refused law, a row with s = 0 and
+ * a > 0), LDDL_EINDEX (a row index outside [0, n_total)), LDDL_ECAPACITY (a
+ * row longer than 2048 tokens, a total >= 2^31). */
+int lddl_collate_infill_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                      const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                      const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                      int64_t n_total, const int32_t *d_cu_seqlens,
+                                      const int32_t *d_decoder_cu_seqlens, int64_t total, int64_t decoder_total,
+                                      int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio,
+                                      uint64_t seed, uint64_t counter, int64_t *d_input_ids, int64_t *d_position_ids,
+                                      int64_t *d_decoder_input_ids, int64_t *d_decoder_position_ids, int64_t *d_labels,
+                                      void *hip_stream);
+
 /* ---- compact MLM targets ----------------------------------------------------
  * The masked positions of a batch and their labels, in order: what a trainer
  * gathers the hidden states at before the LM head, so that the vocabulary

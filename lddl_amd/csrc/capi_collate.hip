@@ -1,5 +1,5 @@
 // C-ABI, host side of the training-time collate (kernels: collate.hip,
-// collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, rows_from_strings.hip, mlm_targets.hip).
+// collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, collate_infill.hip, rows_from_strings.hip, mlm_targets.hip).
 #include "capi_ctx.h"
 
 #include <math.h>
@@ -41,24 +41,13 @@ static int collate_vocab(lddl_ctx* c, CollateVocab* V) {
 }
 
 // ---------------------------------------------------------------- span masking --
-extern "C" int lddl_span_params(int32_t max_span, double geo_p, double mlm_probability, double* out_q,
-                                double out_cdf[16]) {
-  if (!out_q || !out_cdf) return set_err(LDDL_EINVAL, "null output pointer");
-  if (max_span < 1 || max_span > 16) return set_err(LDDL_EINVAL, "max_span %d not in [1, 16]", max_span);
-  if (!(geo_p > 0.0 && geo_p <= 1.0)) return set_err(LDDL_EINVAL, "geo_p not in (0, 1]");
-  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
-  const int L = max_span;
-  const double p = mlm_probability;
-  // 1 - (1 - g)^t = -expm1(t * log1p(-g)): no cancellation for a small g, and 1 for g = 1
-  const double lg = log1p(-geo_p), all = -expm1(L * lg);
-  for (int t = 1; t <= 16; ++t) out_cdf[t - 1] = t < L ? std::min(-expm1(t * lg) / all, 1.0) : 1.0;
-  if (L == 1) {
-    *out_q = p;
-    return 0;
-  }
-  // 1 - prod (1 - q * S_t), S_0 = 1, S_t = 1 - cdf[t], is 0 at 0, >= p at p and monotone.  Compared as the product
-  // against 1 - p, which stays exact near p = 1.  64 halvings of [0, p] keep missed(lo) > 1 - p >= missed(hi);
-  // q = hi, which is exactly 0 for p = 0 and exactly 1 for p = 1.
+// The start probability of a span law with max_span L, out_cdf[t - 1] = P(len <= t), that covers an interior word
+// with probability p (lddl_span_params and lddl_infill_params; include/lddl_amd.h).
+// 1 - prod (1 - q * S_t), S_0 = 1, S_t = 1 - cdf[t], is 0 at 0, >= p at p and monotone.  Compared as the product
+// against 1 - p, which stays exact near p = 1.  64 halvings of [0, p] keep missed(lo) > 1 - p >= missed(hi);
+// q = hi, which is exactly 0 for p = 0 and exactly 1 for p = 1.
+static double span_start_probability(int L, double p, const double out_cdf[16]) {
+  if (L == 1) return p;
   const auto missed = [&](double q) {
     double keep = 1.0 - q;
     for (int t = 1; t < L; ++t) keep *= 1.0 - q * (1.0 - out_cdf[t - 1]);
@@ -70,7 +59,39 @@ extern "C" int lddl_span_params(int32_t max_span, double geo_p, double mlm_proba
     if (missed(mid) > 1.0 - p) lo = mid;
     else hi = mid;
   }
-  *out_q = hi;
+  return hi;
+}
+
+extern "C" int lddl_span_params(int32_t max_span, double geo_p, double mlm_probability, double* out_q,
+                                double out_cdf[16]) {
+  if (!out_q || !out_cdf) return set_err(LDDL_EINVAL, "null output pointer");
+  if (max_span < 1 || max_span > 16) return set_err(LDDL_EINVAL, "max_span %d not in [1, 16]", max_span);
+  if (!(geo_p > 0.0 && geo_p <= 1.0)) return set_err(LDDL_EINVAL, "geo_p not in (0, 1]");
+  if (!(mlm_probability >= 0.0 && mlm_probability <= 1.0)) return set_err(LDDL_EINVAL, "mlm_probability not in [0, 1]");
+  const int L = max_span;
+  // 1 - (1 - g)^t = -expm1(t * log1p(-g)): no cancellation for a small g, and 1 for g = 1
+  const double lg = log1p(-geo_p), all = -expm1(L * lg);
+  for (int t = 1; t <= 16; ++t) out_cdf[t - 1] = t < L ? std::min(-expm1(t * lg) / all, 1.0) : 1.0;
+  *out_q = span_start_probability(L, mlm_probability, out_cdf);
+  return 0;
+}
+
+// Text infilling's law: Poisson(lambda) on 1 .. L.  The terms lambda^l / l! and their sums in long double, so that
+// every entry is the closed form rounded once; lambda^16 of a finite double is within its range.
+extern "C" int lddl_infill_params(int32_t max_span, double poisson_lambda, double mask_ratio, double* out_q,
+                                  double out_cdf[16]) {
+  if (!out_q || !out_cdf) return set_err(LDDL_EINVAL, "null output pointer");
+  if (max_span < 1 || max_span > 16) return set_err(LDDL_EINVAL, "max_span %d not in [1, 16]", max_span);
+  if (!(poisson_lambda > 0.0) || !std::isfinite(poisson_lambda)) return set_err(LDDL_EINVAL, "poisson_lambda not finite and > 0");
+  if (!(mask_ratio >= 0.0 && mask_ratio <= 1.0)) return set_err(LDDL_EINVAL, "mask_ratio not in [0, 1]");
+  const int L = max_span;
+  long double term = 1.0L, sum[17] = {0.0L};
+  for (int l = 1; l <= L; ++l) {
+    term *= (long double)poisson_lambda / l;
+    sum[l] = sum[l - 1] + term;
+  }
+  for (int t = 1; t <= 16; ++t) out_cdf[t - 1] = t < L ? std::min((double)(sum[t] / sum[L]), 1.0) : 1.0;
+  *out_q = span_start_probability(L, mask_ratio, out_cdf);
   return 0;
 }
 
@@ -595,6 +616,152 @@ extern "C" int lddl_collate_code_rows_fixed(lddl_ctx* c, const uint16_t* d_ids, 
                              nullptr, nullptr, nullptr, max_seqlen, d_cu_seqlens, tok_cap, mode, ignore_index, mlm_probability,
                              seed, counter, d_input_ids, d_token_type_ids, nullptr, d_position_ids, d_labels, nullptr, stream,
                              &F);
+}
+
+// ------------------------------------------------------------- text infilling --
+// What the three lddl_collate_infill_rows* calls share: the checks of the row selection and of the law, and the
+// params of a CodeBERT-row reader under that law.  labels 0: the offsets call, which has no ignore_index.  The
+// ctx's switches are not read: the law is the call's own.
+static int infill_common(lddl_ctx* c, int labels, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                         const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags, const int64_t* d_rows,
+                         int64_t row0, int64_t n_rows, int64_t n_total, int64_t ignore_index, int32_t max_span,
+                         double poisson_lambda, double mask_ratio, uint64_t seed, uint64_t counter,
+                         CollateInfillParams* I) {
+  if (!c) return set_err(LDDL_EINVAL, "null ctx");
+  if (n_rows < 0 || n_total < 0) return set_err(LDDL_EINVAL, "negative n_rows / n_total");
+  if (n_rows == 0) return set_err(LDDL_EINVAL, "empty batch");
+  if (!d_ids || !d_src0 || !d_src1 || !d_len0 || !d_len1 || !d_flags) return set_err(LDDL_EINVAL, "null pointer");
+  if (labels && (ignore_index < INT32_MIN || ignore_index > INT32_MAX)) return set_err(LDDL_EINVAL, "ignore_index out of int32");
+  CollateRowsParams& P = I->R;
+  int rc;
+  if ((rc = lddl_infill_params(max_span, poisson_lambda, mask_ratio, &P.span.q, P.span.cdf))) return rc;
+  P.span.L = max_span;
+  collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
+  P.ids = d_ids;
+  P.src0 = d_src0;
+  P.src1 = d_src1;
+  P.cls = (int32_t)c->special[2];
+  P.sep = (int32_t)c->special[3];
+  P.mask_id = (int32_t)c->special[4];
+  P.n_random = c->vocab_size;
+  P.ignore_index = ignore_index;
+  P.seed = seed;
+  P.counter = counter;
+  P.cont = c->d_cont;
+  HIP_TRY(hipSetDevice(c->device));
+  if ((rc = ws_get(c, CW_COLLATE_ERR, 1, &P.err))) return rc;
+  return 0;
+}
+
+extern "C" int lddl_collate_infill_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                        const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                        const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                        int64_t seq_len, int64_t ignore_index, int32_t max_span, double poisson_lambda,
+                                        double mask_ratio, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                        int64_t* d_attention_mask, int64_t* d_decoder_input_ids, int64_t* d_labels,
+                                        int32_t* d_enc_len, void* hip_stream) {
+  CollateInfillParams I{};
+  int rc;
+  if ((rc = infill_common(c, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, ignore_index,
+                          max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
+    return rc;
+  if (seq_len < 2 || seq_len > COLLATE_MAX_LEN)
+    return set_err(LDDL_ECAPACITY, "seq_len %lld not in [2, %d]", (long long)seq_len, COLLATE_MAX_LEN);
+  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_enc_len)
+    return set_err(LDDL_EINVAL, "null pointer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  I.R.seq_len = (int32_t)seq_len;
+  I.R.input_ids = d_input_ids;
+  I.R.attention_mask = d_attention_mask;
+  I.R.labels = d_labels;
+  I.decoder_input_ids = d_decoder_input_ids;
+  I.enc_len = d_enc_len;
+  uint32_t e;
+  HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
+  HIP_TRY(launch_infill_rows(I, c->n_cu, st));
+  if ((rc = read_err(c, I.R.err, st, &e))) return rc;
+  return e ? collate_rows_error(e, seq_len) : 0;
+}
+
+extern "C" int lddl_collate_infill_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                   const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                   const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                   int64_t n_rows, int64_t n_total, int32_t max_span,
+                                                   double poisson_lambda, double mask_ratio, uint64_t seed,
+                                                   uint64_t counter, int32_t* d_cu_seqlens, int32_t* d_decoder_cu_seqlens,
+                                                   int64_t out_totals[2], int64_t out_max_seqlens[2], void* hip_stream) {
+  CollateInfillParams I{};
+  int rc;
+  if ((rc = infill_common(c, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, 0, max_span,
+                          poisson_lambda, mask_ratio, seed, counter, &I)))
+    return rc;
+  if (!d_cu_seqlens || !d_decoder_cu_seqlens || !out_totals || !out_max_seqlens) return set_err(LDDL_EINVAL, "null pointer");
+  if (n_rows > INT32_MAX / 2) return set_err(LDDL_ECAPACITY, "%lld rows hold 2^31 tokens or more", (long long)n_rows);
+  hipStream_t st = (hipStream_t)hip_stream;
+  I.cu_enc = d_cu_seqlens;
+  I.cu_dec = d_decoder_cu_seqlens;
+  I.n_chunks = collate_chunks(n_rows);
+  int64_t* meta;  // both totals, then both maxima as int32: the layout of HW_NTOK, HW_PACK_ERR, HW_NMASK
+  if ((rc = ws_get(c, CW_SHARED_META, 3, &meta)) || (rc = ws_get(c, CW_SHARED_BSUM, 2 * (size_t)I.n_chunks, &I.chunk_sum)))
+    return rc;
+  I.totals_out = meta;
+  I.max_out = (int32_t*)(meta + 2);
+  uint32_t e;
+  HIP_TRY(hipMemsetAsync(meta, 0, 24, st));
+  HIP_TRY(hipMemsetAsync(I.chunk_sum, 0, 8 * (size_t)I.n_chunks, st));
+  HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
+  HIP_TRY(launch_infill_cu_seqlens(I, c->n_cu, st));
+  HIP_TRY(fetch_word(c, HW_NTOK, meta, 24, st));
+  if ((rc = read_err(c, I.R.err, st, &e))) return rc;
+  if (e) return collate_unpadded_error(e);
+  const int64_t te = c->h_tot[HW_NTOK], td = c->h_tot[HW_PACK_ERR];
+  if (te > INT32_MAX || td > INT32_MAX)
+    return set_err(LDDL_ECAPACITY, "the batch holds %lld encoder and %lld decoder tokens: cu_seqlens are int32", (long long)te,
+                   (long long)td);
+  const int32_t* mx = (const int32_t*)&c->h_tot[HW_NMASK];
+  out_totals[0] = te;
+  out_totals[1] = td;
+  out_max_seqlens[0] = mx[0];
+  out_max_seqlens[1] = mx[1];
+  return 0;
+}
+
+extern "C" int lddl_collate_infill_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                 const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                 const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                 int64_t n_rows, int64_t n_total, const int32_t* d_cu_seqlens,
+                                                 const int32_t* d_decoder_cu_seqlens, int64_t total,
+                                                 int64_t decoder_total, int64_t ignore_index, int32_t max_span,
+                                                 double poisson_lambda, double mask_ratio, uint64_t seed, uint64_t counter,
+                                                 int64_t* d_input_ids, int64_t* d_position_ids,
+                                                 int64_t* d_decoder_input_ids, int64_t* d_decoder_position_ids,
+                                                 int64_t* d_labels, void* hip_stream) {
+  CollateInfillParams I{};
+  int rc;
+  if ((rc = infill_common(c, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, ignore_index,
+                          max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
+    return rc;
+  if (total < 0 || decoder_total < 0) return set_err(LDDL_EINVAL, "negative total");
+  if (total > INT32_MAX || decoder_total > INT32_MAX)
+    return set_err(LDDL_ECAPACITY, "total %lld / %lld: cu_seqlens are int32", (long long)total, (long long)decoder_total);
+  if (!d_cu_seqlens || !d_decoder_cu_seqlens || !d_input_ids || !d_position_ids || !d_decoder_input_ids ||
+      !d_decoder_position_ids || !d_labels)
+    return set_err(LDDL_EINVAL, "null pointer");
+  hipStream_t st = (hipStream_t)hip_stream;
+  I.R.input_ids = d_input_ids;
+  I.R.labels = d_labels;
+  I.decoder_input_ids = d_decoder_input_ids;
+  I.position_ids = d_position_ids;
+  I.decoder_position_ids = d_decoder_position_ids;
+  I.cu_enc = const_cast<int32_t*>(d_cu_seqlens);  // read only by the fill pass
+  I.cu_dec = const_cast<int32_t*>(d_decoder_cu_seqlens);
+  I.total_enc = total;
+  I.total_dec = decoder_total;
+  uint32_t e;
+  HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
+  HIP_TRY(launch_infill_unpadded(I, c->n_cu, st));
+  if ((rc = read_err(c, I.R.err, st, &e))) return rc;
+  return e ? collate_unpadded_error(e) : 0;
 }
 
 // ------------------------------------------------------ compact MLM targets --

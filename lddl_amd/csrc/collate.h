@@ -152,6 +152,26 @@ struct CollateFixedParams {
   int64_t* total_out;      // [1] tokens of the batch, 64-bit
 };
 
+// lddl_collate_infill_rows[_cu_seqlens | _unpadded] (collate_infill.hip): text-infilling batches of CodeBERT /
+// MLM-only rows.  Of R: the row table and the row selection, cls / sep / mask_id / n_random, seed / counter,
+// ignore_index, cont and span (lddl_infill_params' law) are read; input_ids is the encoder's, labels the decoder's;
+// seq_len and attention_mask belong to the padded call; err as everywhere.
+struct CollateInfillParams {
+  CollateRowsParams R;
+  int64_t* decoder_input_ids;     // padded: [n_rows, seq_len]; padding-free: [total_dec], as R.labels
+  int32_t* enc_len;               // padded: [n_rows] e_r
+  int32_t* cu_enc;                // padding-free: [n_rows + 1] offsets of the encoder stream: the count pass leaves e_r in
+                                  // [r + 1], the scan sums in place, the fill checks them
+  int32_t* cu_dec;                // the same of the decoder stream, n_r - 1 tokens a row
+  int64_t* position_ids;          // [total_enc], as R.input_ids
+  int64_t* decoder_position_ids;  // [total_dec]
+  int64_t total_enc, total_dec;   // fill pass: the capacities of the two streams
+  uint32_t* chunk_sum;            // offsets pass: [n_chunks][2] encoder and decoder tokens of each chunk of rows (zeroed by the host)
+  int64_t* totals_out;            // offsets pass: [2] the tokens of the two streams
+  int32_t* max_out;               // offsets pass: [2] the longest row of each (zeroed by the host)
+  int64_t n_chunks;               // collate_chunks(n_rows)
+};
+
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
 // lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
@@ -240,6 +260,9 @@ hipError_t launch_collate_rows(const CollateRowsParams& P, bool code, int32_t mo
 hipError_t launch_collate_cu_seqlens(const CollateUnpaddedParams& P, bool code, hipStream_t s);
 hipError_t launch_collate_unpadded(const CollateUnpaddedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
 hipError_t launch_collate_fixed(const CollateFixedParams& P, bool code, int32_t mode, int n_cu, hipStream_t s);
+hipError_t launch_infill_rows(const CollateInfillParams& P, int n_cu, hipStream_t s);
+hipError_t launch_infill_cu_seqlens(const CollateInfillParams& P, int n_cu, hipStream_t s);
+hipError_t launch_infill_unpadded(const CollateInfillParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 // (a CodeBERT shard when P.num_tokens is set)

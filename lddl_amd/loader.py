@@ -808,6 +808,62 @@ class CodeCollate(_RowCollate):
     [max_seqs + 1], num_tokens / num_rows / num_seqs and ``status``."""
     return self._collate(True, res, rows, row0, n_rows, mode, (max_tokens, max_seqs, max_seqlen))
 
+  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span):
+    who = 'collate_infill_unpadded' if unpadded else 'collate_infill'
+    _, rows, row0, n = self._row_batch(who, res, rows, row0, n_rows, MODE_DYNAMIC)
+    L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
+    table = (p(res.ids), p(res.src0), p(res.src1), p(res.len0), p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs)
+    law = (int(max_span), float(poisson_lambda), float(mask_ratio), self.seed, self.counter)
+    i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=self.device)  # noqa: E731
+    if unpadded:
+      cu = torch.empty((2, n + 1), dtype=torch.int32, device=self.device)
+      totals, longest = (ctypes.c_int64 * 2)(), (ctypes.c_int64 * 2)()
+      _check(L.lddl_collate_infill_rows_cu_seqlens(h, *table, *law, p(cu[0]), p(cu[1]), totals, longest, st))
+      enc, dec = i64(2, totals[0]), i64(3, totals[1])
+      rc = L.lddl_collate_infill_rows_unpadded(h, *table, p(cu[0]), p(cu[1]), totals[0], totals[1], self.ignore_index, *law,
+                                               p(enc[0]), p(enc[1]), p(dec[0]), p(dec[2]), p(dec[1]), st)
+      batch = {'input_ids': enc[0], 'position_ids': enc[1], 'cu_seqlens': cu[0], 'max_seqlen': int(longest[0]),
+               'decoder_input_ids': dec[0], 'decoder_position_ids': dec[2], 'labels': dec[1],
+               'decoder_cu_seqlens': cu[1], 'decoder_max_seqlen': int(longest[1])}
+    else:
+      seq = ctypes.c_int64()
+      _check(L.lddl_collate_code_rows_seq_len(h, p(res.len0), p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs,
+                                              self.sequence_length_alignment, ctypes.byref(seq), st))
+      out, lens = i64(4, n, int(seq.value)), torch.empty(n, dtype=torch.int32, device=self.device)
+      rc = L.lddl_collate_infill_rows(h, *table, int(seq.value), self.ignore_index, *law, p(out[0]), p(out[1]), p(out[2]),
+                                      p(out[3]), p(lens), st)
+      batch = {'input_ids': out[0], 'attention_mask': out[1], 'decoder_input_ids': out[2], 'labels': out[3],
+               'encoder_lengths': lens}
+    self.counter += 1
+    _check(rc)
+    return batch
+
+  def collate_infill(self, res, rows=None, row0=0, n_rows=None, *, mask_ratio=0.3, poisson_lambda=3.0, max_span=10):
+    """A padded text-infilling batch (BART's denoising objective) for a
+    sequence-to-sequence model, rows picked as in ``collate_rows``
+    (lddl_collate_infill_rows; include/lddl_amd.h defines it).  Runs of whole
+    words inside one segment are selected: span lengths are Poisson
+    (``poisson_lambda``) on 1 .. ``max_span``, and spans start so often that a
+    word is covered with ``mask_ratio``.  Each selected run collapses to one
+    [MASK] in ``input_ids`` (int64 [n, S], 0 padded, with ``attention_mask`` and
+    the int32 ``encoder_lengths`` [n]); ``decoder_input_ids`` is the row without
+    its last token and ``labels`` the row without its first (ignore_index on
+    the padding).  S is ``collate_rows``' padded length: a corrupted row is
+    never longer than its source.  Draws by (seed, batch counter, row, column)
+    as ``collate_rows`` does, and advances the batch counter; the collate's
+    ``whole_word_mask`` / ``span_mask`` / ``max_predictions`` play no part."""
+    return self._infill(False, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span)
+
+  def collate_infill_unpadded(self, res, rows=None, row0=0, n_rows=None, *, mask_ratio=0.3, poisson_lambda=3.0,
+                              max_span=10):
+    """``collate_infill`` at the same seed and counter with the padding of both
+    sides dropped, bit for bit (lddl_collate_infill_rows_cu_seqlens +
+    lddl_collate_infill_rows_unpadded): the encoder stream ``input_ids`` /
+    ``position_ids`` with ``cu_seqlens`` (int32 [n + 1]) and ``max_seqlen``,
+    and the decoder stream ``decoder_input_ids`` / ``decoder_position_ids`` /
+    ``labels`` with ``decoder_cu_seqlens`` and ``decoder_max_seqlen``."""
+    return self._infill(True, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span)
+
   def load_rows(self, table, bins=None, part=None, nbins=None):
     """The rows of a CodeBERT shard as a GPU row table, once
     (lddl_code_rows_from_strings_len + lddl_code_rows_from_strings): a

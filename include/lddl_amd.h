@@ -877,6 +877,122 @@ int lddl_collate_infill_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, cons
                                       int64_t *d_decoder_input_ids, int64_t *d_decoder_position_ids, int64_t *d_labels,
                                       void *hip_stream);
 
+/* ---- span-corruption collate --------------------------------------------------
+ * The other sequence-to-sequence denoising objective: T5's span corruption
+ * (CodeT5's as well, and the R / X denoisers of UL2) over a WordPiece
+ * vocabulary.  The k-th corrupted run of a row becomes sentinel k in the
+ * encoder input, and the target lists every sentinel followed by the tokens it
+ * stands for.  Rows, the per-call law and the selection are text infilling's:
+ * for batch row r with n columns, id_j, special(j), start(j) and selected(j)
+ * are exactly those of the text-infilling definition above, span masking's
+ * `selected` under (q, cdf, L) of lddl_infill_params(max_span, poisson_lambda,
+ * mask_ratio), keyed by (seed, counter, r, j).  The ctx's whole-word, span and
+ * budget switches are neither read nor changed; BERT pair rows are out of
+ * scope.  The reference has no such loader.
+ *
+ * Sentinels: sentinel(k) = sentinel_base + k for k in [0, S), S =
+ * num_sentinels, ascending.
+ *   open(j)    = selected(j) and (j == 0 or !selected(j - 1))
+ *   ord(j)     = #{ i <= j : open(i) } - 1     (the ordinal of the run that
+ *                                               column j lies in)
+ *   corrupt(j) = selected(j) and ord(j) < S    (runs beyond the S-th are left
+ *                                               as they are)
+ *   encoder  walk j = 0 .. n-1:  !corrupt(j)            -> emit id_j
+ *                                corrupt(j) and open(j) -> emit sentinel(ord(j))
+ *                                otherwise              -> emit nothing
+ *            e_r = the number emitted; input_ids[r, 0:e_r] = the emitted
+ *            tokens, attention_mask 1 there, both 0 behind
+ *   target   walk j = 0 .. n-1:  corrupt(j) and open(j) -> emit sentinel(ord(j)),
+ *                                                          then id_j
+ *                                corrupt(j), not open   -> emit id_j
+ *            then emit [SEP] (the end-of-sequence token)
+ *            t_r = corrupted columns + corrupted runs + 1
+ *            labels[r, 0:t_r] = target, ignore_index behind
+ *            decoder_input_ids[r, 0] = [CLS]; decoder_input_ids[r, p] =
+ *            target[p - 1] for 1 <= p < t_r; 0 behind
+ *   enc_len[r] = e_r, dec_len[r] = t_r   (int32, on the device)
+ * Facts the layout rests on: runs are separated by at least one unselected
+ * column, and [CLS] and the final [SEP] are never selected, so corrupted
+ * columns + (runs - 1) <= n - 2, hence t_r <= n and e_r <= n.  Neither side is
+ * ever longer than its source row: the padded batch keeps
+ * lddl_collate_code_rows_seq_len's length for both sides (and a per-row buffer
+ * of 2048 entries holds either stream on the device).  Limits: mask_ratio 0
+ * gives input_ids = the row and labels = [SEP] alone (t_r = 1); mask_ratio 1
+ * with S >= 2 gives, for an MLM-only row, [CLS] sentinel(0) [SEP] against a
+ * target of length n.  There is no random-token replacement.
+ * tests/corrupt_model.py is this in numpy.
+ *
+ * Sentinel range, LDDL_EINVAL unless all hold: num_sentinels >= 1,
+ * sentinel_base >= 0, sentinel_base + num_sentinels <= 65536, and the range
+ * holds none of the ctx's [PAD], [CLS], [SEP], [MASK] ids.  It may lie beyond
+ * the vocabulary (extra ids appended to the embedding table): there is no
+ * vocabulary-size check.
+ *
+ * The three calls mirror the three text-infilling calls argument for argument,
+ * with sentinel_base, num_sentinels behind mask_ratio; hip_stream as there.
+ *
+ * lddl_collate_corrupt_rows: the padded batch, four int64 [n_rows, seq_len]
+ * outputs, d_enc_len and d_dec_len; seq_len from
+ * lddl_collate_code_rows_seq_len (or any value that holds the longest row).
+ * Synchronises the stream.  Errors, first one wins, none faults, a refused row
+ * is left unwritten: LDDL_EINDEX (a row index outside [0, n_total), checked
+ * before any load through it), LDDL_ECAPACITY (a row longer than seq_len,
+ * seq_len not in [2, 2048]), LDDL_EINVAL (n_rows <= 0, null pointers, a refused
+ * law, a refused sentinel range, a row with s = 0 and a > 0). */
+int lddl_collate_corrupt_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                              const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                              const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total, int64_t seq_len,
+                              int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio,
+                              int32_t sentinel_base, int32_t num_sentinels, uint64_t seed, uint64_t counter,
+                              int64_t *d_input_ids, int64_t *d_attention_mask, int64_t *d_decoder_input_ids,
+                              int64_t *d_labels, int32_t *d_enc_len, int32_t *d_dec_len, void *hip_stream);
+
+/* The padding-free batch: the encoder stream with row r at [cu_seqlens[r],
+ * cu_seqlens[r] + e_r) and the decoder stream with row r at
+ * [decoder_cu_seqlens[r], decoder_cu_seqlens[r] + t_r).  Bit for bit
+ * lddl_collate_corrupt_rows at the same law, sentinels, seed and counter with
+ * the columns >= e_r (encoder) and >= t_r (decoder) of every row dropped.
+ *
+ * lddl_collate_corrupt_rows_cu_seqlens: both offset arrays, int32 [n_rows + 1]
+ * on the device (both lengths depend on the selection, which is computed to
+ * count them); out_totals = {encoder tokens, decoder tokens}, out_max_seqlens =
+ * {max e_r, max t_r}.  Synchronises the stream.  LDDL_EINDEX (a row index
+ * outside [0, n_total)), LDDL_EINVAL (n_rows <= 0, null pointers, a refused
+ * law, a refused sentinel range, a row with s = 0 and a > 0), LDDL_ECAPACITY (a
+ * row longer than 2048 tokens; a stream of 2^31 tokens or more, summed in 64
+ * bits: the arrays then hold no offsets). */
+int lddl_collate_corrupt_rows_cu_seqlens(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                         const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                         const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                         int64_t n_total, int32_t max_span, double poisson_lambda, double mask_ratio,
+                                         int32_t sentinel_base, int32_t num_sentinels, uint64_t seed, uint64_t counter,
+                                         int32_t *d_cu_seqlens, int32_t *d_decoder_cu_seqlens, int64_t out_totals[2],
+                                         int64_t out_max_seqlens[2], void *hip_stream);
+
+/* Fill the streams: for t = cu_seqlens[r] + p, 0 <= p < e_r: input_ids[t] =
+ * input_ids[r, p] of the padded batch and position_ids[t] = p; for
+ * t = decoder_cu_seqlens[r] + p, 0 <= p < t_r: decoder_input_ids[t] and
+ * labels[t] = those of the padded batch at [r, p], decoder_position_ids[t] = p.
+ * The encoder outputs are int64 [total], the decoder outputs int64
+ * [decoder_total] (the totals of the offsets call, or more).  Both offset
+ * arrays are checked, not trusted: the encoder's and the decoder's are each
+ * compared with the walk's own count before anything of the row is stored.
+ * Synchronises the stream.  Errors, first one wins, none faults, the row is
+ * left unwritten and no row stores outside its own tokens: LDDL_EINVAL (a row
+ * whose offsets are negative, do not hold e_r and t_r tokens or end beyond the
+ * totals; n_rows <= 0, null pointers, a refused law, a refused sentinel range,
+ * a row with s = 0 and a > 0), LDDL_EINDEX (a row index outside [0, n_total)),
+ * LDDL_ECAPACITY (a row longer than 2048 tokens, a total >= 2^31). */
+int lddl_collate_corrupt_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                       const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                       const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                       int64_t n_total, const int32_t *d_cu_seqlens,
+                                       const int32_t *d_decoder_cu_seqlens, int64_t total, int64_t decoder_total,
+                                       int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio,
+                                       int32_t sentinel_base, int32_t num_sentinels, uint64_t seed, uint64_t counter,
+                                       int64_t *d_input_ids, int64_t *d_position_ids, int64_t *d_decoder_input_ids,
+                                       int64_t *d_decoder_position_ids, int64_t *d_labels, void *hip_stream);
+
 /* ---- compact MLM targets ----------------------------------------------------
  * The masked positions of a batch and their labels, in order: what a trainer
  * gathers the hidden states at before the LM head, so that the vocabulary

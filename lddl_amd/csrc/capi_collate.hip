@@ -1,5 +1,6 @@
 // C-ABI, host side of the training-time collate (kernels: collate.hip,
-// collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, collate_infill.hip, rows_from_strings.hip, mlm_targets.hip).
+// collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, collate_infill.hip, collate_corrupt.hip,
+// rows_from_strings.hip, mlm_targets.hip).
 #include "capi_ctx.h"
 
 #include <math.h>
@@ -622,8 +623,32 @@ extern "C" int lddl_collate_code_rows_fixed(lddl_ctx* c, const uint16_t* d_ids, 
 // What the three lddl_collate_infill_rows* calls share: the checks of the row selection and of the law, and the
 // params of a CodeBERT-row reader under that law.  labels 0: the offsets call, which has no ignore_index.  The
 // ctx's switches are not read: the law is the call's own.
-static int infill_common(lddl_ctx* c, int labels, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
-                         const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags, const int64_t* d_rows,
+//
+// The three lddl_collate_corrupt_rows* calls are the same three bodies (infill_rows, infill_cu_seqlens,
+// infill_unpadded below) with a Sentinels: its range is checked here, and the launch is collate_corrupt.hip's over
+// the same params and the same workspace words.  X NULL: text infilling.
+struct Sentinels {
+  int32_t base, count;
+  int32_t* d_dec_len;  // the padded call's second length output
+};
+
+static int check_sentinels(const lddl_ctx* c, const Sentinels& X) {
+  if (X.count < 1 || X.base < 0 || (int64_t)X.base + X.count > 65536)
+    return set_err(LDDL_EINVAL, "sentinels (base %d, count %d) are not a range inside [0, 65536)", X.base, X.count);
+  static const char* const kName[5] = {"[PAD]", "[UNK]", "[CLS]", "[SEP]", "[MASK]"};
+  for (int k : {0, 2, 3, 4})
+    if ((int64_t)c->special[k] >= X.base && (int64_t)c->special[k] < (int64_t)X.base + X.count)
+      return set_err(LDDL_EINVAL, "sentinels [%d, %d) hold %s (id %u)", X.base, X.base + X.count, kName[k], c->special[k]);
+  return 0;
+}
+
+static CollateCorruptParams corrupt_params(const CollateInfillParams& I, const Sentinels& X) {
+  return CollateCorruptParams{I, X.base, X.count, X.d_dec_len};
+}
+
+static int infill_common(lddl_ctx* c, const Sentinels* X, int labels, const uint16_t* d_ids, const int64_t* d_src0,
+                         const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                         const uint8_t* d_flags, const int64_t* d_rows,
                          int64_t row0, int64_t n_rows, int64_t n_total, int64_t ignore_index, int32_t max_span,
                          double poisson_lambda, double mask_ratio, uint64_t seed, uint64_t counter,
                          CollateInfillParams* I) {
@@ -635,6 +660,7 @@ static int infill_common(lddl_ctx* c, int labels, const uint16_t* d_ids, const i
   CollateRowsParams& P = I->R;
   int rc;
   if ((rc = lddl_infill_params(max_span, poisson_lambda, mask_ratio, &P.span.q, P.span.cdf))) return rc;
+  if (X && (rc = check_sentinels(c, *X))) return rc;
   P.span.L = max_span;
   collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   P.ids = d_ids;
@@ -653,21 +679,20 @@ static int infill_common(lddl_ctx* c, int labels, const uint16_t* d_ids, const i
   return 0;
 }
 
-extern "C" int lddl_collate_infill_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
-                                        const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
-                                        const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
-                                        int64_t seq_len, int64_t ignore_index, int32_t max_span, double poisson_lambda,
-                                        double mask_ratio, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
-                                        int64_t* d_attention_mask, int64_t* d_decoder_input_ids, int64_t* d_labels,
-                                        int32_t* d_enc_len, void* hip_stream) {
+static int infill_rows(lddl_ctx* c, const Sentinels* X, const uint16_t* d_ids, const int64_t* d_src0,
+                       const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                       const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total, int64_t seq_len,
+                       int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio, uint64_t seed,
+                       uint64_t counter, int64_t* d_input_ids, int64_t* d_attention_mask, int64_t* d_decoder_input_ids,
+                       int64_t* d_labels, int32_t* d_enc_len, void* hip_stream) {
   CollateInfillParams I{};
   int rc;
-  if ((rc = infill_common(c, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, ignore_index,
-                          max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
+  if ((rc = infill_common(c, X, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                          ignore_index, max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
     return rc;
   if (seq_len < 2 || seq_len > COLLATE_MAX_LEN)
     return set_err(LDDL_ECAPACITY, "seq_len %lld not in [2, %d]", (long long)seq_len, COLLATE_MAX_LEN);
-  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_enc_len)
+  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_enc_len || (X && !X->d_dec_len))
     return set_err(LDDL_EINVAL, "null pointer");
   hipStream_t st = (hipStream_t)hip_stream;
   I.R.seq_len = (int32_t)seq_len;
@@ -678,22 +703,47 @@ extern "C" int lddl_collate_infill_rows(lddl_ctx* c, const uint16_t* d_ids, cons
   I.enc_len = d_enc_len;
   uint32_t e;
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(launch_infill_rows(I, c->n_cu, st));
+  HIP_TRY(X ? launch_corrupt_rows(corrupt_params(I, *X), c->n_cu, st) : launch_infill_rows(I, c->n_cu, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   return e ? collate_rows_error(e, seq_len) : 0;
 }
 
-extern "C" int lddl_collate_infill_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
-                                                   const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
-                                                   const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
-                                                   int64_t n_rows, int64_t n_total, int32_t max_span,
-                                                   double poisson_lambda, double mask_ratio, uint64_t seed,
-                                                   uint64_t counter, int32_t* d_cu_seqlens, int32_t* d_decoder_cu_seqlens,
-                                                   int64_t out_totals[2], int64_t out_max_seqlens[2], void* hip_stream) {
+extern "C" int lddl_collate_infill_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                        const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                        const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                        int64_t seq_len, int64_t ignore_index, int32_t max_span, double poisson_lambda,
+                                        double mask_ratio, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                        int64_t* d_attention_mask, int64_t* d_decoder_input_ids, int64_t* d_labels,
+                                        int32_t* d_enc_len, void* hip_stream) {
+  return infill_rows(c, nullptr, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, seq_len,
+                     ignore_index, max_span, poisson_lambda, mask_ratio, seed, counter, d_input_ids, d_attention_mask,
+                     d_decoder_input_ids, d_labels, d_enc_len, hip_stream);
+}
+
+extern "C" int lddl_collate_corrupt_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                         const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                         const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                         int64_t seq_len, int64_t ignore_index, int32_t max_span, double poisson_lambda,
+                                         double mask_ratio, int32_t sentinel_base, int32_t num_sentinels, uint64_t seed,
+                                         uint64_t counter, int64_t* d_input_ids, int64_t* d_attention_mask,
+                                         int64_t* d_decoder_input_ids, int64_t* d_labels, int32_t* d_enc_len,
+                                         int32_t* d_dec_len, void* hip_stream) {
+  const Sentinels X{sentinel_base, num_sentinels, d_dec_len};
+  return infill_rows(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, seq_len,
+                     ignore_index, max_span, poisson_lambda, mask_ratio, seed, counter, d_input_ids, d_attention_mask,
+                     d_decoder_input_ids, d_labels, d_enc_len, hip_stream);
+}
+
+static int infill_cu_seqlens(lddl_ctx* c, const Sentinels* X, const uint16_t* d_ids, const int64_t* d_src0,
+                             const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                             const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                             int64_t n_total, int32_t max_span, double poisson_lambda, double mask_ratio, uint64_t seed,
+                             uint64_t counter, int32_t* d_cu_seqlens, int32_t* d_decoder_cu_seqlens,
+                             int64_t out_totals[2], int64_t out_max_seqlens[2], void* hip_stream) {
   CollateInfillParams I{};
   int rc;
-  if ((rc = infill_common(c, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, 0, max_span,
-                          poisson_lambda, mask_ratio, seed, counter, &I)))
+  if ((rc = infill_common(c, X, 0, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, 0,
+                          max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
     return rc;
   if (!d_cu_seqlens || !d_decoder_cu_seqlens || !out_totals || !out_max_seqlens) return set_err(LDDL_EINVAL, "null pointer");
   if (n_rows > INT32_MAX / 2) return set_err(LDDL_ECAPACITY, "%lld rows hold 2^31 tokens or more", (long long)n_rows);
@@ -710,7 +760,7 @@ extern "C" int lddl_collate_infill_rows_cu_seqlens(lddl_ctx* c, const uint16_t* 
   HIP_TRY(hipMemsetAsync(meta, 0, 24, st));
   HIP_TRY(hipMemsetAsync(I.chunk_sum, 0, 8 * (size_t)I.n_chunks, st));
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(launch_infill_cu_seqlens(I, c->n_cu, st));
+  HIP_TRY(X ? launch_corrupt_cu_seqlens(corrupt_params(I, *X), c->n_cu, st) : launch_infill_cu_seqlens(I, c->n_cu, st));
   HIP_TRY(fetch_word(c, HW_NTOK, meta, 24, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   if (e) return collate_unpadded_error(e);
@@ -726,20 +776,44 @@ extern "C" int lddl_collate_infill_rows_cu_seqlens(lddl_ctx* c, const uint16_t* 
   return 0;
 }
 
-extern "C" int lddl_collate_infill_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
-                                                 const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
-                                                 const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
-                                                 int64_t n_rows, int64_t n_total, const int32_t* d_cu_seqlens,
-                                                 const int32_t* d_decoder_cu_seqlens, int64_t total,
-                                                 int64_t decoder_total, int64_t ignore_index, int32_t max_span,
-                                                 double poisson_lambda, double mask_ratio, uint64_t seed, uint64_t counter,
-                                                 int64_t* d_input_ids, int64_t* d_position_ids,
-                                                 int64_t* d_decoder_input_ids, int64_t* d_decoder_position_ids,
-                                                 int64_t* d_labels, void* hip_stream) {
+extern "C" int lddl_collate_infill_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                   const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                   const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                   int64_t n_rows, int64_t n_total, int32_t max_span,
+                                                   double poisson_lambda, double mask_ratio, uint64_t seed,
+                                                   uint64_t counter, int32_t* d_cu_seqlens, int32_t* d_decoder_cu_seqlens,
+                                                   int64_t out_totals[2], int64_t out_max_seqlens[2], void* hip_stream) {
+  return infill_cu_seqlens(c, nullptr, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                           max_span, poisson_lambda, mask_ratio, seed, counter, d_cu_seqlens, d_decoder_cu_seqlens,
+                           out_totals, out_max_seqlens, hip_stream);
+}
+
+extern "C" int lddl_collate_corrupt_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                    const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                    const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                    int64_t n_rows, int64_t n_total, int32_t max_span,
+                                                    double poisson_lambda, double mask_ratio, int32_t sentinel_base,
+                                                    int32_t num_sentinels, uint64_t seed, uint64_t counter,
+                                                    int32_t* d_cu_seqlens, int32_t* d_decoder_cu_seqlens,
+                                                    int64_t out_totals[2], int64_t out_max_seqlens[2], void* hip_stream) {
+  const Sentinels X{sentinel_base, num_sentinels, nullptr};
+  return infill_cu_seqlens(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, max_span,
+                           poisson_lambda, mask_ratio, seed, counter, d_cu_seqlens, d_decoder_cu_seqlens, out_totals,
+                           out_max_seqlens, hip_stream);
+}
+
+static int infill_unpadded(lddl_ctx* c, const Sentinels* X, const uint16_t* d_ids, const int64_t* d_src0,
+                           const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                           const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                           const int32_t* d_cu_seqlens, const int32_t* d_decoder_cu_seqlens, int64_t total,
+                           int64_t decoder_total, int64_t ignore_index, int32_t max_span, double poisson_lambda,
+                           double mask_ratio, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                           int64_t* d_position_ids, int64_t* d_decoder_input_ids, int64_t* d_decoder_position_ids,
+                           int64_t* d_labels, void* hip_stream) {
   CollateInfillParams I{};
   int rc;
-  if ((rc = infill_common(c, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, ignore_index,
-                          max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
+  if ((rc = infill_common(c, X, 1, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                          ignore_index, max_span, poisson_lambda, mask_ratio, seed, counter, &I)))
     return rc;
   if (total < 0 || decoder_total < 0) return set_err(LDDL_EINVAL, "negative total");
   if (total > INT32_MAX || decoder_total > INT32_MAX)
@@ -759,9 +833,43 @@ extern "C" int lddl_collate_infill_rows_unpadded(lddl_ctx* c, const uint16_t* d_
   I.total_dec = decoder_total;
   uint32_t e;
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(launch_infill_unpadded(I, c->n_cu, st));
+  HIP_TRY(X ? launch_corrupt_unpadded(corrupt_params(I, *X), c->n_cu, st) : launch_infill_unpadded(I, c->n_cu, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   return e ? collate_unpadded_error(e) : 0;
+}
+
+extern "C" int lddl_collate_infill_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                 const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                 const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                 int64_t n_rows, int64_t n_total, const int32_t* d_cu_seqlens,
+                                                 const int32_t* d_decoder_cu_seqlens, int64_t total,
+                                                 int64_t decoder_total, int64_t ignore_index, int32_t max_span,
+                                                 double poisson_lambda, double mask_ratio, uint64_t seed, uint64_t counter,
+                                                 int64_t* d_input_ids, int64_t* d_position_ids,
+                                                 int64_t* d_decoder_input_ids, int64_t* d_decoder_position_ids,
+                                                 int64_t* d_labels, void* hip_stream) {
+  return infill_unpadded(c, nullptr, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                         d_cu_seqlens, d_decoder_cu_seqlens, total, decoder_total, ignore_index, max_span, poisson_lambda,
+                         mask_ratio, seed, counter, d_input_ids, d_position_ids, d_decoder_input_ids,
+                         d_decoder_position_ids, d_labels, hip_stream);
+}
+
+extern "C" int lddl_collate_corrupt_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                  const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                  const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                  int64_t n_rows, int64_t n_total, const int32_t* d_cu_seqlens,
+                                                  const int32_t* d_decoder_cu_seqlens, int64_t total,
+                                                  int64_t decoder_total, int64_t ignore_index, int32_t max_span,
+                                                  double poisson_lambda, double mask_ratio, int32_t sentinel_base,
+                                                  int32_t num_sentinels, uint64_t seed, uint64_t counter,
+                                                  int64_t* d_input_ids, int64_t* d_position_ids,
+                                                  int64_t* d_decoder_input_ids, int64_t* d_decoder_position_ids,
+                                                  int64_t* d_labels, void* hip_stream) {
+  const Sentinels X{sentinel_base, num_sentinels, nullptr};
+  return infill_unpadded(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                         d_cu_seqlens, d_decoder_cu_seqlens, total, decoder_total, ignore_index, max_span, poisson_lambda,
+                         mask_ratio, seed, counter, d_input_ids, d_position_ids, d_decoder_input_ids,
+                         d_decoder_position_ids, d_labels, hip_stream);
 }
 
 // ------------------------------------------------------ compact MLM targets --

@@ -172,6 +172,16 @@ struct CollateInfillParams {
   int64_t n_chunks;               // collate_chunks(n_rows)
 };
 
+// lddl_collate_corrupt_rows[_cu_seqlens | _unpadded] (collate_corrupt.hip): span-corruption batches of the same rows
+// under the same law.  I is read as the infill kernels read it, with two differences: the decoder side is the
+// target stream (t_r tokens a row, data-dependent as e_r is), so cu_dec is checked against the walk's count as
+// cu_enc is, and R.mask_id is not read: corrupted run k < num_sentinels shows sentinel_base + k.
+struct CollateCorruptParams {
+  CollateInfillParams I;
+  int32_t sentinel_base, num_sentinels;  // checked by the host: [base, base + count) lies in [0, 65536)
+  int32_t* dec_len;                      // padded: [n_rows] t_r
+};
+
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
 // lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
@@ -263,6 +273,11 @@ hipError_t launch_collate_fixed(const CollateFixedParams& P, bool code, int32_t 
 hipError_t launch_infill_rows(const CollateInfillParams& P, int n_cu, hipStream_t s);
 hipError_t launch_infill_cu_seqlens(const CollateInfillParams& P, int n_cu, hipStream_t s);
 hipError_t launch_infill_unpadded(const CollateInfillParams& P, int n_cu, hipStream_t s);
+// the second level of launch_infill_cu_seqlens alone: cu_enc / cu_dec hold the rows' counts, chunk_sum their chunk sums
+hipError_t launch_infill_scan(const CollateInfillParams& P, hipStream_t s);
+hipError_t launch_corrupt_rows(const CollateCorruptParams& P, int n_cu, hipStream_t s);
+hipError_t launch_corrupt_cu_seqlens(const CollateCorruptParams& P, int n_cu, hipStream_t s);
+hipError_t launch_corrupt_unpadded(const CollateCorruptParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 // (a CodeBERT shard when P.num_tokens is set)

@@ -41,7 +41,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .tokenizer import Tokenizer, _stream
+from .tokenizer import Tokenizer, _stream, vocab_entries
 
 MODE_SPECIAL_MASK, MODE_STATIC, MODE_DYNAMIC = 0, 1, 2
 
@@ -147,6 +147,22 @@ def _shard_columns(table):
   parts = [_table_columns(t, static) for t in table]
   cols = [_merge_columns([c[k] for c, _ in parts]) for k in range(4 if static else 2)]
   return cols, np.concatenate([rn for _, rn in parts]), static
+
+
+def default_sentinels(vocab):
+  """(base, count) of the sentinels that ``collate_span_corruption`` takes when
+  it is given none: the longest run [unused0], [unused1], ... whose ids are
+  consecutive.  vocab: a token -> id mapping, or a vocabulary file.  Host
+  only."""
+  if not hasattr(vocab, 'get'):
+    vocab = {t: i for i, t in enumerate(vocab_entries(vocab))}
+  base = vocab.get('[unused0]')
+  if base is None:
+    raise ValueError('sentinels: the vocabulary has no [unused0] to take them from; pass sentinels=(base, count)')
+  count = 1
+  while vocab.get('[unused%d]' % count) == base + count:
+    count += 1
+  return base, count
 
 
 def _check(rc):
@@ -808,20 +824,26 @@ class CodeCollate(_RowCollate):
     [max_seqs + 1], num_tokens / num_rows / num_seqs and ``status``."""
     return self._collate(True, res, rows, row0, n_rows, mode, (max_tokens, max_seqs, max_seqlen))
 
-  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span):
-    who = 'collate_infill_unpadded' if unpadded else 'collate_infill'
-    _, rows, row0, n = self._row_batch(who, res, rows, row0, n_rows, MODE_DYNAMIC)
+  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, sentinels=None):
+    """The body of the two denoising objectives: text infilling, or, with
+    ``sentinels`` = (base, count), span corruption, whose three C calls take the
+    same arguments with the pair behind the law and a second length output."""
     L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
+    if sentinels is None:
+      name, who, law2 = 'lddl_collate_infill_rows', 'collate_infill', ()
+    else:
+      name, who, law2 = 'lddl_collate_corrupt_rows', 'collate_span_corruption', (int(sentinels[0]), int(sentinels[1]))
+    _, rows, row0, n = self._row_batch(who + '_unpadded' * unpadded, res, rows, row0, n_rows, MODE_DYNAMIC)
     table = (p(res.ids), p(res.src0), p(res.src1), p(res.len0), p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs)
-    law = (int(max_span), float(poisson_lambda), float(mask_ratio), self.seed, self.counter)
+    law = (int(max_span), float(poisson_lambda), float(mask_ratio)) + law2 + (self.seed, self.counter)
     i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=self.device)  # noqa: E731
     if unpadded:
       cu = torch.empty((2, n + 1), dtype=torch.int32, device=self.device)
       totals, longest = (ctypes.c_int64 * 2)(), (ctypes.c_int64 * 2)()
-      _check(L.lddl_collate_infill_rows_cu_seqlens(h, *table, *law, p(cu[0]), p(cu[1]), totals, longest, st))
+      _check(getattr(L, name + '_cu_seqlens')(h, *table, *law, p(cu[0]), p(cu[1]), totals, longest, st))
       enc, dec = i64(2, totals[0]), i64(3, totals[1])
-      rc = L.lddl_collate_infill_rows_unpadded(h, *table, p(cu[0]), p(cu[1]), totals[0], totals[1], self.ignore_index, *law,
-                                               p(enc[0]), p(enc[1]), p(dec[0]), p(dec[2]), p(dec[1]), st)
+      rc = getattr(L, name + '_unpadded')(h, *table, p(cu[0]), p(cu[1]), totals[0], totals[1], self.ignore_index, *law,
+                                          p(enc[0]), p(enc[1]), p(dec[0]), p(dec[2]), p(dec[1]), st)
       batch = {'input_ids': enc[0], 'position_ids': enc[1], 'cu_seqlens': cu[0], 'max_seqlen': int(longest[0]),
                'decoder_input_ids': dec[0], 'decoder_position_ids': dec[2], 'labels': dec[1],
                'decoder_cu_seqlens': cu[1], 'decoder_max_seqlen': int(longest[1])}
@@ -829,11 +851,13 @@ class CodeCollate(_RowCollate):
       seq = ctypes.c_int64()
       _check(L.lddl_collate_code_rows_seq_len(h, p(res.len0), p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs,
                                               self.sequence_length_alignment, ctypes.byref(seq), st))
-      out, lens = i64(4, n, int(seq.value)), torch.empty(n, dtype=torch.int32, device=self.device)
-      rc = L.lddl_collate_infill_rows(h, *table, int(seq.value), self.ignore_index, *law, p(out[0]), p(out[1]), p(out[2]),
-                                      p(out[3]), p(lens), st)
+      out, lens = i64(4, n, int(seq.value)), torch.empty((1 + bool(law2), n), dtype=torch.int32, device=self.device)
+      rc = getattr(L, name)(h, *table, int(seq.value), self.ignore_index, *law, p(out[0]), p(out[1]), p(out[2]), p(out[3]),
+                            *[p(x) for x in lens], st)
       batch = {'input_ids': out[0], 'attention_mask': out[1], 'decoder_input_ids': out[2], 'labels': out[3],
-               'encoder_lengths': lens}
+               'encoder_lengths': lens[0]}
+      if law2:
+        batch['decoder_lengths'] = lens[1]
     self.counter += 1
     _check(rc)
     return batch
@@ -863,6 +887,41 @@ class CodeCollate(_RowCollate):
     and the decoder stream ``decoder_input_ids`` / ``decoder_position_ids`` /
     ``labels`` with ``decoder_cu_seqlens`` and ``decoder_max_seqlen``."""
     return self._infill(True, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span)
+
+  def _sentinels(self, sentinels):
+    if sentinels is not None:
+      base, count = sentinels
+      return int(base), int(count)
+    return default_sentinels(self.tok.vocab)
+
+  def collate_span_corruption(self, res, rows=None, row0=0, n_rows=None, *, mask_ratio=0.15, poisson_lambda=3.0,
+                              max_span=10, sentinels=None):
+    """A padded span-corruption batch (T5's and CodeT5's denoising objective)
+    for a sequence-to-sequence model, rows picked as in ``collate_rows``
+    (lddl_collate_corrupt_rows; include/lddl_amd.h defines it).  Runs of whole
+    words are selected as ``collate_infill`` selects them.  The k-th run of a
+    row becomes sentinel k in ``input_ids`` (int64 [n, S], 0 padded, with
+    ``attention_mask`` and the int32 ``encoder_lengths`` [n]); ``labels`` lists
+    every sentinel followed by the tokens it stands for and ends with [SEP]
+    (ignore_index behind, the int32 ``decoder_lengths`` [n]), and
+    ``decoder_input_ids`` is ``labels`` shifted right behind a [CLS].  S is
+    ``collate_rows``' padded length on both sides: neither is ever longer than
+    the row.  ``sentinels`` = (base, count): sentinel k is id base + k; runs
+    beyond the count-th are left as they are; the ids may lie beyond the
+    vocabulary, but may not be [PAD], [CLS], [SEP] or [MASK].  None: the longest
+    run [unused0], [unused1], ... of consecutive ids in the collate's
+    vocabulary (``default_sentinels``; 1..99 for the BERT vocabulary), and a
+    ValueError when it has no [unused0].  Draws and the batch counter as
+    ``collate_infill``."""
+    return self._infill(False, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, self._sentinels(sentinels))
+
+  def collate_span_corruption_unpadded(self, res, rows=None, row0=0, n_rows=None, *, mask_ratio=0.15, poisson_lambda=3.0,
+                                       max_span=10, sentinels=None):
+    """``collate_span_corruption`` at the same seed and counter with the padding
+    of both sides dropped, bit for bit (lddl_collate_corrupt_rows_cu_seqlens +
+    lddl_collate_corrupt_rows_unpadded), under the keys of
+    ``collate_infill_unpadded``: both streams' lengths depend on the draw."""
+    return self._infill(True, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, self._sentinels(sentinels))
 
   def load_rows(self, table, bins=None, part=None, nbins=None):
     """The rows of a CodeBERT shard as a GPU row table, once

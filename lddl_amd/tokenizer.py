@@ -57,6 +57,17 @@ class CapacityError(RuntimeError):
     self.total, self.cap = total, cap
 
 
+def vocab_entries(vocab_file):
+  """The entries of a vocabulary file by id, as the native tables read them
+  (tok_tables.h): split at '\\n' only, trailing White_Space trimmed; a
+  duplicate line's last id wins.  Host only."""
+  with open(vocab_file, 'rb') as f:
+    lines = f.read().split(b'\n')
+  if lines and lines[-1] == b'':
+    lines.pop()
+  return [l.decode('utf-8', 'replace').rstrip(_WHITE_SPACE) for l in lines]
+
+
 class Tokenizer:
   """Owns the device vocab/Unicode tables for one GPU (one lddl_ctx)."""
 
@@ -74,13 +85,7 @@ class Tokenizer:
     ids = (ctypes.c_int32 * 5)()
     _lib.check(L.lddl_special_ids(h, ids))
     self.pad_id, self.unk_id, self.cls_id, self.sep_id, self.mask_id = list(ids)
-    # the lines as the native tables read them (tok_tables.h): split at '\n'
-    # only, trailing White_Space trimmed; a duplicate line's last id wins
-    with open(vocab_file, 'rb') as f:
-      lines = f.read().split(b'\n')
-    if lines and lines[-1] == b'':
-      lines.pop()
-    self.ids_to_tokens = [l.decode('utf-8', 'replace').rstrip(_WHITE_SPACE) for l in lines]
+    self.ids_to_tokens = vocab_entries(vocab_file)
     if len(self.ids_to_tokens) != self.vocab_size:
       raise RuntimeError('lddl_amd: %s has %d lines here and %d entries in the device tables (did the file change?)'
                          % (vocab_file, len(self.ids_to_tokens), self.vocab_size))

@@ -993,6 +993,95 @@ int lddl_collate_corrupt_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, con
                                        int64_t *d_input_ids, int64_t *d_position_ids, int64_t *d_decoder_input_ids,
                                        int64_t *d_decoder_position_ids, int64_t *d_labels, void *hip_stream);
 
+/* ---- exact-count span corruption ------------------------------------------------
+ * Span corruption as T5 draws it (`random_spans_noise_mask`, which HF's
+ * DataCollatorForT5MLM copies): the number of noise tokens and of noise spans
+ * of a row are fixed by its length, and the draw is one uniformly random
+ * segmentation with exactly those counts.  Both output lengths of a row are
+ * therefore functions of its length alone (lddl_corrupt_exact_lengths, host
+ * only), where the Poisson law above leaves them binomial.  Rows, row picking,
+ * sentinels and every output are those of lddl_collate_corrupt_rows*; the ctx's
+ * switches are neither read nor changed; BERT pair rows are out of scope.  Only
+ * `selected` differs.  For batch row r with n columns:
+ *
+ * Units: the c = n - 2 columns strictly between [CLS] and the last [SEP], in
+ * order, token by token as in T5.  No word alignment is applied, and the inner
+ * [SEP] of a CodeBERT pair row is an ordinary unit that a span may cover or
+ * cross: T5 knows no separator.
+ *
+ * Counts, in double with rint (round half even), the same on host and device:
+ *   c < 2:  N = S = 0  (the row passes unchanged, the target is [SEP] alone)
+ *   else    N = min(max(rint(c * noise_density), 1), c - 1)
+ *           S = min(max(rint(N / mean_span), 1), N, c - N, num_sentinels)
+ * The num_sentinels clip is this library's: it keeps the lengths closed-form
+ * where the Poisson route leaves late runs uncorrupted (a 2048-token row at
+ * 0.15 / 3.0 wants 102 spans, and the BERT vocabulary's default run has 99).
+ * The c - N clip keeps a segmentation possible at densities above one half.
+ *
+ * Segmentation: noise lengths a_1 .. a_S >= 1 with sum N, from S - 1 of the
+ * N - 1 gaps between noise items; the other lengths b_1 .. b_S >= 1 with sum
+ * c - N, from S - 1 of the c - N - 1 gaps likewise (gap g lies behind item g of
+ * its kind, from 0).  The chosen gaps of set t are the K = S - 1 gaps with the
+ * smallest keys
+ *   key_t(g) = (splitmix64(k_t + mask_idx(r, g)) & ~0xFFFFF) | g
+ *   k_t      = splitmix64(mask_key(seed, counter) ^ C_t)
+ *   C_noise  = 0x5345474E4F495345, C_plain = 0x534547504C41494E
+ * with mask_key and mask_idx as in lddl_mask_tokens.  This is the rank key of
+ * lddl_set_mask_budget, so keys are unique and the choice is a uniform
+ * K-subset.  The interior reads b_1 a_1 b_2 a_2 ... b_S a_S: its first token is
+ * never noise and its last one always is, as in T5.  selected(j) = column j lies
+ * in some a_k.
+ *
+ * Outputs: the k-th noise span is run k of the definition above; open, ord,
+ * encoder and target are as there, and corrupt = selected, since
+ * ord < S <= num_sentinels.  Hence
+ *   e_r = n - N + S   and   t_r = N + S + 1,   both at most n.
+ * tests/segment_model.py is this in numpy.
+ *
+ * lddl_corrupt_exact_lengths: e_r, t_r, N and S of a row of n tokens.  No ctx,
+ * no GPU.  LDDL_EINVAL (n < 2, num_sentinels < 1, a refused law, null
+ * pointers), LDDL_ECAPACITY (n > 2048).
+ *
+ * Law, LDDL_EINVAL unless both hold: 0 < noise_density < 1; mean_span finite
+ * and >= 1.
+ *
+ * The three row calls take the arguments of the three lddl_collate_corrupt_rows*
+ * calls with (noise_density, mean_span) in place of (max_span, poisson_lambda,
+ * mask_ratio), and return their errors.  The offsets call performs no
+ * selection: it opens every row for its length and writes the cumulative closed
+ * form.  The fill checks both offset pairs against the capacities and the
+ * closed form before it selects, and against its walk's own counts before it
+ * stores. */
+int lddl_corrupt_exact_lengths(int32_t n, double noise_density, double mean_span, int32_t num_sentinels,
+                               int32_t *out_enc, int32_t *out_dec, int32_t *out_noise, int32_t *out_spans);
+
+int lddl_collate_corrupt_exact_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                                    const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                                    const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                    int64_t seq_len, int64_t ignore_index, double noise_density, double mean_span,
+                                    int32_t sentinel_base, int32_t num_sentinels, uint64_t seed, uint64_t counter,
+                                    int64_t *d_input_ids, int64_t *d_attention_mask, int64_t *d_decoder_input_ids,
+                                    int64_t *d_labels, int32_t *d_enc_len, int32_t *d_dec_len, void *hip_stream);
+
+int lddl_collate_corrupt_exact_rows_cu_seqlens(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                               const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                               const uint8_t *d_flags, const int64_t *d_rows, int64_t row0,
+                                               int64_t n_rows, int64_t n_total, double noise_density, double mean_span,
+                                               int32_t sentinel_base, int32_t num_sentinels, uint64_t seed,
+                                               uint64_t counter, int32_t *d_cu_seqlens, int32_t *d_decoder_cu_seqlens,
+                                               int64_t out_totals[2], int64_t out_max_seqlens[2], void *hip_stream);
+
+int lddl_collate_corrupt_exact_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                             const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                             const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                             int64_t n_total, const int32_t *d_cu_seqlens,
+                                             const int32_t *d_decoder_cu_seqlens, int64_t total, int64_t decoder_total,
+                                             int64_t ignore_index, double noise_density, double mean_span,
+                                             int32_t sentinel_base, int32_t num_sentinels, uint64_t seed,
+                                             uint64_t counter, int64_t *d_input_ids, int64_t *d_position_ids,
+                                             int64_t *d_decoder_input_ids, int64_t *d_decoder_position_ids,
+                                             int64_t *d_labels, void *hip_stream);
+
 /* ---- compact MLM targets ----------------------------------------------------
  * The masked positions of a batch and their labels, in order: what a trainer
  * gathers the hidden states at before the LM head, so that the vocabulary

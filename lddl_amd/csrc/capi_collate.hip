@@ -627,9 +627,14 @@ extern "C" int lddl_collate_code_rows_fixed(lddl_ctx* c, const uint16_t* d_ids, 
 // The three lddl_collate_corrupt_rows* calls are the same three bodies (infill_rows, infill_cu_seqlens,
 // infill_unpadded below) with a Sentinels: its range is checked here, and the launch is collate_corrupt.hip's over
 // the same params and the same workspace words.  X NULL: text infilling.
+//
+// The three lddl_collate_corrupt_exact_rows* calls are those bodies again with `exact` set: the law is the pair
+// (noise_density, mean_span), checked here in place of lddl_infill_params, and the launch is collate_segment.hip's.
 struct Sentinels {
   int32_t base, count;
   int32_t* d_dec_len;  // the padded call's second length output
+  bool exact;          // T5's exact-count segmentation under the pair below; the Poisson law's arguments are not read
+  double noise_density, mean_span;
 };
 
 static int check_sentinels(const lddl_ctx* c, const Sentinels& X) {
@@ -646,6 +651,31 @@ static CollateCorruptParams corrupt_params(const CollateInfillParams& I, const S
   return CollateCorruptParams{I, X.base, X.count, X.d_dec_len};
 }
 
+static CollateSegmentParams segment_params(const CollateInfillParams& I, const Sentinels& X) {
+  return CollateSegmentParams{corrupt_params(I, X), X.noise_density, X.mean_span};
+}
+
+static int check_exact_law(double noise_density, double mean_span) {
+  if (!(noise_density > 0.0 && noise_density < 1.0)) return set_err(LDDL_EINVAL, "noise_density not in (0, 1)");
+  if (!(mean_span >= 1.0) || !std::isfinite(mean_span)) return set_err(LDDL_EINVAL, "mean_span not finite and >= 1");
+  return 0;
+}
+
+extern "C" int lddl_corrupt_exact_lengths(int32_t n, double noise_density, double mean_span, int32_t num_sentinels,
+                                          int32_t* out_enc, int32_t* out_dec, int32_t* out_noise, int32_t* out_spans) {
+  if (!out_enc || !out_dec || !out_noise || !out_spans) return set_err(LDDL_EINVAL, "null output pointer");
+  if (n < 2) return set_err(LDDL_EINVAL, "n %d: a row has [CLS] and [SEP] at least", n);
+  if (n > COLLATE_MAX_LEN) return set_err(LDDL_ECAPACITY, "n %d is more than %d tokens", n, COLLATE_MAX_LEN);
+  if (num_sentinels < 1) return set_err(LDDL_EINVAL, "num_sentinels %d: one sentinel at least", num_sentinels);
+  if (int rc = check_exact_law(noise_density, mean_span)) return rc;
+  const SegmentCounts k = segment_counts(n, noise_density, mean_span, num_sentinels);
+  *out_enc = n - k.N + k.S;
+  *out_dec = k.N + k.S + 1;
+  *out_noise = k.N;
+  *out_spans = k.S;
+  return 0;
+}
+
 static int infill_common(lddl_ctx* c, const Sentinels* X, int labels, const uint16_t* d_ids, const int64_t* d_src0,
                          const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
                          const uint8_t* d_flags, const int64_t* d_rows,
@@ -659,9 +689,13 @@ static int infill_common(lddl_ctx* c, const Sentinels* X, int labels, const uint
   if (labels && (ignore_index < INT32_MIN || ignore_index > INT32_MAX)) return set_err(LDDL_EINVAL, "ignore_index out of int32");
   CollateRowsParams& P = I->R;
   int rc;
-  if ((rc = lddl_infill_params(max_span, poisson_lambda, mask_ratio, &P.span.q, P.span.cdf))) return rc;
+  if (X && X->exact) {  // P.span stays off: the segment kernels read the pair
+    if ((rc = check_exact_law(X->noise_density, X->mean_span))) return rc;
+  } else {
+    if ((rc = lddl_infill_params(max_span, poisson_lambda, mask_ratio, &P.span.q, P.span.cdf))) return rc;
+    P.span.L = max_span;
+  }
   if (X && (rc = check_sentinels(c, *X))) return rc;
-  P.span.L = max_span;
   collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   P.ids = d_ids;
   P.src0 = d_src0;
@@ -703,7 +737,9 @@ static int infill_rows(lddl_ctx* c, const Sentinels* X, const uint16_t* d_ids, c
   I.enc_len = d_enc_len;
   uint32_t e;
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(X ? launch_corrupt_rows(corrupt_params(I, *X), c->n_cu, st) : launch_infill_rows(I, c->n_cu, st));
+  HIP_TRY(!X         ? launch_infill_rows(I, c->n_cu, st)
+          : X->exact ? launch_segment_rows(segment_params(I, *X), c->n_cu, st)
+                     : launch_corrupt_rows(corrupt_params(I, *X), c->n_cu, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   return e ? collate_rows_error(e, seq_len) : 0;
 }
@@ -760,7 +796,9 @@ static int infill_cu_seqlens(lddl_ctx* c, const Sentinels* X, const uint16_t* d_
   HIP_TRY(hipMemsetAsync(meta, 0, 24, st));
   HIP_TRY(hipMemsetAsync(I.chunk_sum, 0, 8 * (size_t)I.n_chunks, st));
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(X ? launch_corrupt_cu_seqlens(corrupt_params(I, *X), c->n_cu, st) : launch_infill_cu_seqlens(I, c->n_cu, st));
+  HIP_TRY(!X         ? launch_infill_cu_seqlens(I, c->n_cu, st)
+          : X->exact ? launch_segment_cu_seqlens(segment_params(I, *X), st)
+                     : launch_corrupt_cu_seqlens(corrupt_params(I, *X), c->n_cu, st));
   HIP_TRY(fetch_word(c, HW_NTOK, meta, 24, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   if (e) return collate_unpadded_error(e);
@@ -833,7 +871,9 @@ static int infill_unpadded(lddl_ctx* c, const Sentinels* X, const uint16_t* d_id
   I.total_dec = decoder_total;
   uint32_t e;
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(X ? launch_corrupt_unpadded(corrupt_params(I, *X), c->n_cu, st) : launch_infill_unpadded(I, c->n_cu, st));
+  HIP_TRY(!X         ? launch_infill_unpadded(I, c->n_cu, st)
+          : X->exact ? launch_segment_unpadded(segment_params(I, *X), c->n_cu, st)
+                     : launch_corrupt_unpadded(corrupt_params(I, *X), c->n_cu, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   return e ? collate_unpadded_error(e) : 0;
 }
@@ -870,6 +910,53 @@ extern "C" int lddl_collate_corrupt_rows_unpadded(lddl_ctx* c, const uint16_t* d
                          d_cu_seqlens, d_decoder_cu_seqlens, total, decoder_total, ignore_index, max_span, poisson_lambda,
                          mask_ratio, seed, counter, d_input_ids, d_position_ids, d_decoder_input_ids,
                          d_decoder_position_ids, d_labels, hip_stream);
+}
+
+// T5's exact-count segmentation: the corrupt calls with (noise_density, mean_span) in place of the Poisson law
+extern "C" int lddl_collate_corrupt_exact_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                               const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                               const uint8_t* d_flags, const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                               int64_t n_total, int64_t seq_len, int64_t ignore_index,
+                                               double noise_density, double mean_span, int32_t sentinel_base,
+                                               int32_t num_sentinels, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                               int64_t* d_attention_mask, int64_t* d_decoder_input_ids, int64_t* d_labels,
+                                               int32_t* d_enc_len, int32_t* d_dec_len, void* hip_stream) {
+  const Sentinels X{sentinel_base, num_sentinels, d_dec_len, true, noise_density, mean_span};
+  return infill_rows(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, seq_len,
+                     ignore_index, 0, 0.0, 0.0, seed, counter, d_input_ids, d_attention_mask, d_decoder_input_ids,
+                     d_labels, d_enc_len, hip_stream);
+}
+
+extern "C" int lddl_collate_corrupt_exact_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                          const int64_t* d_src1, const uint16_t* d_len0,
+                                                          const uint16_t* d_len1, const uint8_t* d_flags,
+                                                          const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                                          int64_t n_total, double noise_density, double mean_span,
+                                                          int32_t sentinel_base, int32_t num_sentinels, uint64_t seed,
+                                                          uint64_t counter, int32_t* d_cu_seqlens,
+                                                          int32_t* d_decoder_cu_seqlens, int64_t out_totals[2],
+                                                          int64_t out_max_seqlens[2], void* hip_stream) {
+  const Sentinels X{sentinel_base, num_sentinels, nullptr, true, noise_density, mean_span};
+  return infill_cu_seqlens(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, 0, 0.0,
+                           0.0, seed, counter, d_cu_seqlens, d_decoder_cu_seqlens, out_totals, out_max_seqlens, hip_stream);
+}
+
+extern "C" int lddl_collate_corrupt_exact_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                        const int64_t* d_src1, const uint16_t* d_len0,
+                                                        const uint16_t* d_len1, const uint8_t* d_flags,
+                                                        const int64_t* d_rows, int64_t row0, int64_t n_rows,
+                                                        int64_t n_total, const int32_t* d_cu_seqlens,
+                                                        const int32_t* d_decoder_cu_seqlens, int64_t total,
+                                                        int64_t decoder_total, int64_t ignore_index, double noise_density,
+                                                        double mean_span, int32_t sentinel_base, int32_t num_sentinels,
+                                                        uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                                        int64_t* d_position_ids, int64_t* d_decoder_input_ids,
+                                                        int64_t* d_decoder_position_ids, int64_t* d_labels,
+                                                        void* hip_stream) {
+  const Sentinels X{sentinel_base, num_sentinels, nullptr, true, noise_density, mean_span};
+  return infill_unpadded(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                         d_cu_seqlens, d_decoder_cu_seqlens, total, decoder_total, ignore_index, 0, 0.0, 0.0, seed, counter,
+                         d_input_ids, d_position_ids, d_decoder_input_ids, d_decoder_position_ids, d_labels, hip_stream);
 }
 
 // ------------------------------------------------------ compact MLM targets --

@@ -94,16 +94,16 @@ enum CtxWs {
   CW_SHARED_BSUM,  // tokenize: chunk_fill + chunk_ctr; lddl_render_strings / _npy / _masked: block sums of the lens scan;
                    // lddl_collate_rows_cu_seqlens / lddl_rows_from_strings_len: chunk sums of their scans;
                    // lddl_mlm_targets: M, its error word, then the chunk sums of its scan (one memset);
-                   // lddl_collate_infill_rows_cu_seqlens / lddl_collate_corrupt_rows_cu_seqlens: the chunk sums of their two scans
+                   // lddl_collate_infill_rows_cu_seqlens / lddl_collate_corrupt[_exact]_rows_cu_seqlens: the chunk sums of their two scans
   CW_SHARED_META,  // tokenize: smeta, per sentence; lddl_collate[_rows]_seq_len: max_len;
                    // lddl_collate_rows_cu_seqlens: total, max_len; lddl_rows_from_strings_len: its three totals;
                    // lddl_collate_rows_fixed: total, its error word (one memset);
-                   // lddl_collate_infill_rows_cu_seqlens / lddl_collate_corrupt_rows_cu_seqlens: both totals, both max lengths
+                   // lddl_collate_infill_rows_cu_seqlens / lddl_collate_corrupt[_exact]_rows_cu_seqlens: both totals, both max lengths
                    // (one memset)
                    // the lddl_bart_* calls use the three too: ROWS = chunks per document (plan_len) / bytes per chunk
                    // (plan), BSUM = block sums of their scans, META = {bytes total, refused chunk, error word}
   CW_COLLATE_ERR,  // lddl_collate_bert / lddl_collate_rows[_seq_len | _cu_seqlens | _unpadded] / lddl_rows_from_strings[_len] /
-                   // lddl_collate_infill_rows[_cu_seqlens | _unpadded] / lddl_collate_corrupt_rows[_cu_seqlens | _unpadded]:
+                   // lddl_collate_infill_rows[_cu_seqlens | _unpadded] / lddl_collate_corrupt[_exact]_rows[_cu_seqlens | _unpadded]:
                    // the error word
   CW_SENT_SPEC,    // per sentence: holds [CLS] / [SEP]; written by lddl_tokenize (lddl_set_special_flags),
                    // read by the next masked lddl_pack_bert over the same buffers (pack_common)
@@ -131,7 +131,7 @@ enum HostWord {
   HW_NPAIRS,        // lddl_pack_bert / _codebert: the rows of the pack
   HW_BART_LO = HW_NPAIRS,  // the same word; lddl_bart_plan_len: the chunks; lddl_bart_render: chunk_off[c0]
   HW_NTOK,          // lddl_pack_bert / _codebert: their tokens; lddl_rows_from_strings_len: the table's ids;
-                    // lddl_collate_infill_rows_cu_seqlens / lddl_collate_corrupt_rows_cu_seqlens: the encoder stream's tokens, the decoder's in HW_PACK_ERR and both
+                    // lddl_collate_infill_rows_cu_seqlens / lddl_collate_corrupt[_exact]_rows_cu_seqlens: the encoder stream's tokens, the decoder's in HW_PACK_ERR and both
                     // max lengths (int32 each) in HW_NMASK (one 24-byte copy)
   HW_BART_HI = HW_NTOK,    // the same word; lddl_bart_plan_len: the chunks' bytes; lddl_bart_render: chunk_off[c0 + n],
                            // then the lowest refused chunk

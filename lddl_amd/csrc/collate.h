@@ -2,6 +2,7 @@
 // lddl_collate_seq_len / lddl_collate_bert / lddl_mask_tokens).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 namespace lddl {
@@ -182,6 +183,31 @@ struct CollateCorruptParams {
   int32_t* dec_len;                      // padded: [n_rows] t_r
 };
 
+// lddl_collate_corrupt_exact_rows[_cu_seqlens | _unpadded] (collate_segment.hip): span corruption under T5's
+// exact-count segmentation.  C is read as the corrupt kernels read it, without R.cont and R.span: the units are
+// tokens and the law is the pair below.
+struct CollateSegmentParams {
+  CollateCorruptParams C;
+  double noise_density, mean_span;  // checked by the host: in (0, 1), and finite and >= 1
+};
+
+// The counts of a row of n columns under that law (include/lddl_amd.h defines them): N noise tokens in S spans
+// among the c = n - 2 interior tokens.  In double with rint (round half even); one text for the host
+// (lddl_corrupt_exact_lengths) and the device, so that both give the same integers.  e_r = n - N + S and
+// t_r = N + S + 1.
+struct SegmentCounts {
+  int32_t N, S;
+};
+__host__ __device__ inline SegmentCounts segment_counts(int32_t n, double noise_density, double mean_span,
+                                                        int32_t num_sentinels) {
+  const int32_t c = n - 2;
+  if (c < 2) return {0, 0};
+  const double cd = (double)c;  // < 2^31: exact, as every count below
+  const double N = fmin(fmax(rint(cd * noise_density), 1.0), cd - 1.0);
+  const double S = fmin(fmin(fmax(rint(N / mean_span), 1.0), N), fmin(cd - N, (double)num_sentinels));
+  return {(int32_t)N, (int32_t)S};
+}
+
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
 // lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
@@ -278,6 +304,10 @@ hipError_t launch_infill_scan(const CollateInfillParams& P, hipStream_t s);
 hipError_t launch_corrupt_rows(const CollateCorruptParams& P, int n_cu, hipStream_t s);
 hipError_t launch_corrupt_cu_seqlens(const CollateCorruptParams& P, int n_cu, hipStream_t s);
 hipError_t launch_corrupt_unpadded(const CollateCorruptParams& P, int n_cu, hipStream_t s);
+// (the offsets launch holds no selection: the closed-form lengths, then launch_infill_scan)
+hipError_t launch_segment_rows(const CollateSegmentParams& P, int n_cu, hipStream_t s);
+hipError_t launch_segment_cu_seqlens(const CollateSegmentParams& P, hipStream_t s);
+hipError_t launch_segment_unpadded(const CollateSegmentParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 // (a CodeBERT shard when P.num_tokens is set)

@@ -41,12 +41,9 @@
 namespace lddl {
 namespace {
 
-struct CorruptLen {
-  int32_t e, t;  // wave-uniform
-};
-
 // The walk of open batch row r by its wave.  With STAGE the encoder's tokens are left in enc[0, e) and the target
-// in tgt[0, t).  e <= n and t <= n: the caller's bound on n is the bound on what is written.
+// in tgt[0, t).  e <= n and t <= n: the caller's bound on n is the bound on what is written.  The placement of a
+// step is corrupt_step (collate_tokens.h), shared with collate_segment.hip.
 template <bool STAGE>
 __device__ __forceinline__ CorruptLen corrupt_row(const CollateCorruptParams& P, const OpenRow& R, int64_t r,
                                                   uint16_t* enc, uint16_t* tgt) {
@@ -54,44 +51,16 @@ __device__ __forceinline__ CorruptLen corrupt_row(const CollateCorruptParams& P,
   const int lane = threadIdx.x & 63;
   const int32_t n = R.L.n;
   SpanCarry carry;
-  int32_t e = 0, t = 0, runs = 0;  // runs: opened in the steps before, corrupted or not
-  uint64_t last = 0;               // the last column of the step before is selected
+  CorruptWalk w;
   for (int32_t base = 0; base < n; base += 64) {
     const int32_t j = base + lane;
     const WordColumn c = word_column(C, R, j, j < n, false);
     const bool st[1] = {c.start}, sp[1] = {c.special};
     bool sel[1];  // false on a special column and behind the row
     span_select<1>(C.span, C.seed, C.counter, r, base, st, sp, carry, sel);
-    const uint64_t ms = __ballot(sel[0]);
-    const uint64_t mo = ms & ~(ms << 1 | last);
-    const bool open = lane_in(mo);
-    const int32_t ord = runs + bits_below(mo) + (open ? 1 : 0) - 1;
-    const bool corrupt = sel[0] && ord < P.num_sentinels;
-    const uint64_t mc = __ballot(corrupt), mco = mc & mo;
-    const bool emit = j < n && (!corrupt || open);
-    const uint64_t me = __ballot(emit);
-    if (STAGE) {
-      const uint16_t sentinel = (uint16_t)(P.sentinel_base + ord);
-      if (emit) enc[e + bits_below(me)] = corrupt ? sentinel : (uint16_t)c.id;
-      if (corrupt) {
-        const int32_t place = t + bits_below(mc) + bits_below(mco) + (open ? 1 : 0);
-        if (open) tgt[place - 1] = sentinel;
-        tgt[place] = (uint16_t)c.id;
-      }
-    }
-    e += (int32_t)__popcll(me);
-    t += (int32_t)__popcll(mc) + (int32_t)__popcll(mco);
-    runs += (int32_t)__popcll(mo);
-    last = ms >> 63;
+    corrupt_step<STAGE>(P, __ballot(sel[0]), sel[0], j < n, (uint16_t)c.id, w, enc, tgt);
   }
-  if (STAGE && lane == 0) tgt[t] = (uint16_t)C.sep;  // t <= n - 1 here
-  return {e, t + 1};
-}
-
-// the decoder's planes of target token j < t out of the staged target: decoder_input_ids, labels
-__device__ __forceinline__ void decoder_token(const uint16_t* tgt, int32_t cls, int32_t j, int64_t& in, int64_t& lab) {
-  in = j ? (int64_t)tgt[j - 1] : (int64_t)cls;
-  lab = tgt[j];
+  return corrupt_finish<STAGE>(C.sep, w, tgt);
 }
 
 // ------------------------------------------------------------- padded batch --
@@ -158,11 +127,6 @@ __global__ __launch_bounds__(256) void corrupt_count_kernel(CollateCorruptParams
       }
     }
   }
-}
-
-// whether [c0, c1) can be a row of at most n tokens inside a stream of `total`
-__device__ __forceinline__ bool offsets_ok(int64_t c0, int64_t c1, int32_t n, int64_t total) {
-  return c0 >= 0 && c1 >= c0 && c1 - c0 <= n && c1 <= total;
 }
 
 __global__ __launch_bounds__(256) void corrupt_unpadded_kernel(CollateCorruptParams P) {

@@ -1,11 +1,13 @@
-// What the collates that change a row's length share on the device (collate_infill.hip, collate_corrupt.hip): the
-// id of a column of an open row, and the store of a row's tokens into int64 planes by one wave.
+// What the collates that change a row's length share on the device (collate_infill.hip, collate_corrupt.hip,
+// collate_segment.hip): the id of a column of an open row, the store of a row's tokens into int64 planes by one wave,
+// and span corruption's placement of a step's columns into both of its streams.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "collate.h"
 #include "collate_row.h"
+#include "wave.h"
 
 namespace lddl {
 
@@ -52,6 +54,65 @@ __device__ __forceinline__ bool planes_aligned(int64_t* const (&out)[N]) {
 #pragma unroll
   for (int t = 0; t < N; ++t) x |= (uintptr_t)out[t];
   return (x & 15) == 0;
+}
+
+// ------------------------------------------------ span corruption's placement --
+// What both selections of span corruption (collate_corrupt.hip: runs of whole words under the Poisson law;
+// collate_segment.hip: T5's exact-count segmentation) drive: given which columns of a 64-column step are selected,
+// the run ordinals, the sentinel cap and the places of both streams, as the head of collate_corrupt.hip tells.
+struct CorruptLen {
+  int32_t e, t;  // wave-uniform
+};
+
+// what a row carries from step to step, wave-uniform
+struct CorruptWalk {
+  int32_t e = 0, t = 0, runs = 0;  // runs: opened in the steps before, corrupted or not
+  uint64_t last = 0;               // the last column of the step before is selected
+};
+
+// One step of the walk.  ms: the step's selected columns, sel: this lane's bit of it; valid: the lane's column is a
+// column of the row, id: its id.  With STAGE the tokens go to enc[w.e ..) and tgt[w.t ..).
+template <bool STAGE>
+__device__ __forceinline__ void corrupt_step(const CollateCorruptParams& P, uint64_t ms, bool sel, bool valid,
+                                             uint16_t id, CorruptWalk& w, uint16_t* enc, uint16_t* tgt) {
+  const uint64_t mo = ms & ~(ms << 1 | w.last);
+  const bool open = lane_in(mo);
+  const int32_t ord = w.runs + bits_below(mo) + (open ? 1 : 0) - 1;
+  const bool corrupt = sel && ord < P.num_sentinels;
+  const uint64_t mc = __ballot(corrupt), mco = mc & mo;
+  const bool emit = valid && (!corrupt || open);
+  const uint64_t me = __ballot(emit);
+  if (STAGE) {
+    const uint16_t sentinel = (uint16_t)(P.sentinel_base + ord);
+    if (emit) enc[w.e + bits_below(me)] = corrupt ? sentinel : id;
+    if (corrupt) {
+      const int32_t place = w.t + bits_below(mc) + bits_below(mco) + (open ? 1 : 0);
+      if (open) tgt[place - 1] = sentinel;
+      tgt[place] = id;
+    }
+  }
+  w.e += (int32_t)__popcll(me);
+  w.t += (int32_t)__popcll(mc) + (int32_t)__popcll(mco);
+  w.runs += (int32_t)__popcll(mo);
+  w.last = ms >> 63;
+}
+
+// the [SEP] that ends the target, and both lengths
+template <bool STAGE>
+__device__ __forceinline__ CorruptLen corrupt_finish(int32_t sep, const CorruptWalk& w, uint16_t* tgt) {
+  if (STAGE && (threadIdx.x & 63) == 0) tgt[w.t] = (uint16_t)sep;  // t <= n - 1 here
+  return {w.e, w.t + 1};
+}
+
+// the decoder's planes of target token j < t out of the staged target: decoder_input_ids, labels
+__device__ __forceinline__ void decoder_token(const uint16_t* tgt, int32_t cls, int32_t j, int64_t& in, int64_t& lab) {
+  in = j ? (int64_t)tgt[j - 1] : (int64_t)cls;
+  lab = tgt[j];
+}
+
+// whether [c0, c1) can be a row of at most n tokens inside a stream of `total`
+__device__ __forceinline__ bool offsets_ok(int64_t c0, int64_t c1, int32_t n, int64_t total) {
+  return c0 >= 0 && c1 >= c0 && c1 - c0 <= n && c1 <= total;
 }
 
 }  // namespace lddl

@@ -165,6 +165,20 @@ def default_sentinels(vocab):
   return base, count
 
 
+def span_corruption_lengths(n, noise_density=0.15, mean_span=3.0, num_sentinels=99):
+  """(encoder length, decoder length, noise tokens, noise spans) of a row of n
+  tokens ([CLS] and the last [SEP] included) under
+  ``collate_span_corruption_exact`` (lddl_corrupt_exact_lengths): functions of
+  the row's length alone, which is what sizes both sides of a step before any
+  batch is drawn.  ``num_sentinels``: the count of the sentinels that the
+  collate is given, which caps the spans; the default is the BERT vocabulary's
+  [unused0] .. [unused98] run.  Host only."""
+  out = [ctypes.c_int32() for _ in range(4)]
+  _lib.check(_lib.lib().lddl_corrupt_exact_lengths(int(n), float(noise_density), float(mean_span), int(num_sentinels),
+                                                   *[ctypes.byref(x) for x in out]))
+  return tuple(x.value for x in out)
+
+
 def _check(rc):
   """_lib.check with LDDL_EINDEX (-7) as the IndexError the reference raises for a position out of range"""
   if rc == -7:
@@ -824,18 +838,23 @@ class CodeCollate(_RowCollate):
     [max_seqs + 1], num_tokens / num_rows / num_seqs and ``status``."""
     return self._collate(True, res, rows, row0, n_rows, mode, (max_tokens, max_seqs, max_seqlen))
 
-  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, sentinels=None):
-    """The body of the two denoising objectives: text infilling, or, with
+  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, sentinels=None, exact=None):
+    """The body of the denoising objectives: text infilling, or, with
     ``sentinels`` = (base, count), span corruption, whose three C calls take the
-    same arguments with the pair behind the law and a second length output."""
+    same arguments with the pair behind the law and a second length output;
+    with ``exact`` = (noise_density, mean_span) as well, its exact-count form,
+    whose calls take that pair for the law."""
     L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
     if sentinels is None:
       name, who, law2 = 'lddl_collate_infill_rows', 'collate_infill', ()
     else:
       name, who, law2 = 'lddl_collate_corrupt_rows', 'collate_span_corruption', (int(sentinels[0]), int(sentinels[1]))
+      if exact is not None:
+        name, who = 'lddl_collate_corrupt_exact_rows', 'collate_span_corruption_exact'
     _, rows, row0, n = self._row_batch(who + '_unpadded' * unpadded, res, rows, row0, n_rows, MODE_DYNAMIC)
     table = (p(res.ids), p(res.src0), p(res.src1), p(res.len0), p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs)
-    law = (int(max_span), float(poisson_lambda), float(mask_ratio)) + law2 + (self.seed, self.counter)
+    law = (int(max_span), float(poisson_lambda), float(mask_ratio)) if exact is None else (float(exact[0]), float(exact[1]))
+    law += law2 + (self.seed, self.counter)
     i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device=self.device)  # noqa: E731
     if unpadded:
       cu = torch.empty((2, n + 1), dtype=torch.int32, device=self.device)
@@ -922,6 +941,33 @@ class CodeCollate(_RowCollate):
     lddl_collate_corrupt_rows_unpadded), under the keys of
     ``collate_infill_unpadded``: both streams' lengths depend on the draw."""
     return self._infill(True, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, self._sentinels(sentinels))
+
+  def collate_span_corruption_exact(self, res, rows=None, row0=0, n_rows=None, *, noise_density=0.15, mean_span=3.0,
+                                    sentinels=None):
+    """``collate_span_corruption`` under T5's own length law
+    (lddl_collate_corrupt_exact_rows; include/lddl_amd.h defines it): a row of
+    c interior tokens gets exactly N = round(c * ``noise_density``) noise tokens
+    in exactly S = round(N / ``mean_span``) spans, S capped by the sentinel
+    count, and the draw is one uniformly random segmentation with those counts.
+    ``encoder_lengths`` and ``decoder_lengths`` are therefore functions of the
+    row's length alone (``span_corruption_lengths``).  The units are tokens, as
+    in T5: no word alignment, and the inner [SEP] of a pair row is an ordinary
+    token.  Keys, sentinels, draws and the batch counter as
+    ``collate_span_corruption``."""
+    return self._infill(False, res, rows, row0, n_rows, 0.0, 0.0, 0, self._sentinels(sentinels),
+                        (noise_density, mean_span))
+
+  def collate_span_corruption_exact_unpadded(self, res, rows=None, row0=0, n_rows=None, *, noise_density=0.15,
+                                             mean_span=3.0, sentinels=None):
+    """``collate_span_corruption_exact`` at the same seed and counter with the
+    padding of both sides dropped, bit for bit
+    (lddl_collate_corrupt_exact_rows_cu_seqlens +
+    lddl_collate_corrupt_exact_rows_unpadded), under the keys of
+    ``collate_infill_unpadded``.  Both ``cu_seqlens`` are the cumulative
+    ``span_corruption_lengths`` of the rows: no selection is computed for
+    them."""
+    return self._infill(True, res, rows, row0, n_rows, 0.0, 0.0, 0, self._sentinels(sentinels),
+                        (noise_density, mean_span))
 
   def load_rows(self, table, bins=None, part=None, nbins=None):
     """The rows of a CodeBERT shard as a GPU row table, once

@@ -812,8 +812,9 @@ int lddl_infill_params(int32_t max_span, double poisson_lambda, double mask_rati
  *   decoder  decoder_input_ids[r, j] = id_j for j in [0, n - 1), then 0
  *   labels   labels[r, j] = id_{j + 1} for j in [0, n - 1), then ignore_index
  *   enc_len[r] = e_r (int32, on the device)
- * There is no random-token replacement and no sentence permutation (rows keep
- * no sentence boundaries).  mask_ratio 0: the encoder input is the row itself;
+ * There is no random-token replacement and no sentence permutation here: both
+ * belong to lddl_collate_denoise_rows below, which takes a full-stop token as
+ * the end of a sentence.  mask_ratio 0: the encoder input is the row itself;
  * mask_ratio 1: every segment becomes one [MASK].  tests/infill_model.py is
  * this in numpy.  hip_stream: the hipStream_t that the three calls queue
  * their work on, as `stream` of the calls above.
@@ -876,6 +877,92 @@ int lddl_collate_infill_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, cons
                                       uint64_t seed, uint64_t counter, int64_t *d_input_ids, int64_t *d_position_ids,
                                       int64_t *d_decoder_input_ids, int64_t *d_decoder_position_ids, int64_t *d_labels,
                                       void *hip_stream);
+
+/* ---- full denoising collate: sentence permutation and random replacement ------
+ * BART's published pre-training recipe is text infilling together with
+ * sentence permutation (fairseq's denoising task: permute_sentences = 1.0,
+ * random_ratio = 0.1).  The three calls below are the three calls above with
+ * three arguments behind mask_ratio; rows, law, outputs, counters and every
+ * error rule are text infilling's.  A sentence ends at a full-stop token, as in
+ * fairseq's DenoisingDataset.permute_sentences; over a WordPiece vocabulary `.`
+ * is a token of its own.
+ *
+ * For batch row r with n columns, each segment on its own: segment g = 0 is
+ * what lies between [CLS] and the first [SEP], segment g = 1 what lies between
+ * the inner [SEP] of a [CLS] doc [SEP] code [SEP] row and the last; a segment
+ * occupies columns [lo, hi); [CLS] and every [SEP] stay where they are.
+ *   stop(j) = id_j == full_stop_id
+ *   end(j)  = (stop(j) and !(j > lo and stop(j - 1))) or j == hi - 1
+ * The sentences 0 .. m - 1 of a segment are the maximal ranges that end at an
+ * end column: a run `...` ends one sentence at its first stop and the other
+ * stops open the next one; an empty segment has none; a segment of c tokens
+ * has at most c / 2 + 1.
+ *   K = min(m, ceil(m * permute_ratio)), in double; K < 2: nothing moves
+ *   k, i(row, col) and sm as in the dynamic-masking definition above
+ *   kp     = sm(k ^ 0x5045524D53454E54)
+ *   h32(i) = sm(kp + i(r, g << 11 | i)) >> 32
+ *   key(i) = h32(i) << 32 | i                  (unique within the segment)
+ *   rank(i) = #{ t : key(t) < key(i) }
+ * The chosen sentences are those of rank < K, at positions c_0 < ... < c_{K-1}.
+ * In the permuted segment position c_k holds the chosen sentence of rank k and
+ * every other position keeps its sentence; the sentences follow each other
+ * from lo in that order.  One set of independent unique keys gives a uniform
+ * K-subset and, independently of it, a uniform order within it: fairseq's
+ * ordering[substitutions] = substitutions[randperm(K)].
+ *
+ * Text infilling: id', start' and selected' are id, start and selected of the
+ * text-infilling definition evaluated on the permuted row, under (q, cdf, L) of
+ * lddl_infill_params, with row = r and col = the permuted column; emit, pos and
+ * the encoder's planes as there.
+ *
+ * Random replacement: an emitted [MASK] that opens at permuted column j is
+ *   kr = sm(k ^ 0x52414E44544F4B4E), h = sm(kr + i(r, j))
+ *   (h & 0xFFFFFFFF) * n_vocab >> 32   iff unit53(h) < random_ratio
+ * (mask_selected's mapping of a random id), decided once per collapsed run as
+ * fairseq decides once per span.
+ *
+ * Decoder: decoder_input_ids and labels are the row as the table holds it,
+ * exactly text infilling's, so the decoder's lengths are n_r - 1.
+ * permute_ratio 0 and random_ratio 0: lddl_collate_infill_rows bit for bit.
+ * Out of scope: zero-length insertions, fairseq's replace_length 0 and -1,
+ * document rotation.  tests/denoise_model.py is this in numpy.
+ *
+ * Errors: those of the text-infilling call of the same suffix, and LDDL_EINVAL
+ * for a permute_ratio or random_ratio outside [0, 1] or not finite, a
+ * full_stop_id outside [0, 65535], a vocabulary of more than 65536 entries. */
+int lddl_collate_denoise_rows(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0, const int64_t *d_src1,
+                              const uint16_t *d_len0, const uint16_t *d_len1, const uint8_t *d_flags,
+                              const int64_t *d_rows, int64_t row0, int64_t n_rows, int64_t n_total, int64_t seq_len,
+                              int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio,
+                              double permute_ratio, double random_ratio, int32_t full_stop_id, uint64_t seed,
+                              uint64_t counter, int64_t *d_input_ids, int64_t *d_attention_mask,
+                              int64_t *d_decoder_input_ids, int64_t *d_labels, int32_t *d_enc_len, void *hip_stream);
+
+/* Both offset arrays of the padding-free batch, as
+ * lddl_collate_infill_rows_cu_seqlens: the permutation is computed too, because
+ * the selection depends on the permuted row. */
+int lddl_collate_denoise_rows_cu_seqlens(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                         const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                         const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                         int64_t n_total, int32_t max_span, double poisson_lambda, double mask_ratio,
+                                         double permute_ratio, double random_ratio, int32_t full_stop_id,
+                                         uint64_t seed, uint64_t counter, int32_t *d_cu_seqlens,
+                                         int32_t *d_decoder_cu_seqlens, int64_t out_totals[2],
+                                         int64_t out_max_seqlens[2], void *hip_stream);
+
+/* The fill of both streams, as lddl_collate_infill_rows_unpadded: bit for bit
+ * lddl_collate_denoise_rows without its padding; both offset arrays are
+ * checked, not trusted. */
+int lddl_collate_denoise_rows_unpadded(lddl_ctx *ctx, const uint16_t *d_ids, const int64_t *d_src0,
+                                       const int64_t *d_src1, const uint16_t *d_len0, const uint16_t *d_len1,
+                                       const uint8_t *d_flags, const int64_t *d_rows, int64_t row0, int64_t n_rows,
+                                       int64_t n_total, const int32_t *d_cu_seqlens,
+                                       const int32_t *d_decoder_cu_seqlens, int64_t total, int64_t decoder_total,
+                                       int64_t ignore_index, int32_t max_span, double poisson_lambda, double mask_ratio,
+                                       double permute_ratio, double random_ratio, int32_t full_stop_id, uint64_t seed,
+                                       uint64_t counter, int64_t *d_input_ids, int64_t *d_position_ids,
+                                       int64_t *d_decoder_input_ids, int64_t *d_decoder_position_ids, int64_t *d_labels,
+                                       void *hip_stream);
 
 /* ---- span-corruption collate --------------------------------------------------
  * The other sequence-to-sequence denoising objective: T5's span corruption

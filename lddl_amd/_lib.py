@@ -125,6 +125,15 @@ SIGNATURES = {
     'lddl_collate_corrupt_exact_rows_unpadded': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 2 +
                                                  [c_int64, c_int64, c_int64, c_double, c_double, c_int32, c_int32,
                                                   c_uint64, c_uint64] + [c_void_p] * 6),
+    'lddl_collate_denoise_rows': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] +
+                                  [c_int64, c_int64, c_int32, c_double, c_double, c_double, c_double, c_int32, c_uint64,
+                                   c_uint64] + [c_void_p] * 6),
+    'lddl_collate_denoise_rows_cu_seqlens': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] +
+                                             [c_int32, c_double, c_double, c_double, c_double, c_int32, c_uint64, c_uint64] +
+                                             [c_void_p] * 2 + [ctypes.POINTER(c_int64)] * 2 + [c_void_p]),
+    'lddl_collate_denoise_rows_unpadded': (c_int, [c_void_p] * 8 + [c_int64, c_int64, c_int64] + [c_void_p] * 2 +
+                                           [c_int64, c_int64, c_int64, c_int32, c_double, c_double, c_double, c_double,
+                                            c_int32, c_uint64, c_uint64] + [c_void_p] * 6),
     'lddl_mlm_targets': (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p,
                                  c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     'lddl_code_rows_from_strings_len': (c_int, [c_void_p] * 6 + [c_int64] + [c_void_p] * 5 +

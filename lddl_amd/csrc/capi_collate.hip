@@ -1,5 +1,6 @@
 // C-ABI, host side of the training-time collate (kernels: collate.hip,
 // collate_rows.hip, collate_unpadded.hip, collate_fixed.hip, collate_infill.hip, collate_corrupt.hip,
+// collate_segment.hip, collate_denoise.hip,
 // rows_from_strings.hip, mlm_targets.hip).
 #include "capi_ctx.h"
 
@@ -630,12 +631,41 @@ extern "C" int lddl_collate_code_rows_fixed(lddl_ctx* c, const uint16_t* d_ids, 
 //
 // The three lddl_collate_corrupt_exact_rows* calls are those bodies again with `exact` set: the law is the pair
 // (noise_density, mean_span), checked here in place of lddl_infill_params, and the launch is collate_segment.hip's.
+//
+// The three lddl_collate_denoise_rows* calls are text infilling's bodies with `denoise` set: no sentinels, the two
+// ratios and the full stop checked here, and the launch is collate_denoise.hip's.
 struct Sentinels {
   int32_t base, count;
   int32_t* d_dec_len;  // the padded call's second length output
   bool exact;          // T5's exact-count segmentation under the pair below; the Poisson law's arguments are not read
   double noise_density, mean_span;
+  bool denoise;        // BART's full objective: base .. mean_span are not read
+  double permute_ratio, random_ratio;
+  int32_t full_stop_id;
 };
+
+static Sentinels denoise_args(double permute_ratio, double random_ratio, int32_t full_stop_id) {
+  Sentinels X{};
+  X.denoise = true;
+  X.permute_ratio = permute_ratio;
+  X.random_ratio = random_ratio;
+  X.full_stop_id = full_stop_id;
+  return X;
+}
+
+static CollateDenoiseParams denoise_params(const CollateInfillParams& I, const Sentinels& X) {
+  return CollateDenoiseParams{I, X.permute_ratio, X.random_ratio, X.full_stop_id};
+}
+
+static int check_denoise(const lddl_ctx* c, const Sentinels& X) {
+  if (!(X.permute_ratio >= 0.0 && X.permute_ratio <= 1.0)) return set_err(LDDL_EINVAL, "permute_ratio not in [0, 1]");
+  if (!(X.random_ratio >= 0.0 && X.random_ratio <= 1.0)) return set_err(LDDL_EINVAL, "random_ratio not in [0, 1]");
+  if (X.full_stop_id < 0 || X.full_stop_id > 65535)
+    return set_err(LDDL_EINVAL, "full_stop_id %d not in [0, 65535]", X.full_stop_id);
+  if (c->vocab_size > 65536)
+    return set_err(LDDL_EINVAL, "a vocabulary of %d entries: a random id would not fit 16 bits", c->vocab_size);
+  return 0;
+}
 
 static int check_sentinels(const lddl_ctx* c, const Sentinels& X) {
   if (X.count < 1 || X.base < 0 || (int64_t)X.base + X.count > 65536)
@@ -695,7 +725,7 @@ static int infill_common(lddl_ctx* c, const Sentinels* X, int labels, const uint
     if ((rc = lddl_infill_params(max_span, poisson_lambda, mask_ratio, &P.span.q, P.span.cdf))) return rc;
     P.span.L = max_span;
   }
-  if (X && (rc = check_sentinels(c, *X))) return rc;
+  if (X && (rc = X->denoise ? check_denoise(c, *X) : check_sentinels(c, *X))) return rc;
   collate_rows_index(&P, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total);
   P.ids = d_ids;
   P.src0 = d_src0;
@@ -726,7 +756,8 @@ static int infill_rows(lddl_ctx* c, const Sentinels* X, const uint16_t* d_ids, c
     return rc;
   if (seq_len < 2 || seq_len > COLLATE_MAX_LEN)
     return set_err(LDDL_ECAPACITY, "seq_len %lld not in [2, %d]", (long long)seq_len, COLLATE_MAX_LEN);
-  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_enc_len || (X && !X->d_dec_len))
+  if (!d_input_ids || !d_attention_mask || !d_decoder_input_ids || !d_labels || !d_enc_len ||
+      (X && !X->denoise && !X->d_dec_len))
     return set_err(LDDL_EINVAL, "null pointer");
   hipStream_t st = (hipStream_t)hip_stream;
   I.R.seq_len = (int32_t)seq_len;
@@ -737,9 +768,10 @@ static int infill_rows(lddl_ctx* c, const Sentinels* X, const uint16_t* d_ids, c
   I.enc_len = d_enc_len;
   uint32_t e;
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(!X         ? launch_infill_rows(I, c->n_cu, st)
-          : X->exact ? launch_segment_rows(segment_params(I, *X), c->n_cu, st)
-                     : launch_corrupt_rows(corrupt_params(I, *X), c->n_cu, st));
+  HIP_TRY(!X           ? launch_infill_rows(I, c->n_cu, st)
+          : X->denoise ? launch_denoise_rows(denoise_params(I, *X), c->n_cu, st)
+          : X->exact   ? launch_segment_rows(segment_params(I, *X), c->n_cu, st)
+                       : launch_corrupt_rows(corrupt_params(I, *X), c->n_cu, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   return e ? collate_rows_error(e, seq_len) : 0;
 }
@@ -796,9 +828,10 @@ static int infill_cu_seqlens(lddl_ctx* c, const Sentinels* X, const uint16_t* d_
   HIP_TRY(hipMemsetAsync(meta, 0, 24, st));
   HIP_TRY(hipMemsetAsync(I.chunk_sum, 0, 8 * (size_t)I.n_chunks, st));
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(!X         ? launch_infill_cu_seqlens(I, c->n_cu, st)
-          : X->exact ? launch_segment_cu_seqlens(segment_params(I, *X), st)
-                     : launch_corrupt_cu_seqlens(corrupt_params(I, *X), c->n_cu, st));
+  HIP_TRY(!X           ? launch_infill_cu_seqlens(I, c->n_cu, st)
+          : X->denoise ? launch_denoise_cu_seqlens(denoise_params(I, *X), c->n_cu, st)
+          : X->exact   ? launch_segment_cu_seqlens(segment_params(I, *X), st)
+                       : launch_corrupt_cu_seqlens(corrupt_params(I, *X), c->n_cu, st));
   HIP_TRY(fetch_word(c, HW_NTOK, meta, 24, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   if (e) return collate_unpadded_error(e);
@@ -871,9 +904,10 @@ static int infill_unpadded(lddl_ctx* c, const Sentinels* X, const uint16_t* d_id
   I.total_dec = decoder_total;
   uint32_t e;
   HIP_TRY(hipMemsetAsync(I.R.err, 0, 4, st));
-  HIP_TRY(!X         ? launch_infill_unpadded(I, c->n_cu, st)
-          : X->exact ? launch_segment_unpadded(segment_params(I, *X), c->n_cu, st)
-                     : launch_corrupt_unpadded(corrupt_params(I, *X), c->n_cu, st));
+  HIP_TRY(!X           ? launch_infill_unpadded(I, c->n_cu, st)
+          : X->denoise ? launch_denoise_unpadded(denoise_params(I, *X), c->n_cu, st)
+          : X->exact   ? launch_segment_unpadded(segment_params(I, *X), c->n_cu, st)
+                       : launch_corrupt_unpadded(corrupt_params(I, *X), c->n_cu, st));
   if ((rc = read_err(c, I.R.err, st, &e))) return rc;
   return e ? collate_unpadded_error(e) : 0;
 }
@@ -957,6 +991,54 @@ extern "C" int lddl_collate_corrupt_exact_rows_unpadded(lddl_ctx* c, const uint1
   return infill_unpadded(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
                          d_cu_seqlens, d_decoder_cu_seqlens, total, decoder_total, ignore_index, 0, 0.0, 0.0, seed, counter,
                          d_input_ids, d_position_ids, d_decoder_input_ids, d_decoder_position_ids, d_labels, hip_stream);
+}
+
+// BART's full denoising objective: the infill calls with (permute_ratio, random_ratio, full_stop_id) behind mask_ratio
+extern "C" int lddl_collate_denoise_rows(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0, const int64_t* d_src1,
+                                         const uint16_t* d_len0, const uint16_t* d_len1, const uint8_t* d_flags,
+                                         const int64_t* d_rows, int64_t row0, int64_t n_rows, int64_t n_total,
+                                         int64_t seq_len, int64_t ignore_index, int32_t max_span, double poisson_lambda,
+                                         double mask_ratio, double permute_ratio, double random_ratio,
+                                         int32_t full_stop_id, uint64_t seed, uint64_t counter, int64_t* d_input_ids,
+                                         int64_t* d_attention_mask, int64_t* d_decoder_input_ids, int64_t* d_labels,
+                                         int32_t* d_enc_len, void* hip_stream) {
+  const Sentinels X = denoise_args(permute_ratio, random_ratio, full_stop_id);
+  return infill_rows(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, seq_len,
+                     ignore_index, max_span, poisson_lambda, mask_ratio, seed, counter, d_input_ids, d_attention_mask,
+                     d_decoder_input_ids, d_labels, d_enc_len, hip_stream);
+}
+
+extern "C" int lddl_collate_denoise_rows_cu_seqlens(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                    const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                    const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                    int64_t n_rows, int64_t n_total, int32_t max_span,
+                                                    double poisson_lambda, double mask_ratio, double permute_ratio,
+                                                    double random_ratio, int32_t full_stop_id, uint64_t seed,
+                                                    uint64_t counter, int32_t* d_cu_seqlens,
+                                                    int32_t* d_decoder_cu_seqlens, int64_t out_totals[2],
+                                                    int64_t out_max_seqlens[2], void* hip_stream) {
+  const Sentinels X = denoise_args(permute_ratio, random_ratio, full_stop_id);
+  return infill_cu_seqlens(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total, max_span,
+                           poisson_lambda, mask_ratio, seed, counter, d_cu_seqlens, d_decoder_cu_seqlens, out_totals,
+                           out_max_seqlens, hip_stream);
+}
+
+extern "C" int lddl_collate_denoise_rows_unpadded(lddl_ctx* c, const uint16_t* d_ids, const int64_t* d_src0,
+                                                  const int64_t* d_src1, const uint16_t* d_len0, const uint16_t* d_len1,
+                                                  const uint8_t* d_flags, const int64_t* d_rows, int64_t row0,
+                                                  int64_t n_rows, int64_t n_total, const int32_t* d_cu_seqlens,
+                                                  const int32_t* d_decoder_cu_seqlens, int64_t total,
+                                                  int64_t decoder_total, int64_t ignore_index, int32_t max_span,
+                                                  double poisson_lambda, double mask_ratio, double permute_ratio,
+                                                  double random_ratio, int32_t full_stop_id, uint64_t seed,
+                                                  uint64_t counter, int64_t* d_input_ids, int64_t* d_position_ids,
+                                                  int64_t* d_decoder_input_ids, int64_t* d_decoder_position_ids,
+                                                  int64_t* d_labels, void* hip_stream) {
+  const Sentinels X = denoise_args(permute_ratio, random_ratio, full_stop_id);
+  return infill_unpadded(c, &X, d_ids, d_src0, d_src1, d_len0, d_len1, d_flags, d_rows, row0, n_rows, n_total,
+                         d_cu_seqlens, d_decoder_cu_seqlens, total, decoder_total, ignore_index, max_span, poisson_lambda,
+                         mask_ratio, seed, counter, d_input_ids, d_position_ids, d_decoder_input_ids,
+                         d_decoder_position_ids, d_labels, hip_stream);
 }
 
 // ------------------------------------------------------ compact MLM targets --

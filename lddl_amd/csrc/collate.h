@@ -208,6 +208,22 @@ __host__ __device__ inline SegmentCounts segment_counts(int32_t n, double noise_
   return {(int32_t)N, (int32_t)S};
 }
 
+// lddl_collate_denoise_rows[_cu_seqlens | _unpadded] (collate_denoise.hip): BART's full denoising batches of the
+// same rows: the sentences of every segment are permuted, text infilling runs over the permuted row, and an opened
+// [MASK] may become a random id.  I is read as the infill kernels read it.
+struct CollateDenoiseParams {
+  CollateInfillParams I;
+  double permute_ratio, random_ratio;  // checked by the host: in [0, 1]
+  int32_t full_stop_id;                // checked by the host: in [0, 65535]
+};
+
+// K, the sentences that move, of a segment of m sentences (include/lddl_amd.h defines it): min(m, ceil(m *
+// permute_ratio)) in double; one text for whoever computes it, as segment_counts
+__host__ __device__ inline int32_t denoise_permuted(int32_t m, double permute_ratio) {
+  const double md = (double)m;  // <= 1024: exact
+  return (int32_t)fmin(md, ceil(md * permute_ratio));
+}
+
 // lddl_rows_from_strings_len / lddl_rows_from_strings (rows_from_strings.hip):
 // the string columns of a shard into the row table that lddl_row_spans +
 // lddl_masked_lm_spans leave behind.  mlm_off .. mlm_token are NULL without
@@ -308,6 +324,10 @@ hipError_t launch_corrupt_unpadded(const CollateCorruptParams& P, int n_cu, hipS
 hipError_t launch_segment_rows(const CollateSegmentParams& P, int n_cu, hipStream_t s);
 hipError_t launch_segment_cu_seqlens(const CollateSegmentParams& P, hipStream_t s);
 hipError_t launch_segment_unpadded(const CollateSegmentParams& P, int n_cu, hipStream_t s);
+// (the offsets launch ends with launch_infill_scan)
+hipError_t launch_denoise_rows(const CollateDenoiseParams& P, int n_cu, hipStream_t s);
+hipError_t launch_denoise_cu_seqlens(const CollateDenoiseParams& P, int n_cu, hipStream_t s);
+hipError_t launch_denoise_unpadded(const CollateDenoiseParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_len(const CollateParams& P, int n_cu, hipStream_t s);
 hipError_t launch_collate_fill(const CollateParams& P, int n_cu, hipStream_t s);
 // (a CodeBERT shard when P.num_tokens is set)

@@ -55,30 +55,12 @@
 namespace lddl {
 namespace {
 
-// The walk of open batch row r by its wave: returns e_r (wave-uniform) and, with STAGE, leaves the encoder's tokens
-// in tok[0, e_r).  e_r <= n: the caller's bound on n is the bound on what is written.
+// infill_walk (collate_tokens.h) over the row table itself, every run collapsing to [MASK]
 template <bool STAGE>
 __device__ __forceinline__ int32_t infill_row(const CollateRowsParams& P, const OpenRow& R, int64_t r, uint16_t* tok) {
-  const int lane = threadIdx.x & 63;
-  const int32_t n = R.L.n;
-  SpanCarry carry;
-  int32_t count = 0;
-  uint64_t last = 0;  // the last column of the step before is selected
-  for (int32_t base = 0; base < n; base += 64) {
-    const int32_t j = base + lane;
-    const WordColumn c = word_column(P, R, j, j < n, false);
-    const bool st[1] = {c.start}, sp[1] = {c.special};
-    bool sel[1];  // false on a special column and behind the row
-    span_select<1>(P.span, P.seed, P.counter, r, base, st, sp, carry, sel);
-    const uint64_t ms = __ballot(sel[0]);
-    const bool before = lane_in(ms << 1 | last);  // the column before this one is selected
-    const bool emit = j < n && !(sel[0] && before);
-    const uint64_t me = __ballot(emit);
-    if (STAGE && emit) tok[count + bits_below(me)] = (uint16_t)(sel[0] ? P.mask_id : (int32_t)c.id);
-    count += (int32_t)__popcll(me);
-    last = ms >> 63;
-  }
-  return count;
+  return infill_walk<STAGE>(
+      P, R, r, tok, [&](int32_t k) { return (int32_t)(k <= R.L.a ? R.s0[k] : R.s1[k]); },
+      [&](int32_t) { return P.mask_id; });
 }
 
 // ------------------------------------------------------------- padded batch --

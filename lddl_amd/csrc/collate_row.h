@@ -158,17 +158,24 @@ struct WordColumn {
 };
 
 // valid: j is a column of the batch row (the wide paths compute a neighbour
-// that is not); pad as in row_column
+// that is not); pad as in row_column.  at(k): the token source, the id at column
+// k of a segment (the row table, or a reordered copy of the row: collate_denoise.hip)
+template <class At>
 __device__ __forceinline__ WordColumn word_column(const CollateRowsParams& P, const OpenRow& R, int32_t j, bool valid,
-                                                  bool pad) {
+                                                  bool pad, At at) {
   WordColumn c;
   c.special = !valid || pad || R.L.special(j);
   c.id = 0;
-  if (valid && !pad)
-    c.id = R.L.base_id(j, P.cls, P.sep, [&](int32_t k) { return (int32_t)(k <= R.L.a ? R.s0[k] : R.s1[k]); });
+  if (valid && !pad) c.id = R.L.base_id(j, P.cls, P.sep, at);
   // j - 1 is special exactly where j begins a segment: no column is in front of [CLS]
   c.start = !c.special && (R.L.special(j - 1) || !word_cont(P.cont, P.n_random, c.id));
   return c;
+}
+
+// the columns of the row table itself
+__device__ __forceinline__ WordColumn word_column(const CollateRowsParams& P, const OpenRow& R, int32_t j, bool valid,
+                                                  bool pad) {
+  return word_column(P, R, j, valid, pad, [&](int32_t k) { return (int32_t)(k <= R.L.a ? R.s0[k] : R.s1[k]); });
 }
 
 // the picks of a step of batch row r (step_picks, collate_dev.h): lane l holds columns base + W * l + k

@@ -1,6 +1,7 @@
 // What the collates that change a row's length share on the device (collate_infill.hip, collate_corrupt.hip,
-// collate_segment.hip): the id of a column of an open row, the store of a row's tokens into int64 planes by one wave,
-// and span corruption's placement of a step's columns into both of its streams.
+// collate_segment.hip, collate_denoise.hip): the id of a column of an open row, the store of a row's tokens into
+// int64 planes by one wave, text infilling's walk over a token source, and span corruption's placement of a step's
+// columns into both of its streams.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,6 +55,35 @@ __device__ __forceinline__ bool planes_aligned(int64_t* const (&out)[N]) {
 #pragma unroll
   for (int t = 0; t < N; ++t) x |= (uintptr_t)out[t];
   return (x & 15) == 0;
+}
+
+// ------------------------------------------------------- text infilling's walk --
+// The walk of open batch row r by its wave, as the head of collate_infill.hip tells: returns e_r (wave-uniform) and,
+// with STAGE, leaves the encoder's tokens in tok[0, e_r).  e_r <= n: the caller's bound on n is the bound on what is
+// written.  at(k): the token source (word_column's); opened(j): what the run that opens at column j collapses to.
+template <bool STAGE, class At, class Opened>
+__device__ __forceinline__ int32_t infill_walk(const CollateRowsParams& P, const OpenRow& R, int64_t r, uint16_t* tok,
+                                               At at, Opened opened) {
+  const int lane = threadIdx.x & 63;
+  const int32_t n = R.L.n;
+  SpanCarry carry;
+  int32_t count = 0;
+  uint64_t last = 0;  // the last column of the step before is selected
+  for (int32_t base = 0; base < n; base += 64) {
+    const int32_t j = base + lane;
+    const WordColumn c = word_column(P, R, j, j < n, false, at);
+    const bool st[1] = {c.start}, sp[1] = {c.special};
+    bool sel[1];  // false on a special column and behind the row
+    span_select<1>(P.span, P.seed, P.counter, r, base, st, sp, carry, sel);
+    const uint64_t ms = __ballot(sel[0]);
+    const bool before = lane_in(ms << 1 | last);  // the column before this one is selected
+    const bool emit = j < n && !(sel[0] && before);
+    const uint64_t me = __ballot(emit);
+    if (STAGE && emit) tok[count + bits_below(me)] = (uint16_t)(sel[0] ? opened(j) : (int32_t)c.id);
+    count += (int32_t)__popcll(me);
+    last = ms >> 63;
+  }
+  return count;
 }
 
 // ------------------------------------------------ span corruption's placement --

@@ -165,6 +165,18 @@ def default_sentinels(vocab):
   return base, count
 
 
+def default_full_stop(vocab):
+  """The id of ``.``, which ends a sentence for ``collate_denoise`` when it is
+  given no ``full_stop``.  vocab: a token -> id mapping, or a vocabulary file.
+  Host only."""
+  if not hasattr(vocab, 'get'):
+    vocab = {t: i for i, t in enumerate(vocab_entries(vocab))}
+  stop = vocab.get('.')
+  if stop is None:
+    raise ValueError("full_stop: the vocabulary has no '.' entry to end a sentence at; pass full_stop=<id>")
+  return stop
+
+
 def span_corruption_lengths(n, noise_density=0.15, mean_span=3.0, num_sentinels=99):
   """(encoder length, decoder length, noise tokens, noise spans) of a row of n
   tokens ([CLS] and the last [SEP] included) under
@@ -838,14 +850,21 @@ class CodeCollate(_RowCollate):
     [max_seqs + 1], num_tokens / num_rows / num_seqs and ``status``."""
     return self._collate(True, res, rows, row0, n_rows, mode, (max_tokens, max_seqs, max_seqlen))
 
-  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, sentinels=None, exact=None):
+  def _infill(self, unpadded, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span, sentinels=None, exact=None,
+              denoise=None):
     """The body of the denoising objectives: text infilling, or, with
     ``sentinels`` = (base, count), span corruption, whose three C calls take the
     same arguments with the pair behind the law and a second length output;
     with ``exact`` = (noise_density, mean_span) as well, its exact-count form,
-    whose calls take that pair for the law."""
+    whose calls take that pair for the law.  ``denoise`` = (permute_ratio,
+    random_ratio, full_stop_id): BART's full objective, whose calls take the
+    triple behind the law and return what text infilling's return."""
     L, st, p, h = _lib.lib(), _stream(), _ptr, self.tok.handle
-    if sentinels is None:
+    n_lens = 1 + (sentinels is not None)
+    if denoise is not None:
+      name, who = 'lddl_collate_denoise_rows', 'collate_denoise'
+      law2 = (float(denoise[0]), float(denoise[1]), int(denoise[2]))
+    elif sentinels is None:
       name, who, law2 = 'lddl_collate_infill_rows', 'collate_infill', ()
     else:
       name, who, law2 = 'lddl_collate_corrupt_rows', 'collate_span_corruption', (int(sentinels[0]), int(sentinels[1]))
@@ -870,12 +889,12 @@ class CodeCollate(_RowCollate):
       seq = ctypes.c_int64()
       _check(L.lddl_collate_code_rows_seq_len(h, p(res.len0), p(res.len1), p(res.flags), p(rows), row0, n, res.n_pairs,
                                               self.sequence_length_alignment, ctypes.byref(seq), st))
-      out, lens = i64(4, n, int(seq.value)), torch.empty((1 + bool(law2), n), dtype=torch.int32, device=self.device)
+      out, lens = i64(4, n, int(seq.value)), torch.empty((n_lens, n), dtype=torch.int32, device=self.device)
       rc = getattr(L, name)(h, *table, int(seq.value), self.ignore_index, *law, p(out[0]), p(out[1]), p(out[2]), p(out[3]),
                             *[p(x) for x in lens], st)
       batch = {'input_ids': out[0], 'attention_mask': out[1], 'decoder_input_ids': out[2], 'labels': out[3],
                'encoder_lengths': lens[0]}
-      if law2:
+      if n_lens == 2:
         batch['decoder_lengths'] = lens[1]
     self.counter += 1
     _check(rc)
@@ -906,6 +925,34 @@ class CodeCollate(_RowCollate):
     and the decoder stream ``decoder_input_ids`` / ``decoder_position_ids`` /
     ``labels`` with ``decoder_cu_seqlens`` and ``decoder_max_seqlen``."""
     return self._infill(True, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span)
+
+  def _denoise(self, permute_sentences, random_ratio, full_stop):
+    return permute_sentences, random_ratio, default_full_stop(self.tok.vocab) if full_stop is None else int(full_stop)
+
+  def collate_denoise(self, res, rows=None, row0=0, n_rows=None, *, mask_ratio=0.3, poisson_lambda=3.0, max_span=10,
+                      permute_sentences=1.0, random_ratio=0.1, full_stop=None):
+    """A padded batch of BART's full denoising objective, under the keys of
+    ``collate_infill`` (lddl_collate_denoise_rows; include/lddl_amd.h defines
+    it).  A sentence ends at a ``full_stop`` token (None: the id of ``.`` in the
+    collate's vocabulary, and a ValueError when it has none).  Within each
+    segment ceil(m * ``permute_sentences``) of its m sentences, drawn
+    uniformly, change places in a uniformly random order; [CLS] and every [SEP]
+    stay.  Text infilling as ``collate_infill`` does it then runs over the
+    permuted row, and the [MASK] of a run becomes a random id with probability
+    ``random_ratio``, decided once per run.  ``decoder_input_ids`` and
+    ``labels`` are the row as the table holds it, so the decoder restores the
+    order as well.  Draws and the batch counter as ``collate_infill``."""
+    return self._infill(False, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span,
+                        denoise=self._denoise(permute_sentences, random_ratio, full_stop))
+
+  def collate_denoise_unpadded(self, res, rows=None, row0=0, n_rows=None, *, mask_ratio=0.3, poisson_lambda=3.0,
+                               max_span=10, permute_sentences=1.0, random_ratio=0.1, full_stop=None):
+    """``collate_denoise`` at the same seed and counter with the padding of both
+    sides dropped, bit for bit (lddl_collate_denoise_rows_cu_seqlens +
+    lddl_collate_denoise_rows_unpadded), under the keys of
+    ``collate_infill_unpadded``."""
+    return self._infill(True, res, rows, row0, n_rows, mask_ratio, poisson_lambda, max_span,
+                        denoise=self._denoise(permute_sentences, random_ratio, full_stop))
 
   def _sentinels(self, sentinels):
     if sentinels is not None:
